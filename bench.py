@@ -8,7 +8,8 @@ query upload -> fused similarity (MFMA) + DP kernel -> bounded result set -> flo
 winners -> results on the host (N > 1: + all-gather of the per-rank result sets + merge).
 
   python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5|5wrd|2f32] [--gap exp5|linear]
-                  [--locality local|global|semiglobal] [--sentences n] [--no-extra] [--scaling weak|strong]
+                  [--locality local|global|semiglobal] [--sentences n] [--scaling weak|strong]
+                  [--dump-outputs DIR] [--full [--no-extra] [--no-cpu-baseline]]
 
 N > 1 is launched by the driver as
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
@@ -17,7 +18,13 @@ rank holds its own shard of the workload's per-GPU size); the only exchange is t
 --scaling strong keeps the configuration's TOTAL fixed instead (config 3: 10 M sentences, config 5: 4 M, configs 2 / 4: 1 M;
 --sentences then names the total) and gives every rank total / N of it: the configurations at their literal sizes for every N.
 
---config picks the workload of the headline `value` (default 2); at N = 1 the other SURVEY 8(d)
+A plain run builds the headline's shard, runs W warm-up steps, times K steps (`ms_per_step` = the timed region / K) and prints
+the line.  --dump-outputs DIR then writes the result sets the last timed step returned (the merged ones with N > 1) as
+DIR/<field>.npy; the inputs are seeded, so two builds given the same arguments can be compared array for array.
+Everything else is measured only with --full: the other configurations, the CPU baseline and, where the calls in flight
+overlap on the chip, the kernel time taken one call at a time.
+
+--config picks the workload of the headline `value` (default 2); with --full at N = 1 the other SURVEY 8(d)
 configurations are then timed as well, each on its own resident corpus at its per-GPU shape, and reported
 in the same JSON line as roofline.by_config = {name: [value, kernel_ms, frac]} (the line stays under 2 KB; the long
 form -- workload texts, phases, traffic sources, every entry's full roofline -- goes to stderr and to $VK_BENCH_FULL):
@@ -199,6 +206,35 @@ def make_queries(E, ids, off, n_queries, seed, static=False, len_t=LEN_T):
 	return qs
 
 
+DUMP_BUDGET = 64 << 20
+DUMP_FIELDS = ("score", "raw_score", "sentence", "mapping", "edge_sim", "sim_rows", "plan")
+
+
+def dump_outputs(path, tops):
+	"""--dump-outputs: the result sets of one step as path/<field>.npy.  Every field holds the winners of all the step's queries
+	one after the other (each set trimmed to its n winners), n.npy the count per query.  float32 fields as returned, integer
+	fields as float64 (exact).  Should the whole exceed DUMP_BUDGET, a fixed, seeded sample of the winners is written
+	(sample_rows.npy: their indices)."""
+	os.makedirs(path, exist_ok=True)
+	out = {"n": np.array([t.n for t in tops], dtype=np.float64)}
+	for name in DUMP_FIELDS:
+		parts = [getattr(t, name, None) for t in tops]
+		if any(p is None for p in parts):
+			continue
+		a = np.concatenate([np.asarray(p[:t.n]) for p, t in zip(parts, tops)])
+		out[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+	rows = int(out["n"].sum())
+	total = sum(a.nbytes for a in out.values())
+	if total > DUMP_BUDGET and rows > 0:
+		per_row = (total - out["n"].nbytes) / rows + 8   # + its index in sample_rows
+		keep = max(1, min(rows, int((DUMP_BUDGET - out["n"].nbytes) // per_row)))
+		idx = np.sort(np.random.default_rng(20240601).choice(rows, size=keep, replace=False))
+		out = {k: (a if k == "n" else a[idx]) for k, a in out.items()}
+		out["sample_rows"] = idx.astype(np.float64)
+	for name, a in out.items():
+		np.save(os.path.join(path, name + ".npy"), a)
+
+
 def usable_cores():
 	"""host cores this process may actually run on: the affinity mask and the cgroup CPU quota, not the machine's count"""
 	n = os.cpu_count() or 1
@@ -310,6 +346,7 @@ class Runner:
 		self.gather_batch = max(1, int(os.environ.get("VK_BENCH_GATHER_BATCH", "4")))   # result sets of this many queries travel in one all-gather
 		self.gather_depth = int(os.environ.get("VK_BENCH_GATHER_DEPTH", "1"))   # a collective gets this many further exchanges to complete before anyone waits for it
 		self.submitted = 0
+		self.last_tops, self.last_merged = None, None   # the result sets of the step retired last (with ranks: of the last exchange)
 		self.score_ms, self.phases, self.retired_at, self.median_gap_ms, self.gap_min_max_ms = [], [], [], None, None
 		gs, gt, _ = gap_spec(gap_name or spec["gap"], spec["max_len"])
 		alg = {"align": core.VK_ALG_ALIGN, "rwmd": core.VK_ALG_RWMD, "wrd": core.VK_ALG_WRD}[spec["alg"]]
@@ -337,10 +374,11 @@ class Runner:
 
 	def _drain(self, keep=0):
 		while len(self.pending) > keep:
-			self.shards.allgather_finish(self.pending.pop(0))   # global top-k of earlier queries on every rank
+			self.last_merged = self.shards.allgather_finish(self.pending.pop(0))   # global top-k of earlier queries on every rank
 
 	def _retire(self):
 		tops, ph = self.inflight.pop(0).result()
+		self.last_tops = tops
 		self.retired_at.append(time.perf_counter())
 		self.score_ms.append(ph["score_ms"])
 		self.phases.append(ph)
@@ -401,6 +439,13 @@ class Runner:
 			print(f"[trace] {self.spec['name']}: {steps} steps, median gap {np.median(gaps):.2f} ms, longest " +
 				", ".join(f"{gaps[i]:.1f} ms at step {i}" for i in top), file=sys.stderr)
 		return elapsed
+
+	def last_step(self):
+		"""the result sets the last step handed its caller: its own, or with several ranks the merged ones of its queries (the
+		last entries of the last exchange)"""
+		if self.dist is None:
+			return list(self.last_tops)
+		return list(self.last_merged)[-len(self.last_tops):]
 
 	def close(self):
 		self.pool.shutdown()
@@ -494,10 +539,14 @@ def main():
 	ap.add_argument("--gap", choices=["exp5", "linear"], default=None, help="gap costs of the headline alignment workload (default: the config's)")
 	ap.add_argument("--locality", choices=sorted(LOCALITIES), default=None, help="locality of the headline alignment workload (default: the config's)")
 	ap.add_argument("--sentences", type=int, default=0, help="sentences per GPU of the headline workload (default: the config's per-GPU size)")
-	ap.add_argument("--no-cpu-baseline", action="store_true")
+	ap.add_argument("--full", action="store_true", help="measure beyond the headline: the other configurations (N = 1), the CPU "
+		"baseline, kernel times taken one call at a time where calls in flight overlap; a plain run times the headline only")
+	ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the result sets of the last "
+		"timed step as DIR/<field>.npy (float32 / float64)")
+	ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
 	ap.add_argument("--no-pipeline", action="store_true", help="one handle, one query at a time")
-	ap.add_argument("--no-extra", action="store_true", help="headline workload only (no \"configs\" object)")
-	ap.add_argument("--extra", default="4,4static,3,2f32,2static,2shared,2q40,5,5wrd,5rwmd,docs,docslin,mid", help="the other configurations timed at N = 1 after the headline")
+	ap.add_argument("--no-extra", action="store_true", help="with --full: headline workload only (no \"configs\" object)")
+	ap.add_argument("--extra", default="4,4static,3,2f32,2static,2shared,2q40,5,5wrd,5rwmd,docs,docslin,mid", help="the other configurations timed at N = 1 after the headline (--full)")
 	ap.add_argument("--scaling", choices=["weak", "strong"], default="weak", help="weak: every rank holds the configuration's per-GPU shard; "
 		"strong: the configuration's total (config 3: 10 M, config 5: 4 M sentences) is divided among the ranks")
 	ap.add_argument("--extra-steps", type=int, default=12)
@@ -508,6 +557,8 @@ def main():
 		"sharded path (per-rank result sets, all-gather, merge) and rank 0 compares the merged result set with the answer of ONE corpus "
 		"holding all ranks' shards (\"selfcheck\" in the JSON line)")
 	args = ap.parse_args()
+	if args.steps < 1 or args.warmup < 0:
+		ap.error("--steps must be at least 1 and --warmup at least 0")
 
 	import torch
 	from vectorian_amd import core
@@ -565,8 +616,9 @@ def main():
 
 	n_handles = 1 if args.no_pipeline else max(1, int(os.environ.get("VK_BENCH_HANDLES", "2")))
 
-	def measure(key, n_sent, warmup, steps, use_dist, gap=None, locality=None, keep=None):
-		"""builds (or takes over) the resident shard of a workload, runs warmup + steps, returns the report entry"""
+	def measure(key, n_sent, warmup, steps, use_dist, gap=None, locality=None, keep=None, dump=None):
+		"""builds (or takes over) the resident shard of a workload, runs warmup + steps, returns the report entry; dump: a
+		directory for the result sets of the last timed step (rank 0 writes them)"""
 		spec = dict(WORKLOADS[key])
 		if gap and spec["alg"] == "align":
 			spec["gap"] = gap
@@ -599,11 +651,14 @@ def main():
 		r = Runner(core, torch, corpus, spec, n_sent, use_dist, xdev, rank, n_handles)
 		try:
 			elapsed = r.run(queries, warmup, steps)
+			if dump and rank == 0:
+				dump_outputs(dump, r.last_step())
 		finally:
 			r.close()
 		kernel_alone_ms = None
 		shared_pass = spec["alg"] == "align" and batch > 0
-		if (spec["alg"] == "wrd" and n_handles > 1) or shared_pass:
+		overlapped = (spec["alg"] == "wrd" and n_handles > 1) or shared_pass
+		if overlapped and args.full:
 			# The bound passes of the queries in flight do not take turns (vk_query.cpp: two passes sharing the chip fill each
 			# other's epilogue gaps), so a launch's own events span the work of its neighbours too.  The kernel's duration for the
 			# roofline is taken one query at a time, in the same process, right after the timed region.
@@ -635,6 +690,9 @@ def main():
 		if kernel_alone_ms is not None:
 			entry["roofline"]["kernel_ms_note"] = ("one call at a time (4 after the timed region); with several in flight the passes "
 				f"overlap on the chip and a call's own events span {float(np.mean(r.score_ms)):.2f} ms")
+		elif overlapped:
+			entry["roofline"]["kernel_ms_note"] = ("events of the calls in flight, whose passes overlap on the chip and span each "
+				"other's work (--full times one call at a time)")
 		return spec, entry
 
 	keep = {}
@@ -645,7 +703,8 @@ def main():
 		n_sent = max(1, total // world)
 	else:
 		n_sent = args.sentences or head["n_sent"]
-	spec, entry = measure(args.config, n_sent, args.warmup, args.steps, dist, gap=args.gap, locality=args.locality, keep=keep)
+	spec, entry = measure(args.config, n_sent, args.warmup, args.steps, dist, gap=args.gap, locality=args.locality, keep=keep,
+		dump=args.dump_outputs)
 	traffic, traffic_source = traffic_of(spec["name"], spec["gap"], n_sent, head["n_sent"])
 	if entry["roofline"]["bound"] != "hbm":
 		traffic, traffic_source = None, None
@@ -724,7 +783,7 @@ def main():
 		full["phases_ms_mean"] = entry["phases_ms_mean"]
 
 	# ---- the other SURVEY 8(d) configurations, one GPU, each on its own resident corpus --------------------------
-	if world == 1 and dist is None and not args.no_extra:
+	if args.full and world == 1 and dist is None and not args.no_extra:
 		configs = {}
 		for key in [k for k in args.extra.split(",") if k and k in WORKLOADS and k != args.config]:
 			w = WORKLOADS[key]
@@ -763,7 +822,7 @@ def main():
 		torch.cuda.empty_cache()
 
 	if rank == 0:
-		if not args.no_cpu_baseline and world == 1:
+		if args.full and not args.no_cpu_baseline and world == 1:
 			cb = cpu_baseline(spec)
 			full["cpu_baseline"] = cb
 			out["cpu_baseline"] = {k_: (round(v_, 1) if isinstance(v_, float) else v_) for k_, v_ in cb.items() if k_ != "blas_note"}

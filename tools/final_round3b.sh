@@ -7,7 +7,7 @@ out=$root/gpurun_out/final
 mkdir -p "$out"
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > "$out/gputest.log" 2>&1
 tail -n 2 "$out/gputest.log"
-VK_BENCH_FULL=$out/bench_default_full.json timeout -k 10 400 python bench.py > "$out/bench_default.json" 2> "$out/bench_default.err"
+VK_BENCH_FULL=$out/bench_default_full.json timeout -k 10 400 python bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err"
 tail -c 600 "$out/bench_default.json"
 timeout -k 10 300 python tools/bench_documents.py > "$out/bench_documents.jsonl" 2> "$out/bench_documents.err"
 timeout -k 10 300 python tools/bench_documents.py --oracle-docs 0 --docs 20 --short 400000 --strategies linear,wsb,rwmd >> "$out/bench_documents.jsonl" 2>> "$out/bench_documents.err"

@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 cd /tmp
 for set in "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU" "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_MISC SQ_WAVE_CYCLES" "SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES"; do
 	name=$(echo $set | tr ' ' '_' | cut -c1-40)
-	rocprofv3 --kernel-trace --pmc $set --output-format csv -d "$out/c4_$name" -- python3 "$root/bench.py" --config 4 --steps 3 --warmup 2 --no-extra --no-cpu-baseline > "$out/c4_$name.log" 2>&1
+	rocprofv3 --kernel-trace --pmc $set --output-format csv -d "$out/c4_$name" -- python3 "$root/bench.py" --config 4 --steps 3 --warmup 2 --full --no-extra --no-cpu-baseline > "$out/c4_$name.log" 2>&1
 	rocprofv3 --kernel-trace --pmc $set --output-format csv -d "$out/q40_$name" -- python3 "$root/tools/bench_configs.py" --alg align --gap exp5 --len-t 40 --sentences 1000000 --steps 3 --warmup 2 > "$out/q40_$name.log" 2>&1
 done
 cd "$root"

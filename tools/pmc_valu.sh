@@ -13,8 +13,8 @@ mkdir -p "$out"
 export TMPDIR=/tmp
 cd /tmp
 for c in $configs; do
-	VK_BENCH_FULL="$out/full_$c.json" rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d "$out/pmc_$c" -- python3 "$root/bench.py" --config $c --steps 4 --warmup 2 --no-extra --no-cpu-baseline > "$out/pmc_$c.log" 2>&1
-	rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats_$c" -- python3 "$root/bench.py" --config $c --steps 12 --warmup 4 --no-extra --no-cpu-baseline > "$out/bench_$c.log" 2>&1
+	VK_BENCH_FULL="$out/full_$c.json" rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d "$out/pmc_$c" -- python3 "$root/bench.py" --config $c --steps 4 --warmup 2 --full --no-extra --no-cpu-baseline > "$out/pmc_$c.log" 2>&1
+	rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats_$c" -- python3 "$root/bench.py" --config $c --steps 12 --warmup 4 --full --no-extra --no-cpu-baseline > "$out/bench_$c.log" 2>&1
 	f=$(find "$out/stats_$c" -name "*kernel_stats.csv" | head -n 1)
 	head -n 8 "$f" > "$out/${tag}_kernel_stats_config$c.csv"
 	tail -n 1 "$out/bench_$c.log" | cut -c1-400

@@ -13,7 +13,7 @@ mkdir -p "$out/summary"
 export TMPDIR=/tmp
 cd /tmp
 for c in $configs; do
-	rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats_$c" -- python3 "$root/bench.py" --config $c --steps 12 --warmup 4 --no-extra --no-cpu-baseline > "$out/bench_$c.log" 2>&1
+	rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats_$c" -- python3 "$root/bench.py" --config $c --steps 12 --warmup 4 --full --no-extra --no-cpu-baseline > "$out/bench_$c.log" 2>&1
 	tail -n 1 "$out/bench_$c.log" | cut -c1-600
 	f=$(find "$out/stats_$c" -name "*kernel_stats.csv" | head -n 1)
 	head -n 8 "$f" > "$out/summary/${tag}_kernel_stats_config$c.csv"
@@ -22,11 +22,11 @@ done
 # HBM traffic of the scoring kernel, every HBM-bound configuration: FETCH_SIZE and WRITE_SIZE in passes of their own
 for c in $configs; do
 	case $c in 4|2static|5rwmd) continue;; esac
-	rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$out/pmc_fetch_$c" -- python3 "$root/bench.py" --config $c --steps 4 --warmup 2 --no-extra --no-cpu-baseline > "$out/pmc_fetch_$c.log" 2>&1
-	rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$out/pmc_write_$c" -- python3 "$root/bench.py" --config $c --steps 4 --warmup 2 --no-extra --no-cpu-baseline > "$out/pmc_write_$c.log" 2>&1
+	rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$out/pmc_fetch_$c" -- python3 "$root/bench.py" --config $c --steps 4 --warmup 2 --full --no-extra --no-cpu-baseline > "$out/pmc_fetch_$c.log" 2>&1
+	rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$out/pmc_write_$c" -- python3 "$root/bench.py" --config $c --steps 4 --warmup 2 --full --no-extra --no-cpu-baseline > "$out/pmc_write_$c.log" 2>&1
 done
 if echo " $configs " | grep -q " 4 "; then
-	rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_BF16 --output-format csv -d "$out/pmc_mfma" -- python3 "$root/bench.py" --config 4 --steps 3 --warmup 2 --no-extra --no-cpu-baseline > "$out/pmc_mfma.log" 2>&1
+	rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_BF16 --output-format csv -d "$out/pmc_mfma" -- python3 "$root/bench.py" --config 4 --steps 3 --warmup 2 --full --no-extra --no-cpu-baseline > "$out/pmc_mfma.log" 2>&1
 	python3 "$root/tools/summarize_mfma.py" "$out/pmc_mfma" "$out/summary/${tag}_pmc_config4_mfma.csv"
 fi
 cd "$root"
