@@ -63,20 +63,11 @@ static int batch_winner_rows(vk_corpus *c, const vk_query_desc *qs, int n_querie
 	auto stamp = [&](const char *what) {
 		if (trace) fprintf(stderr, "[vk] batch_winner_rows %s: %.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
 	};
-	if (c->bqt_cap < (size_t)n_queries) {
-		if (c->d_bqt) { VK_HIP(hipFree(c->d_bqt)); c->d_bqt = nullptr; }
-		if ((rc = alloc_t(c, &c->d_bqt, (size_t)n_queries * c->tile_bytes))) return rc;
-		c->bqt_cap = (size_t)n_queries;
-	}
+	if ((rc = c->d_bqt.reserve((size_t)n_queries * c->tile_bytes, &c->device_bytes))) return rc;
 	const size_t cap_cand = (size_t)n_queries * (size_t)kk;   // buffers for the most a batch of this shape can ask for: no regrowth from batch to batch
-	if (c->bcand_cap < cap_cand) {
-		for (void *ptr : {(void *)c->d_bcand, (void *)c->d_bcandq, (void *)c->d_brows}) if (ptr) VK_HIP(hipFree(ptr));
-		c->d_bcand = nullptr; c->d_bcandq = nullptr; c->d_brows = nullptr;
-		if ((rc = alloc_t(c, &c->d_bcand, cap_cand))) return rc;
-		if ((rc = alloc_t(c, &c->d_bcandq, cap_cand))) return rc;
-		if ((rc = alloc_t(c, &c->d_brows, cap_cand * 64 * 16))) return rc;
-		c->bcand_cap = cap_cand;
-	}
+	if ((rc = c->d_bcand.reserve(cap_cand, &c->device_bytes))) return rc;
+	if ((rc = c->d_bcandq.reserve(cap_cand, &c->device_bytes))) return rc;
+	if ((rc = c->d_brows.reserve(cap_cand * 64 * 16, &c->device_bytes))) return rc;
 	std::vector<uint8_t> &qt = keep.vec<uint8_t>(), one;
 	std::vector<uint64_t> &hk = keep.vec<uint64_t>(n_cand, 0);
 	std::vector<int32_t> &hq = keep.vec<int32_t>(n_cand, 0);
@@ -86,11 +77,7 @@ static int batch_winner_rows(vk_corpus *c, const vk_query_desc *qs, int n_querie
 	if (is_static) {
 		for (int i = 0; i < n_queries; i++)
 			for (int j = 0; j < qs[i].len_t && j < 16 && qs[i].q_token_ids; j++) hids[(size_t)i * 16 + j] = qs[i].q_token_ids[j];
-		if (c->bqids_cap < hids.size()) {
-			if (c->d_bqids) { VK_HIP(hipFree(c->d_bqids)); c->d_bqids = nullptr; c->bqids_cap = 0; }
-			if ((rc = alloc_t(c, &c->d_bqids, hids.size()))) return rc;
-			c->bqids_cap = hids.size();
-		}
+		if ((rc = c->d_bqids.reserve(hids.size(), &c->device_bytes))) return rc;
 		VK_HIP(hipMemcpyAsync(c->d_bqids, hids.data(), hids.size() * 4, hipMemcpyHostToDevice, st));
 	}
 	float mags[VK_MAX_QUERY_LEN];
@@ -120,12 +107,8 @@ static int batch_winner_rows(vk_corpus *c, const vk_query_desc *qs, int n_querie
 	VK_HIP(vk_launch_rows(&w, (int32_t)n_cand, st));
 	// one copy into pinned host memory, then into the callers' arrays (copies into pageable memory go through the runtime's
 	// staging: 256 of them, one per query, took 5 - 30 ms; a zero-initialised std::vector as the bounce buffer 3 ms)
-	const size_t bytes = n_cand * 64 * 16 * 4, cap_bytes = cap_cand * 64 * 16 * 4;
-	if (c->h_brows_cap < cap_bytes) {
-		if (c->h_brows) { VK_HIP(hipHostFree(c->h_brows)); c->h_brows = nullptr; c->h_brows_cap = 0; }
-		VK_HIP(hipHostMalloc((void **)&c->h_brows, cap_bytes, hipHostMallocDefault));
-		c->h_brows_cap = cap_bytes;
-	}
+	const size_t bytes = n_cand * 64 * 16 * 4;
+	if ((rc = c->h_brows.reserve(cap_cand * 64 * 16, nullptr))) return rc;
 	stamp("kernel issued");
 	VK_HIP(hipMemcpyAsync(c->h_brows, c->d_brows, bytes, hipMemcpyDeviceToHost, st));
 	VK_HIP(hipStreamSynchronize(st));
@@ -274,45 +257,29 @@ static int query_batch_shared_pass(vk_corpus_t *c, const vk_query_desc *qs, int3
 
 	// ---- buffers
 	const size_t need_q = (size_t)4 * c->tile_bytes;
-	if (c->bq_cap < need_q) {
-		if (c->d_bq) VK_HIP(hipFree(c->d_bq));
-		if ((rc = alloc_t(c, &c->d_bq, need_q))) return rc;
-		c->bq_cap = need_q;
-	}
-	if (c->bqlen_cap < 16) {
-		if (c->d_bqlen) VK_HIP(hipFree(c->d_bqlen));
-		if ((rc = alloc_t(c, &c->d_bqlen, 16))) return rc;
-		c->bqlen_cap = 16;
-	}
+	if ((rc = c->d_bq.reserve(need_q, &c->device_bytes))) return rc;
+	if ((rc = c->d_bqlen.reserve(16, &c->device_bytes))) return rc;
 	const size_t need_s = (size_t)4 * (size_t)n;
-	if (c->bscores_cap < need_s) {
-		if (c->d_bscores) VK_HIP(hipFree(c->d_bscores));
-		if ((rc = alloc_t(c, &c->d_bscores, need_s))) return rc;
-		c->bscores_cap = need_s;
-	}
-	if (c->braw_cap < need_s) {
-		if (c->d_braw) VK_HIP(hipFree(c->d_braw));
-		if ((rc = alloc_t(c, &c->d_braw, need_s))) return rc;
-		c->braw_cap = need_s;
-	}
+	if ((rc = c->d_bscores.reserve(need_s, &c->device_bytes))) return rc;
+	if ((rc = c->d_braw.reserve(need_s, &c->device_bytes))) return rc;
 	const int64_t nw1 = (n + 4095) / 4096;
 	const size_t need_k = (size_t)4 * (size_t)nw1 * (size_t)kk;
-	if (c->bkeys_cap < need_k) {
-		for (auto &b : c->d_bkeys) if (b) VK_HIP(hipFree(b));
-		if ((rc = alloc_t(c, &c->d_bkeys[0], need_k))) return rc;
-		if ((rc = alloc_t(c, &c->d_bkeys[1], need_k))) return rc;
-		c->bkeys_cap = need_k;
-	}
+	for (auto &b : c->d_bkeys) if ((rc = b.reserve(need_k, &c->device_bytes))) return rc;
+	// the winners' tracebacks of one pass: qb_max x kk slots, 16 columns each
+	if ((rc = c->d_out_raw.reserve((size_t)qb_max * kk, &c->device_bytes))) return rc;
+	if ((rc = c->d_out_sim.reserve((size_t)qb_max * kk * 16, &c->device_bytes))) return rc;
+	if ((rc = c->d_out_map.reserve((size_t)qb_max * kk * 16, &c->device_bytes))) return rc;
+	if ((rc = c->d_ws.reserve(kGapTable, &c->device_bytes))) return rc;
 	VK_HIP(hipMemcpyAsync(c->d_ws, ws, kGapTable * sizeof(float), hipMemcpyHostToDevice, st));
 	VK_HIP(hipMemcpyAsync(c->d_wt, wt, 160 * sizeof(float), hipMemcpyHostToDevice, st));
 	if (q0.boost) {
-		if (!c->d_boost) { rc = alloc_t(c, &c->d_boost, (size_t)n + 8); if (rc) return rc; }
+		if ((rc = c->d_boost.reserve((size_t)n + 8, &c->device_bytes))) return rc;
 		VK_HIP(hipMemcpyAsync(c->d_boost, q0.boost, (size_t)n * 4, hipMemcpyHostToDevice, st));   // no long slices: rows == slices
 	}
 	p.tiles = c->d_tiles; p.sent_start = c->d_sent_start; p.sent_end = c->d_sent_end; p.n_sent = (int32_t)n;
 	p.nk32 = c->nk32; p.tail = c->tail; p.tile_bytes = c->tile_bytes;
 	p.qtiles = c->d_bq; p.locality = q0.locality; p.ws = c->d_ws; p.wt = c->d_wt + 80; p.wt0 = c->d_wt;
-	p.boost = q0.boost ? c->d_boost : nullptr; p.scores = c->d_bscores; p.raw = c->d_braw;
+	p.boost = q0.boost ? (float *)c->d_boost : nullptr; p.scores = c->d_bscores; p.raw = c->d_braw;
 	if (q0.want_flow && q0.algorithm == VK_ALG_ALIGN) p.raw = nullptr;   // the flow kernel restates the winners' aligner scores; nothing else reads the array (no submatch weights here)
 
 	float score_ms_total = 0.0f, total_ms = 0.0f;
@@ -465,9 +432,9 @@ static int build_batch_layout(vk_corpus *c, int gran) {
 		const int tps = (b + 1) * gran;
 		int rc;
 		const size_t bytes = ((size_t)B.n * tps + 1) * (size_t)c->tile_bytes;   // one zero tile follows (the kernel reads it for the last, partly filled chunk)
-		if ((rc = alloc_t(c, &B.tiles, bytes))) return rc;
-		if ((rc = alloc_t(c, &B.len, (size_t)B.n))) return rc;
-		if ((rc = alloc_t(c, &B.id, (size_t)B.n))) return rc;
+		if ((rc = B.tiles.reserve(bytes, &c->device_bytes))) return rc;
+		if ((rc = B.len.reserve((size_t)B.n, &c->device_bytes))) return rc;
+		if ((rc = B.id.reserve((size_t)B.n, &c->device_bytes))) return rc;
 		VK_HIP(hipMemsetAsync(B.tiles + (size_t)B.n * tps * c->tile_bytes, 0, (size_t)c->tile_bytes, c->stream));
 		VK_HIP(hipMemcpy(B.len, lens[b].data(), (size_t)B.n * 4, hipMemcpyHostToDevice));   // (blocking: the host vectors are this function's)
 		VK_HIP(hipMemcpy(B.id, ids[b].data(), (size_t)B.n * 4, hipMemcpyHostToDevice));
@@ -550,23 +517,11 @@ static int query_batch_body(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_q
 	// ---- device buffers (kept for the next batch)
 	// (+1: the kernel prefetches one tile past the last)
 	const size_t need_q = std::max((size_t)n_queries * c->tile_bytes, b32 ? (size_t)(n_qtiles + 1) * nk16 * 1024 : (size_t)0);
-	if (c->bq_cap < need_q) {
-		if (c->d_bq) VK_HIP(hipFree(c->d_bq));
-		if ((rc = alloc_t(c, &c->d_bq, need_q))) return rc;
-		c->bq_cap = need_q;
-	}
+	if ((rc = c->d_bq.reserve(need_q, &c->device_bytes))) return rc;
 	const size_t need_len = 2 * ((size_t)n_queries + 4) + std::max(8 * ((size_t)n_qtiles + 2), 32 * ((size_t)n_super + 1));   // lengths, their reciprocals, kernel parameters
-	if (c->bqlen_cap < need_len) {
-		if (c->d_bqlen) VK_HIP(hipFree(c->d_bqlen));
-		if ((rc = alloc_t(c, &c->d_bqlen, need_len))) return rc;
-		c->bqlen_cap = need_len;
-	}
+	if ((rc = c->d_bqlen.reserve(need_len, &c->device_bytes))) return rc;
 	const size_t need_s = (size_t)score_rows * (size_t)n;
-	if (c->bscores_cap < need_s) {
-		if (c->d_bscores) VK_HIP(hipFree(c->d_bscores));
-		if ((rc = alloc_t(c, &c->d_bscores, need_s))) return rc;
-		c->bscores_cap = need_s;
-	}
+	if ((rc = c->d_bscores.reserve(need_s, &c->device_bytes))) return rc;
 	// with flows: k + 8 candidates per query, restated on the host from their canonical rows; the k best are kept (batch_winner_rows)
 	bool canon_tr = qs[0].want_flow != 0;
 	for (int i = 0; i < n_queries; i++) canon_tr = canon_tr && outs[i].sim_rows != nullptr;
@@ -574,12 +529,7 @@ static int query_batch_body(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_q
 	const float sel_floor = canon_tr ? qs[0].min_score - 1e-5f * std::max(1.0f, std::fabs(qs[0].min_score)) : qs[0].min_score;
 	const int64_t nw1 = (n + 4095) / 4096;
 	const size_t need_k = (size_t)n_queries * (size_t)nw1 * (size_t)kk;
-	if (c->bkeys_cap < need_k) {
-		for (auto &b : c->d_bkeys) if (b) VK_HIP(hipFree(b));
-		if ((rc = alloc_t(c, &c->d_bkeys[0], need_k))) return rc;
-		if ((rc = alloc_t(c, &c->d_bkeys[1], need_k))) return rc;
-		c->bkeys_cap = need_k;
-	}
+	for (auto &b : c->d_bkeys) if ((rc = b.reserve(need_k, &c->device_bytes))) return rc;
 
 	VK_HIP(hipEventRecord(c->ev[0], st));
 	std::vector<uint8_t> &all = keep.vec<uint8_t>((size_t)need_q, 0);
@@ -667,7 +617,7 @@ static int query_batch_body(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_q
 	}
 	if (b32) VK_HIP(hipMemcpyAsync(d_qparam, qparam.data(), qparam.size() * 4, hipMemcpyHostToDevice, st));
 	if (qs[0].boost) {
-		if (!c->d_boost) { rc = alloc_t(c, &c->d_boost, (size_t)n + 8); if (rc) return rc; }
+		if ((rc = c->d_boost.reserve((size_t)n + 8, &c->device_bytes))) return rc;
 		VK_HIP(hipMemcpyAsync(c->d_boost, qs[0].boost, (size_t)n * 4, hipMemcpyHostToDevice, st));
 	}
 
@@ -682,7 +632,7 @@ static int query_batch_body(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_q
 	p.qtiles = c->d_bq; p.q_len = c->d_bqlen; p.n_queries = n_queries; p.n_sent = (int32_t)n;
 	p.tiles_per_sent = c->uniform_len / 16;
 	p.symmetric = qs[0].rwmd_symmetric; p.nbow = qs[0].rwmd_normalize_bow;
-	p.boost = qs[0].boost ? c->d_boost : nullptr;
+	p.boost = qs[0].boost ? (float *)c->d_boost : nullptr;
 	p.scores = c->d_bscores;
 	p.n_qtiles = n_qtiles; p.qpt = qpt; p.q_inv_len = d_qinv; p.q_param = d_qparam; p.dense = dense ? 1 : 0;
 	p.late_mask = wide32 ? 0 : 4;   // waves w and w + 4 of a workgroup share a SIMD (768-d rows: one wave per SIMD, nobody to alternate with)
@@ -692,11 +642,7 @@ static int query_batch_body(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_q
 		const int64_t v_rows = (int64_t)((c->n_tiles + 1) / 2) * 32;
 		const int64_t table_row = (int64_t)n_qtiles * 32;
 		const size_t need_t = (size_t)v_rows * (size_t)table_row;
-		if (c->btable_cap < need_t) {
-			if (c->d_btable) { VK_HIP(hipFree(c->d_btable)); c->d_btable = nullptr; c->btable_cap = 0; }
-			if ((rc = alloc_t(c, &c->d_btable, need_t))) return rc;
-			c->btable_cap = need_t;
-		}
+		if ((rc = c->d_btable.reserve(need_t, &c->device_bytes))) return rc;
 		// sim[id(t_j)][j] = 1 for every query token the vocabulary holds (metric/static.cpp:58-67), after the clip as there
 		std::vector<int64_t> &fix = keep.vec<int64_t>();
 		for (int i = 0; i < n_queries; i++)
@@ -707,11 +653,7 @@ static int query_batch_body(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_q
 				slot_of(i, j, tile, hd, acc);
 				fix.push_back((int64_t)id * table_row + (int64_t)tile * 32 + hd * 16 + acc);
 			}
-		if (c->bfix_cap < fix.size()) {
-			if (c->d_bfix) { VK_HIP(hipFree(c->d_bfix)); c->d_bfix = nullptr; c->bfix_cap = 0; }
-			if ((rc = alloc_t(c, &c->d_bfix, fix.size() + 16))) return rc;
-			c->bfix_cap = fix.size() + 16;
-		}
+		if ((rc = c->d_bfix.reserve(fix.size() + 16, &c->device_bytes))) return rc;
 		if (!fix.empty()) VK_HIP(hipMemcpyAsync(c->d_bfix, fix.data(), fix.size() * 8, hipMemcpyHostToDevice, st));
 		VK_HIP(vk_launch_table_batch(c->d_tiles, c->n_tiles, c->tile_bytes, nk16, c->d_bq, n_qtiles, c->d_btable, st));
 		VK_HIP(vk_launch_table_batch_fix(c->d_btable, c->d_bfix, (int32_t)fix.size(), st));
@@ -719,7 +661,7 @@ static int query_batch_body(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_q
 		p.table = c->d_btable; p.table_row = table_row; p.zero_row = (int32_t)((c->n_tiles - 1) * 16);   // the zero tile behind the vocabulary
 		if (stat_uniform32) VK_HIP(vk_launch_rwmd_static32(&p, 0, st));
 		else {
-			if (c->sb_empty > 0) VK_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_bscores), (int)0xff800000u, (size_t)score_rows * (size_t)n, st));   // -inf: empty slices
+			if (c->sb_empty > 0) VK_HIP(hipMemsetD32Async(static_cast<hipDeviceptr_t>(c->d_bscores), (int)0xff800000u, (size_t)score_rows * (size_t)n, st));   // -inf: empty slices
 			for (int b = 0; b < 2; b++) {
 				if (c->sb_n[b] == 0) continue;
 				VkRwmdBatchParams pb = p;
@@ -731,7 +673,7 @@ static int query_batch_body(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_q
 	else if (b32 && !r32) VK_HIP(vk_launch_rwmd_batch32(&p, st));
 	else if (uniform16) VK_HIP(vk_launch_rwmd_batch(&p, st));
 	else {
-		if (c->bl_empty > 0) VK_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_bscores), (int)0xff800000u, (size_t)n_queries * (size_t)n, st));   // -inf: empty slices
+		if (c->bl_empty > 0) VK_HIP(hipMemsetD32Async(static_cast<hipDeviceptr_t>(c->d_bscores), (int)0xff800000u, (size_t)n_queries * (size_t)n, st));   // -inf: empty slices
 		for (int b = 0; b < 4; b++) {
 			const auto &B = c->bl[b];
 			if (B.n == 0) continue;
@@ -816,7 +758,7 @@ static int build_static_buckets(vk_corpus *c) {
 		c->sb_n[b] = (int64_t)ids[b].size();
 		if (c->sb_n[b] == 0) continue;
 		int rc;
-		if ((rc = alloc_t(c, &c->d_sb_id[b], ids[b].size()))) return rc;
+		if ((rc = c->d_sb_id[b].reserve(ids[b].size(), &c->device_bytes))) return rc;
 		VK_HIP(hipMemcpy(c->d_sb_id[b], ids[b].data(), ids[b].size() * 4, hipMemcpyHostToDevice));   // (blocking: the host vector is this function's)
 	}
 	c->sb_built = true;

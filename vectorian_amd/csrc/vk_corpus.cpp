@@ -28,6 +28,43 @@ vk_devblock::~vk_devblock() {
 	for (void *p : ptrs) if (p) (void)hipFree(p);
 }
 
+// vk_devbuf.h's allocator: device memory, or pinned host memory for staging
+int vk_devbuf_alloc(void **p, size_t bytes, bool pinned) {
+	if (pinned) VK_HIP(hipHostMalloc(p, bytes, hipHostMallocDefault));
+	else VK_HIP(hipMalloc(p, bytes));
+	return VK_OK;
+}
+
+void vk_devbuf_free(void *p, bool pinned) {
+	if (pinned) (void)hipHostFree(p);
+	else (void)hipFree(p);   // synchronises the device: a query before may still be reading the workspace
+}
+
+// The workspaces every handle starts with: the query's tiles and small tables, the winners' outputs (grown on demand by the queries)
+static int reserve_query_workspaces(vk_corpus *c) {
+	int rc;
+	int64_t *live = &c->device_bytes;
+	if (c->desc.layout == VK_LAYOUT_STATIC && (rc = c->d_table.reserve((size_t)c->n_tiles * 16 * 16 * 4, live))) return rc;   // one [V_pad x 16] table per query tile
+	if ((rc = c->d_qtile.reserve((size_t)c->tile_bytes * 4, live))) return rc;   // up to 4 tiles of 16 query rows
+	if ((rc = c->d_ws.reserve(kGapTable, live))) return rc;
+	if ((rc = c->d_wt.reserve(160, live))) return rc;
+	if ((rc = c->d_qids.reserve(80, live))) return rc;
+	if ((rc = c->d_out_raw.reserve(VK_MAX_MATCHES, live))) return rc;
+	if ((rc = c->d_out_sim.reserve((size_t)VK_MAX_MATCHES * 64, live))) return rc;
+	return c->d_out_map.reserve((size_t)VK_MAX_MATCHES * 64, live);
+}
+
+// ... and those sized by the slice table: scores of every row, keys of the block selection
+static int reserve_table_workspaces(vk_corpus *c, int64_t n_entries) {
+	int rc;
+	int64_t *live = &c->device_bytes;
+	if ((rc = c->d_scores.reserve((size_t)n_entries + 8, live))) return rc;
+	if ((rc = c->d_raw.reserve((size_t)n_entries + 8, live))) return rc;
+	const size_t nblk = (size_t)((n_entries + kTopkChunk - 1) / kTopkChunk) + 1;
+	if ((rc = c->d_keys[0].reserve(nblk * VK_MAX_MATCHES + kTopkChunk, live))) return rc;
+	return c->d_keys[1].reserve((nblk * VK_MAX_MATCHES) / 2 + 2 * kTopkChunk, live);
+}
+
 int vk_wait_peer_turn(vk_corpus *c, hipStream_t st) {
 	std::lock_guard<std::mutex> g(vk_ring_mutex());
 	vk_corpus *p = c->peer;
@@ -102,15 +139,8 @@ int vk_corpus_create(const vk_corpus_desc *desc, vk_corpus_t **out) {
 		if (desc->keep_magnitudes && (rc = alloc_shared(c, &c->d_mag, (size_t)c->rows_total + 16))) break;
 		if (desc->layout == VK_LAYOUT_STATIC) {
 			if ((rc = alloc_shared(c, &c->d_tok_id, (size_t)desc->n_tokens + 64))) break;
-			if ((rc = alloc_t(c, &c->d_table, (size_t)c->n_tiles * 16 * 16 * 4))) break;   // one [V_pad x 16] table per query tile
 		}
-		if ((rc = alloc_t(c, &c->d_qtile, (size_t)c->tile_bytes * 4))) break;   // up to 4 tiles of 16 query rows
-		if ((rc = alloc_t(c, &c->d_ws, kGapTable))) break;
-		if ((rc = alloc_t(c, &c->d_wt, 160))) break;
-		if ((rc = alloc_t(c, &c->d_qids, 80))) break;
-		if ((rc = alloc_t(c, &c->d_out_raw, VK_MAX_MATCHES))) break;
-		if ((rc = alloc_t(c, &c->d_out_sim, (size_t)VK_MAX_MATCHES * 64))) break;
-		if ((rc = alloc_t(c, &c->d_out_map, (size_t)VK_MAX_MATCHES * 64))) break;
+		rc = reserve_query_workspaces(c);
 	} while (0);
 	if (rc) { vk_corpus_free(c); return rc; }
 	*out = c;
@@ -126,40 +156,16 @@ int vk_corpus_view(vk_corpus_t *src, vk_corpus_t **out) {
 	if (src->is_view) return fail(VK_ERR_INVALID, "views are taken from the owning handle");
 	VK_HIP(hipSetDevice(src->device));
 	vk_corpus *c = new vk_corpus();
-	c->desc = src->desc; c->device = src->device;
-	c->d_pad = src->d_pad; c->nk32 = src->nk32; c->tail = src->tail; c->tile_bytes = src->tile_bytes; c->prec = src->prec;
-	c->rows_total = src->rows_total; c->rows_appended = src->rows_appended; c->n_tiles = src->n_tiles;
-	c->d_tiles = src->d_tiles; c->d_mag = src->d_mag; c->d_tok_id = src->d_tok_id; c->d_pos = src->d_pos; c->d_tag = src->d_tag;
-	c->d_sent_start = src->d_sent_start; c->d_sent_end = src->d_sent_end; c->d_long_groups = src->d_long_groups;
-	c->contiguous = src->contiguous; c->overlapping = src->overlapping; c->have_ids = src->have_ids; c->have_sent = src->have_sent; c->finalized = true;
-	c->max_len = src->max_len; c->max_group_tiles = src->max_group_tiles; c->max_group_tokens = src->max_group_tokens; c->max_pair_tiles = src->max_pair_tiles; c->max_short_pair_tiles = src->max_short_pair_tiles;
-	c->n_entries = src->n_entries; c->entry_sent = src->entry_sent;
-	c->h_start = src->h_start; c->h_end = src->h_end; c->h_tok = src->h_tok; c->h_tag = src->h_tag;
-	c->n_long_groups = src->n_long_groups; c->max_short_len = src->max_short_len; c->max_long_len = src->max_long_len; c->h_xlong = src->h_xlong; c->h_apart = src->h_apart;
-	c->long_group_tiles = src->long_group_tiles; c->long_group_tokens = src->long_group_tokens;
-	c->uniform_len = src->uniform_len;
+	static_cast<vk_corpus_shape &>(*c) = *src;   // (the owning blocks among it: the arrays live as long as any handle names them)
+	c->finalized = true;
 	c->is_view = true;
-	c->shared = src->shared;           // the arrays live as long as any handle names them
-	c->vectors_of = src->vectors_of;
-	c->shares_vectors = src->shares_vectors;
 	int rc = VK_OK;
 	do {
 		if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { rc = fail(VK_ERR_HIP, "hipStreamCreate failed"); break; }
 		for (auto &e : c->ev) if (hipEventCreate(&e) != hipSuccess) { rc = fail(VK_ERR_HIP, "hipEventCreate failed"); break; }
 		if (rc) break;
-		if (c->desc.layout == VK_LAYOUT_STATIC && (rc = alloc_t(c, &c->d_table, (size_t)c->n_tiles * 16 * 16 * 4))) break;
-		if ((rc = alloc_t(c, &c->d_qtile, (size_t)c->tile_bytes * 4))) break;
-		if ((rc = alloc_t(c, &c->d_ws, kGapTable))) break;
-		if ((rc = alloc_t(c, &c->d_wt, 160))) break;
-		if ((rc = alloc_t(c, &c->d_qids, 80))) break;
-		if ((rc = alloc_t(c, &c->d_out_raw, VK_MAX_MATCHES))) break;
-		if ((rc = alloc_t(c, &c->d_out_sim, (size_t)VK_MAX_MATCHES * 64))) break;
-		if ((rc = alloc_t(c, &c->d_out_map, (size_t)VK_MAX_MATCHES * 64))) break;
-		if ((rc = alloc_t(c, &c->d_scores, (size_t)c->n_entries + 8))) break;
-		if ((rc = alloc_t(c, &c->d_raw, (size_t)c->n_entries + 8))) break;
-		const size_t nblk = (size_t)((c->n_entries + kTopkChunk - 1) / kTopkChunk) + 1;
-		if ((rc = alloc_t(c, &c->d_keys[0], nblk * VK_MAX_MATCHES + kTopkChunk))) break;
-		if ((rc = alloc_t(c, &c->d_keys[1], (nblk * VK_MAX_MATCHES) / 2 + 2 * kTopkChunk))) break;
+		if ((rc = reserve_query_workspaces(c))) break;
+		rc = reserve_table_workspaces(c, c->n_entries);
 	} while (0);
 	if (rc) { vk_corpus_free(c); return rc; }
 	{   // into the ring of the handles on this corpus, once the handle is complete
@@ -187,16 +193,9 @@ int vk_corpus_free(vk_corpus_t *c) {
 		}
 	}
 	if (c->stream) (void)hipStreamSynchronize(c->stream);
-	void *ptrs[] = {c->d_stage, c->d_qtile, c->d_ws, c->d_wt, c->d_qids,
-		c->d_table, c->d_scores, c->d_raw, c->d_boost, c->d_keys[0], c->d_keys[1], c->d_out_raw, c->d_out_sim, c->d_out_map, c->d_wrd_raw, c->d_wrd_val, c->d_bq, c->d_bqlen, c->d_bscores, c->d_bkeys[0], c->d_bkeys[1], c->d_counter, c->d_rows_out, c->d_plan_out, c->d_braw, c->d_wrdl_scratch, c->d_wide_scratch, c->d_wide_order, c->d_xlong_order, c->d_apart_order, c->d_bqt, c->d_bcand, c->d_bcandq, c->d_brows, c->d_qbits,
-		c->d_sb_id[0], c->d_sb_id[1], c->d_btable, c->d_bfix, c->d_bqids, c->d_sort[0], c->d_sort[1], c->d_sort_temp,
-		c->lq.qt, c->lq.fl, c->lq.il, c->lq.table, c->lq.scratch, c->lq.fscratch, c->lq.raw, c->lq.sim, c->lq.map};
-	for (void *p : ptrs) if (p) (void)hipFree(p);
-	if (c->h_brows) (void)hipHostFree(c->h_brows);
-	for (auto &b : c->bl) for (void *p : {(void *)b.tiles, (void *)b.len, (void *)b.id}) if (p) (void)hipFree(p);
 	for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
 	if (c->stream) (void)hipStreamDestroy(c->stream);
-	delete c;
+	delete c;   // the workspaces go with it (vk_devbuf), after the stream has drained
 	return VK_OK;
 }
 
@@ -222,10 +221,7 @@ int vk_corpus_append_vectors(vk_corpus_t *c, const void *rows, int64_t n_rows, i
 		return VK_OK;
 	}
 	if (mem != VK_MEM_HOST) return fail(VK_ERR_INVALID, "bad memory kind");
-	if (!c->d_stage) {
-		int rc = alloc(c, &c->d_stage, (size_t)kStageBytes);
-		if (rc) return rc;
-	}
+	if (int rc = c->d_stage.reserve((size_t)kStageBytes, &c->device_bytes)) return rc;
 	const int64_t rows_per_chunk = std::max<int64_t>(1, kStageBytes / (int64_t)row_bytes);
 	for (int64_t r = 0; r < n_rows; r += rows_per_chunk) {
 		const int64_t nr = std::min(rows_per_chunk, n_rows - r);
@@ -346,17 +342,12 @@ static int set_slices_impl(vk_corpus_t *c, const int64_t *start, const int64_t *
 
 	// ---- device arrays sized by the table (re-created when the slices are set again)
 	for (void *p : {(void *)c->d_sent_start, (void *)c->d_sent_end, (void *)c->d_long_groups}) c->shared->release(p);
-	for (void *p : {(void *)c->d_scores, (void *)c->d_raw, (void *)c->d_keys[0], (void *)c->d_keys[1], (void *)c->d_boost})
-		if (p) VK_HIP(hipFree(p));
-	c->d_sent_start = c->d_sent_end = nullptr; c->d_scores = c->d_raw = c->d_boost = nullptr; c->d_keys[0] = c->d_keys[1] = nullptr; c->d_long_groups = nullptr;
+	c->d_scores.reset(); c->d_raw.reset(); c->d_keys[0].reset(); c->d_keys[1].reset(); c->d_boost.reset();
+	c->d_sent_start = c->d_sent_end = nullptr; c->d_long_groups = nullptr;
 	int rc;
 	if ((rc = alloc_shared(c, &c->d_sent_start, st32.size()))) return rc;
 	if ((rc = alloc_shared(c, &c->d_sent_end, en32.size()))) return rc;
-	if ((rc = alloc_t(c, &c->d_scores, (size_t)n_entries + 8))) return rc;
-	if ((rc = alloc_t(c, &c->d_raw, (size_t)n_entries + 8))) return rc;
-	const size_t nblk = (size_t)((n_entries + kTopkChunk - 1) / kTopkChunk) + 1;
-	if ((rc = alloc_t(c, &c->d_keys[0], nblk * VK_MAX_MATCHES + kTopkChunk))) return rc;
-	if ((rc = alloc_t(c, &c->d_keys[1], (nblk * VK_MAX_MATCHES) / 2 + 2 * kTopkChunk))) return rc;
+	if ((rc = reserve_table_workspaces(c, n_entries))) return rc;
 	if (!long_groups.empty()) {
 		if ((rc = alloc_shared(c, &c->d_long_groups, long_groups.size()))) return rc;
 		VK_HIP(hipMemcpy(c->d_long_groups, long_groups.data(), long_groups.size() * 4, hipMemcpyHostToDevice));
@@ -366,9 +357,7 @@ static int set_slices_impl(vk_corpus_t *c, const int64_t *start, const int64_t *
 	c->h_start = std::make_shared<std::vector<int32_t>>(st32);
 	c->h_end = std::make_shared<std::vector<int32_t>>(en32);
 	c->n_entries = n_entries;
-	if (c->d_wide_order) { VK_HIP(hipFree(c->d_wide_order)); c->d_wide_order = nullptr; }
-	if (c->d_xlong_order) { VK_HIP(hipFree(c->d_xlong_order)); c->d_xlong_order = nullptr; }
-	if (c->d_apart_order) { VK_HIP(hipFree(c->d_apart_order)); c->d_apart_order = nullptr; }
+	c->d_wide_order.reset(); c->d_xlong_order.reset(); c->d_apart_order.reset();
 	c->n_wide_order = c->n_xlong_order = c->n_apart_order = -1;   // the work list of the one-wave-per-slice pass follows the table
 	c->n_long_groups = (int)long_groups.size();
 	c->max_len = max_len;
@@ -446,7 +435,7 @@ int vk_corpus_finalize(vk_corpus_t *c) {
 	if (!c->have_sent) return fail(VK_ERR_STATE, "sentence spans were not set");
 	if (c->desc.layout == VK_LAYOUT_STATIC && !c->have_ids) return fail(VK_ERR_STATE, "token ids were not set");
 	VK_HIP(hipSetDevice(c->device));
-	if (c->d_stage) { VK_HIP(hipFree(c->d_stage)); c->d_stage = nullptr; c->device_bytes -= kStageBytes; }
+	c->d_stage.reset();
 	VK_HIP(hipStreamSynchronize(c->stream));
 	c->finalized = true;
 	return VK_OK;
@@ -512,14 +501,7 @@ int vk_corpus_filter(vk_corpus_t *src, uint64_t pos_mask, uint64_t tag_mask, vk_
 			for (auto &e : c->ev) if (hipEventCreate(&e) != hipSuccess) return fail(VK_ERR_HIP, "hipEventCreate failed");
 			int r;
 			if ((r = alloc_shared(c, &c->d_tok_id, (size_t)n_kept + 64))) return r;
-			if ((r = alloc_t(c, &c->d_table, (size_t)c->n_tiles * 16 * 16 * 4))) return r;
-			if ((r = alloc_t(c, &c->d_qtile, (size_t)c->tile_bytes * 4))) return r;
-			if ((r = alloc_t(c, &c->d_ws, kGapTable))) return r;
-			if ((r = alloc_t(c, &c->d_wt, 160))) return r;
-			if ((r = alloc_t(c, &c->d_qids, 80))) return r;
-			if ((r = alloc_t(c, &c->d_out_raw, VK_MAX_MATCHES))) return r;
-			if ((r = alloc_t(c, &c->d_out_sim, (size_t)VK_MAX_MATCHES * 64))) return r;
-			if ((r = alloc_t(c, &c->d_out_map, (size_t)VK_MAX_MATCHES * 64))) return r;
+			if ((r = reserve_query_workspaces(c))) return r;
 			VK_HIP(hipMemsetAsync(c->d_tok_id, 0, ((size_t)n_kept + 64) * 4, st));
 			VK_HIP(vk_launch_filter_gather(src->d_tok_id, c->d_tok_id, 4, src_of, n_kept, st));
 			c->have_ids = true;

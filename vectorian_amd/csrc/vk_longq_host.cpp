@@ -6,18 +6,6 @@
 #include "vk_internal.h"
 #include "vk_guard.h"
 
-namespace {
-
-template <typename T> int grow(vk_corpus *c, T **p, size_t *cap, size_t need) {
-	if (*cap >= need && *p) return VK_OK;
-	if (*p) { VK_HIP(hipFree(*p)); *p = nullptr; *cap = 0; }
-	const int rc = alloc_t(c, p, need);
-	if (rc == VK_OK) *cap = need;
-	return rc;
-}
-
-} // namespace
-
 int vk_longq_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_host_keep &keep) {
 	int rc = VK_OK;
 	hipStream_t st = c->stream;
@@ -35,7 +23,7 @@ int vk_longq_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_
 	std::vector<uint8_t> &qtile = keep.vec<uint8_t>();
 	std::vector<float> &qmags = keep.vec<float>((size_t)LTP);
 	vk_pack_query(c, q, qtile, qmags.data());
-	if ((rc = grow(c, &lq.qt, &lq.qt_cap, (size_t)nq * c->tile_bytes))) return rc;
+	if ((rc = lq.qt.reserve((size_t)nq * c->tile_bytes, &c->device_bytes))) return rc;
 	VK_HIP(hipMemcpyAsync(lq.qt, qtile.data(), qtile.size(), hipMemcpyHostToDevice, st));
 
 	VkLongqParams p{};
@@ -64,14 +52,14 @@ int vk_longq_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_
 		il[(size_t)j] = (q->tag_weights && j < LT) ? (int32_t)q->q_pos[j] : -1;
 		il[(size_t)LTP + j] = (q->q_token_ids && j < LT) ? q->q_token_ids[j] : -1;
 	}
-	if ((rc = grow(c, &lq.fl, &lq.fl_cap, fl.size()))) return rc;
-	if ((rc = grow(c, &lq.il, &lq.il_cap, il.size()))) return rc;
+	if ((rc = lq.fl.reserve(fl.size(), &c->device_bytes))) return rc;
+	if ((rc = lq.il.reserve(il.size(), &c->device_bytes))) return rc;
 	VK_HIP(hipMemcpyAsync(lq.fl, fl.data(), fl.size() * 4, hipMemcpyHostToDevice, st));
 	VK_HIP(hipMemcpyAsync(lq.il, il.data(), il.size() * 4, hipMemcpyHostToDevice, st));
 
 	std::vector<float> &boost_rows = keep.vec<float>();
 	if (q->boost) {
-		if (!c->d_boost) { rc = alloc_t(c, &c->d_boost, (size_t)n + 8); if (rc) return rc; }
+		if ((rc = c->d_boost.reserve((size_t)n + 8, &c->device_bytes))) return rc;
 		const float *src = q->boost;
 		if (!c->entry_sent.empty()) {
 			boost_rows.resize((size_t)n);
@@ -82,7 +70,7 @@ int vk_longq_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_
 	}
 	const int64_t table_stride = (int64_t)c->n_tiles * 16 * 16;
 	if (is_static && !only) {
-		if ((rc = grow(c, &lq.table, &lq.table_cap, (size_t)nq * (size_t)table_stride))) return rc;
+		if ((rc = lq.table.reserve((size_t)nq * (size_t)table_stride, &c->device_bytes))) return rc;
 		for (int t = 0; t < nq; t++)   // one [V_pad x 16] table per 16 query tokens: cosine, sim[id(t_j)][j] = 1, clip (metric/static.cpp:9-78)
 			VK_HIP(vk_launch_table(c->d_tiles, lq.qt + (size_t)t * c->tile_bytes, (int32_t)c->n_tiles, c->nk32, c->tail, c->tile_bytes,
 				lq.table + (size_t)t * table_stride, q->q_token_ids ? lq.il + LTP + t * 16 : nullptr, std::min(16, LT - t * 16), c->desc.vocab_size, c->prec, st));
@@ -99,8 +87,8 @@ int vk_longq_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_
 		p.tw_keep = 1.0f - q->pos_mismatch_penalty; p.tw_threshold = q->similarity_threshold;
 	}
 	p.ref_total = total;
-	p.boost = q->boost ? c->d_boost : nullptr;
-	p.scores = c->d_scores; p.raw = (q->want_flow ? nullptr : c->d_raw);   // with traceback the retrace restates the winners' aligner scores
+	p.boost = q->boost ? (float *)c->d_boost : nullptr;
+	p.scores = c->d_scores; p.raw = q->want_flow ? nullptr : (float *)c->d_raw;   // with traceback the retrace restates the winners' aligner scores
 	p.d = c->desc.d; p.q_ids = is_static ? lq.il + LTP : nullptr;
 
 	// ---- the scoring pass (handles on one corpus take turns, as in vk_query)
@@ -115,7 +103,7 @@ int vk_longq_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_
 			if (kt_ < LT) p.wt_tail = kt_;
 			if (!vk_longq_hm_in_lds(LT, c->max_len)) {   // the matrix of the scans: in LDS behind the strip where it fits, else a region per workgroup
 				const size_t per = vk_longq_scratch_bytes(LT, 2, 0, 0);
-				if ((rc = grow(c, &lq.scratch, &lq.scratch_cap, per * (size_t)vk_longq_blocks(LT, c->max_len, n, 0)))) return rc;
+				if ((rc = lq.scratch.reserve(per * (size_t)vk_longq_blocks(LT, c->max_len, n, 0), &c->device_bytes))) return rc;
 				p.scratch = lq.scratch; p.scratch_stride = (int64_t)per;
 			}
 		}
@@ -157,10 +145,10 @@ int vk_longq_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_
 	// ---- the winners' tracebacks
 	if (do_flow) {
 		const size_t per = vk_longq_scratch_bytes(LT, p.gap_mode, 1, q->tag_weights != nullptr);
-		if ((rc = grow(c, &lq.fscratch, &lq.fscratch_cap, per * (size_t)kk))) return rc;
-		if ((rc = grow(c, &lq.raw, &lq.raw_cap, (size_t)kk))) return rc;
-		if ((rc = grow(c, &lq.map, &lq.map_cap, (size_t)kk * LTP))) return rc;
-		if ((rc = grow(c, &lq.sim, &lq.sim_cap, (size_t)kk * LTP))) return rc;
+		if ((rc = lq.fscratch.reserve(per * (size_t)kk, &c->device_bytes))) return rc;
+		if ((rc = lq.raw.reserve((size_t)kk, &c->device_bytes))) return rc;
+		if ((rc = lq.map.reserve((size_t)kk * LTP, &c->device_bytes))) return rc;
+		if ((rc = lq.sim.reserve((size_t)kk * LTP, &c->device_bytes))) return rc;
 		VkLongqParams f = p;
 		f.wt_tail = 0;   // (the tracebacks meet every candidate, in the oracle's order)
 		f.keys = c->d_keys[cur]; f.n_keys = kk; f.raw_out = lq.raw; f.mapping = lq.map; f.edge_sim = lq.sim; f.out_stride = LTP;

@@ -201,7 +201,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		w.sent_start = c->d_sent_start; w.sent_end = c->d_sent_end;
 		w.layout = is_static_l ? VK_DEV_LAYOUT_STATIC : VK_DEV_LAYOUT_CONTEXTUAL; w.nk32 = c->nk32; w.tail = c->tail; w.tile_bytes = c->tile_bytes; w.prec = c->prec;
 		w.qtile = c->d_qtile; w.nq = (q->len_t + 15) / 16; w.len_t = q->len_t; w.mag = c->d_mag;
-		w.d = c->desc.d; w.q_ids = is_static_l ? c->d_qids : nullptr;   // canonical similarity rows (sim_canon)
+		w.d = c->desc.d; w.q_ids = is_static_l ? (int32_t *)c->d_qids : nullptr;   // canonical similarity rows (sim_canon)
 		w.ref_total = (float)q->len_t;
 		if (q->tag_weights) {
 			float total = 0.0f;
@@ -230,17 +230,10 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		int rc2;
 		const int cnt = (int)rows_idx.size();
 		const size_t need = (size_t)cnt * R * W;
-		if (c->rows_cap < need) {
-			if (c->d_rows_out) { VK_HIP(hipFree(c->d_rows_out)); VK_HIP(hipFree(c->d_plan_out)); c->d_rows_out = c->d_plan_out = nullptr; }
-			if ((rc2 = alloc_t(c, &c->d_rows_out, need))) return rc2;
-			if ((rc2 = alloc_t(c, &c->d_plan_out, need))) return rc2;
-			c->rows_cap = need;
-		}
-		if (!c->d_wrd_raw) {
-			if ((rc2 = alloc_t(c, &c->d_wrd_raw, (size_t)VK_MAX_MATCHES))) return rc2;
-			if ((rc2 = alloc_t(c, &c->d_wrd_val, (size_t)VK_MAX_MATCHES))) return rc2;
-			c->wrd_cap = VK_MAX_MATCHES;
-		}
+		if ((rc2 = c->d_rows_out.reserve(need, &c->device_bytes))) return rc2;
+		if ((rc2 = c->d_plan_out.reserve(need, &c->device_bytes))) return rc2;
+		if ((rc2 = c->d_wrd_raw.reserve((size_t)VK_MAX_MATCHES, &c->device_bytes))) return rc2;
+		if ((rc2 = c->d_wrd_val.reserve((size_t)VK_MAX_MATCHES, &c->device_bytes))) return rc2;
 		std::vector<uint64_t> &hk = keep.vec<uint64_t>((size_t)cnt);
 		for (int i = 0; i < cnt; i++) hk[(size_t)i] = (1ull << 32) | (uint64_t)(uint32_t)rows_idx[(size_t)i];
 		VK_HIP(hipMemcpyAsync(c->d_keys[1], hk.data(), hk.size() * 8, hipMemcpyHostToDevice, c->stream));
@@ -259,9 +252,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 			VK_HIP(hipMemsetAsync(c->d_plan_out, 0, need * 4, c->stream));   // a solver writes the columns of its winner's tokens only
 			VK_HIP(vk_launch_wrd_exact(&w, cnt, nullptr, c->stream));
 			if (R > VK_FAST_SENT_LEN && c->max_len > VK_FAST_SENT_LEN) {   // winners of 65 .. R tokens: the long solver restates their plans
-				if (w.nq > 1 && !c->d_wrdl_scratch) {
-					if ((rc2 = alloc_t(c, &c->d_wrdl_scratch, (size_t)vk_wrd_long_blocks() * vk_wrd_long_scratch_bytes()))) return rc2;
-				}
+				if (w.nq > 1 && (rc2 = c->d_wrdl_scratch.reserve((size_t)vk_wrd_long_blocks() * vk_wrd_long_scratch_bytes(), &c->device_bytes))) return rc2;
 				w.scratch = c->d_wrdl_scratch; w.scratch_stride = (int64_t)vk_wrd_long_scratch_bytes();
 				VK_HIP(vk_launch_wrd_exact_long(&w, cnt, c->stream));
 			}
@@ -359,11 +350,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		p.gap_mode = 2;
 	}
 	for (size_t i = 0; i < n_ws; i++) ws[i] = (is_align && (int64_t)i <= c->max_len) ? gap_cost(q->gap_s, (int)i) : 0.0f;
-	if (c->ws_cap < n_ws) {
-		if (c->d_ws) { VK_HIP(hipFree(c->d_ws)); c->d_ws = nullptr; c->ws_cap = 0; }
-		if ((rc = alloc_t(c, &c->d_ws, n_ws))) return rc;
-		c->ws_cap = n_ws;
-	}
+	if ((rc = c->d_ws.reserve(n_ws, &c->device_bytes))) return rc;
 	for (int i = 0; i < 80; i++) wt[i] = (is_align && i <= q->len_t) ? gap_cost(q->gap_t, i) : 0.0f;
 	for (int i = 80; i < 160; i++) wt[i] = 0.0f;
 	// The register-history kernels take their in-row candidates from the row's values before in-row gaps, which is the
@@ -383,7 +370,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 
 	std::vector<float> &boost_rows = keep.vec<float>();
 	if (q->boost) {
-		if (!c->d_boost) { rc = alloc_t(c, &c->d_boost, (size_t)n + 8); if (rc) return rc; }
+		if ((rc = c->d_boost.reserve((size_t)n + 8, &c->device_bytes))) return rc;
 		const float *src = q->boost;
 		if (!c->entry_sent.empty()) {
 			boost_rows.resize((size_t)n);
@@ -415,7 +402,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	p.nk32 = c->nk32; p.tail = c->tail; p.tile_bytes = c->tile_bytes; p.prec = c->prec;
 	p.qtile = c->d_qtile; p.len_t = q->len_t; p.locality = q->locality;
 	p.ws = c->d_ws; p.wt = c->d_wt + 80; p.wt0 = c->d_wt;
-	p.boost = q->boost ? c->d_boost : nullptr;
+	p.boost = q->boost ? (float *)c->d_boost : nullptr;
 	p.scores = c->d_scores; p.raw = c->d_raw;
 	p.ref_total = (float)q->len_t;
 	if (q->tag_weights) {
@@ -437,7 +424,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	const bool vocab_fix = is_static && q->algorithm == VK_ALG_RWMD && q->tag_weights && q->q_tags && q->q_token_ids && c->d_tag && c->d_pos;
 	if (vocab_fix) {
 		const size_t words = ((size_t)c->desc.vocab_size + 31) / 32 + 1;
-		if (!c->d_qbits && (rc = alloc_t(c, &c->d_qbits, words))) return rc;
+		if ((rc = c->d_qbits.reserve(words, &c->device_bytes))) return rc;
 		std::vector<uint32_t> &bits = keep.vec<uint32_t>(words, 0u);
 		for (int j = 0; j < q->len_t; j++) {
 			const int32_t id = q->q_token_ids[j];
@@ -467,7 +454,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	// kernels leave to it -- those beyond VK_MAX_SENT_LEN, or, under general gaps, every slice of more than 64 tokens.
 	auto wide_order = [&](int force = -1) -> int {
 		const int which = force >= 0 ? force : wide_score ? 0 : (long_via_wide || rwmd_long_doc) ? 1 : 2;
-		int32_t *&d_ord = which == 0 ? c->d_wide_order : which == 1 ? c->d_apart_order : c->d_xlong_order;
+		vk_devbuf<int32_t> &d_ord = which == 0 ? c->d_wide_order : which == 1 ? c->d_apart_order : c->d_xlong_order;
 		int32_t &n_ord = which == 0 ? c->n_wide_order : which == 1 ? c->n_apart_order : c->n_xlong_order;
 		if (n_ord < 0) {
 			std::vector<int32_t> ord;
@@ -477,13 +464,13 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 			std::stable_sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) {
 				return (*c->h_end)[(size_t)a] - (*c->h_start)[(size_t)a] > (*c->h_end)[(size_t)b] - (*c->h_start)[(size_t)b]; });
 			int rcw;
-			if ((rcw = alloc_t(c, &d_ord, ord.size() + 1))) return rcw;
+			if ((rcw = d_ord.reserve(ord.size() + 1, &c->device_bytes))) return rcw;
 			VK_HIP(hipMemcpy(d_ord, ord.data(), ord.size() * 4, hipMemcpyHostToDevice));
 			n_ord = (int32_t)ord.size();
 		}
 		wp.order = d_ord; wp.n_order = n_ord;
 		if (which == 0) {
-			VK_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_scores), (int)0xff800000u, (size_t)n, st));
+			VK_HIP(hipMemsetD32Async(static_cast<hipDeviceptr_t>(c->d_scores), (int)0xff800000u, (size_t)n, st));
 			if (wp.raw) VK_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(wp.raw), (int)0xff800000u, (size_t)n, st));
 		}
 		return VK_OK;
@@ -509,12 +496,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		const size_t blocks = (size_t)vk_wide_gs_blocks(c->max_len, nq, wp.gap_mode, flow_k, n, wp.h_ring);
 		const size_t need = per * blocks;
 		if (need > ((size_t)16 << 30)) return fail(VK_ERR_UNSUPPORTED, "traceback state of this many slices this long exceeds 16 GiB of scratch");
-		if (c->wide_scratch_cap < need) {
-			if (c->d_wide_scratch) { VK_HIP(hipFree(c->d_wide_scratch)); c->d_wide_scratch = nullptr; c->wide_scratch_cap = 0; }
-			int rcw;
-			if ((rcw = alloc_t(c, &c->d_wide_scratch, need))) return rcw;
-			c->wide_scratch_cap = need;
-		}
+		if (int rcw = c->d_wide_scratch.reserve(need, &c->device_bytes)) return rcw;
 		wp.scratch = c->d_wide_scratch; wp.scratch_stride = (int64_t)per;
 		if (!flow && (xlong || part)) {
 			int rcw = VK_OK;
@@ -543,7 +525,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 			wp.tpos[j] = (p.pos_s && j < q->len_t) ? (int32_t)q->q_pos[j] : -1;
 		}
 		wp.boost = p.boost; wp.scores = c->d_scores; wp.raw = c->d_raw;
-		wp.d = c->desc.d; wp.q_ids = is_static ? c->d_qids : nullptr;   // FLOW: canonical similarity rows (sim_canon)
+		wp.d = c->desc.d; wp.q_ids = is_static ? (int32_t *)c->d_qids : nullptr;   // FLOW: canonical similarity rows (sim_canon)
 		{   // as for the 16-column kernel: the aligner scores of all slices only if something reads them
 			const bool exact_tr2 = q->algorithm == VK_ALG_WRD || (q->algorithm == VK_ALG_RWMD && q->wmd_full);
 			if (((is_align && q->want_flow) || exact_tr2) && !(q->submatch_weight > 0.0f) && !getenv("VK_KEEP_RAW")) wp.raw = nullptr;
@@ -702,12 +684,8 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 			rows_idx[(size_t)i] = c->sent_entry.empty() ? q->only_slices[i] : (int64_t)c->sent_entry[(size_t)q->only_slices[i]];
 			hk[(size_t)i] = (1ull << 32) | (uint64_t)(uint32_t)rows_idx[(size_t)i];
 		}
-		if (c->wrd_cap < (size_t)VK_MAX_MATCHES) {
-			if (c->d_wrd_raw) { VK_HIP(hipFree(c->d_wrd_raw)); VK_HIP(hipFree(c->d_wrd_val)); c->d_wrd_raw = c->d_wrd_val = nullptr; }
-			rc = alloc_t(c, &c->d_wrd_raw, (size_t)VK_MAX_MATCHES); if (rc) return rc;
-			rc = alloc_t(c, &c->d_wrd_val, (size_t)VK_MAX_MATCHES); if (rc) return rc;
-			c->wrd_cap = VK_MAX_MATCHES;
-		}
+		if ((rc = c->d_wrd_raw.reserve((size_t)VK_MAX_MATCHES, &c->device_bytes))) return rc;
+		if ((rc = c->d_wrd_val.reserve((size_t)VK_MAX_MATCHES, &c->device_bytes))) return rc;
 		VK_HIP(hipMemcpyAsync(c->d_keys[0], hk.data(), hk.size() * 8, hipMemcpyHostToDevice, st));
 		VkWrdParams w{};
 		fill_transport(w);
@@ -719,9 +697,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		VK_HIP(hipMemsetAsync(c->d_wrd_val, 0xff, (size_t)cnt * 4, st));
 		VK_HIP(vk_launch_wrd_exact(&w, cnt, nullptr, st));
 		if (c->max_len > VK_FAST_SENT_LEN) {
-			if (w.nq > 1 && !c->d_wrdl_scratch) {
-				if ((rc = alloc_t(c, &c->d_wrdl_scratch, (size_t)vk_wrd_long_blocks() * vk_wrd_long_scratch_bytes()))) return rc;
-			}
+			if (w.nq > 1 && (rc = c->d_wrdl_scratch.reserve((size_t)vk_wrd_long_blocks() * vk_wrd_long_scratch_bytes(), &c->device_bytes))) return rc;
 			w.scratch = c->d_wrdl_scratch; w.scratch_stride = (int64_t)vk_wrd_long_scratch_bytes();
 			VK_HIP(vk_launch_wrd_exact_long(&w, cnt, st));
 		}
@@ -756,13 +732,9 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		// trickle of M-candidate rounds.
 		const int M = 512;
 		const size_t cap = ((size_t)((n + kTopkChunk - 1) / kTopkChunk) + 1) * VK_MAX_MATCHES;   // keys d_keys[0] holds
-		if (c->wrd_cap < cap) {
-			if (c->d_wrd_raw) { VK_HIP(hipFree(c->d_wrd_raw)); VK_HIP(hipFree(c->d_wrd_val)); c->d_wrd_raw = c->d_wrd_val = nullptr; }
-			rc = alloc_t(c, &c->d_wrd_raw, cap); if (rc) return rc;
-			rc = alloc_t(c, &c->d_wrd_val, cap); if (rc) return rc;
-			c->wrd_cap = cap;
-		}
-		if (!c->d_counter) { rc = alloc_t(c, &c->d_counter, 4); if (rc) return rc; }
+		if ((rc = c->d_wrd_raw.reserve(cap, &c->device_bytes))) return rc;
+		if ((rc = c->d_wrd_val.reserve(cap, &c->device_bytes))) return rc;
+		if ((rc = c->d_counter.reserve(4, &c->device_bytes))) return rc;
 		struct Cand { float val, raw; int64_t g; };
 		std::vector<Cand> best;
 		std::vector<uint64_t> &keys = keep.vec<uint64_t>();
@@ -778,8 +750,8 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 			w.keys = d_keys;
 			VK_HIP(vk_launch_wrd_exact(&w, count, c->d_scores, st));
 			if (c->max_len > VK_FAST_SENT_LEN) {   // candidates of 65 .. 512 tokens
-				if (w.nq > 1 && !c->d_wrdl_scratch) {
-					int rc3 = alloc_t(c, &c->d_wrdl_scratch, (size_t)vk_wrd_long_blocks() * vk_wrd_long_scratch_bytes());
+				if (w.nq > 1) {
+					int rc3 = c->d_wrdl_scratch.reserve((size_t)vk_wrd_long_blocks() * vk_wrd_long_scratch_bytes(), &c->device_bytes);
 					if (rc3) return rc3;
 				}
 				w.scratch = c->d_wrdl_scratch; w.scratch_stride = (int64_t)vk_wrd_long_scratch_bytes();
@@ -885,12 +857,8 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 				const int R = (c->max_len + 63) / 64 * 64, Wq = 16 * nq;
 				const size_t need = (size_t)count * R * Wq;
 				if (need * 4 <= ((size_t)2 << 30)) {
-					if (c->rows_cap < need) {
-						if (c->d_rows_out) { VK_HIP(hipFree(c->d_rows_out)); VK_HIP(hipFree(c->d_plan_out)); c->d_rows_out = c->d_plan_out = nullptr; c->rows_cap = 0; }
-						if ((rcw = alloc_t(c, &c->d_rows_out, need))) return rcw;
-						if ((rcw = alloc_t(c, &c->d_plan_out, need))) return rcw;
-						c->rows_cap = need;
-					}
+					if ((rcw = c->d_rows_out.reserve(need, &c->device_bytes))) return rcw;
+					if ((rcw = c->d_plan_out.reserve(need, &c->device_bytes))) return rcw;
 					VkWrdParams w{};
 					fill_transport(w);
 					w.keys = d_keys; w.rows_out = c->d_rows_out; w.rows_len = R;
@@ -915,7 +883,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		f.pos_s = p.pos_s; f.tw_keep = p.tw_keep; f.tw_threshold = p.tw_threshold;
 		memcpy(f.tw, p.tw, sizeof f.tw);
 		memcpy(f.tpos, p.tpos, sizeof f.tpos);
-		f.d = c->desc.d; f.q_ids = is_static ? c->d_qids : nullptr;   // canonical similarity rows (sim_canon)
+		f.d = c->desc.d; f.q_ids = is_static ? (int32_t *)c->d_qids : nullptr;   // canonical similarity rows (sim_canon)
 		f.keys = d_keys; f.raw_out = c->d_out_raw; f.mapping = c->d_out_map; f.edge_sim = c->d_out_sim;
 		VK_HIP(vk_launch_flow(&f, count, st));
 		return VK_OK;
@@ -1031,14 +999,10 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	// (57 .. 64 matches: the margin takes the selection to the k > 64 path; beyond VK_MAX_MATCHES: every score is sorted, never more winners than rows)
 	const int kk = only ? q->n_only : (int)std::min<int64_t>(!(do_flow || canon_tr) ? k : (k <= VK_MAX_MATCHES ? std::min(k + kCanonMargin, VK_MAX_MATCHES) : k + kCanonMargin), std::max<int64_t>(n, 1));
 	const uint64_t *d_sel = nullptr;   // the selected keys on the device, best first
-	if ((size_t)kk > c->out_cap) {   // the winners' device arrays: grown to this result set
-		for (void *ptr : {(void *)c->d_out_raw, (void *)c->d_out_sim, (void *)c->d_out_map}) if (ptr) VK_HIP(hipFree(ptr));
-		c->d_out_raw = nullptr; c->d_out_sim = nullptr; c->d_out_map = nullptr; c->out_cap = 0;
-		if ((rc = alloc_t(c, &c->d_out_raw, (size_t)kk))) return rc;
-		if ((rc = alloc_t(c, &c->d_out_sim, (size_t)kk * 64))) return rc;
-		if ((rc = alloc_t(c, &c->d_out_map, (size_t)kk * 64))) return rc;
-		c->out_cap = (size_t)kk;
-	}
+	// the winners' device arrays: grown to this result set
+	if ((rc = c->d_out_raw.reserve((size_t)kk, &c->device_bytes))) return rc;
+	if ((rc = c->d_out_sim.reserve((size_t)kk * 64, &c->device_bytes))) return rc;
+	if ((rc = c->d_out_map.reserve((size_t)kk * 64, &c->device_bytes))) return rc;
 	const float sel_floor = (do_flow || canon_tr) ? q->min_score - 1e-5f * std::max(1.0f, std::fabs(q->min_score)) : q->min_score;
 	int cur = 0;
 	if (only) {
@@ -1056,21 +1020,12 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		VK_HIP(hipStreamSynchronize(st));   // `hk` leaves scope
 	} else if (kk > VK_MAX_MATCHES) {
 		// more matches than the block selection keeps per 2,048 keys: the keys of all n rows, sorted
-		if (c->sort_cap < (size_t)n) {
-			for (auto &b : c->d_sort) if (b) { VK_HIP(hipFree(b)); b = nullptr; }
-			c->sort_cap = 0;
-			if ((rc = alloc_t(c, &c->d_sort[0], (size_t)n + 64))) return rc;
-			if ((rc = alloc_t(c, &c->d_sort[1], (size_t)n + 64))) return rc;
-			c->sort_cap = (size_t)n;
-		}
+		if ((rc = c->d_sort[0].reserve((size_t)n + 64, &c->device_bytes))) return rc;
+		if ((rc = c->d_sort[1].reserve((size_t)n + 64, &c->device_bytes))) return rc;
 		size_t temp_bytes = 0;
 		uint64_t *sorted = nullptr;
 		VK_HIP(vk_launch_sort_all(nullptr, n, sel_floor, c->d_sort[0], c->d_sort[1], nullptr, &temp_bytes, &sorted, st));
-		if (c->sort_temp_cap < temp_bytes) {
-			if (c->d_sort_temp) { VK_HIP(hipFree(c->d_sort_temp)); c->d_sort_temp = nullptr; c->sort_temp_cap = 0; }
-			if ((rc = alloc(c, &c->d_sort_temp, temp_bytes))) return rc;
-			c->sort_temp_cap = temp_bytes;
-		}
+		if ((rc = c->d_sort_temp.reserve(temp_bytes, &c->device_bytes))) return rc;
 		VK_HIP(vk_launch_sort_all(c->d_scores, n, sel_floor, c->d_sort[0], c->d_sort[1], c->d_sort_temp, &temp_bytes, &sorted, st));
 		d_sel = sorted;
 	} else if (kk <= 64) {
@@ -1155,11 +1110,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	const int rows_R = out->rows_per_winner > 0 ? out->rows_per_winner : VK_FAST_SENT_LEN, rows_W = 16 * ((q->len_t + 15) / 16);
 	if (canon_tr && n_sel > 0) {
 		const size_t rows_bytes = (size_t)n_sel * rows_R * rows_W * 4;
-		if (c->h_brows_cap < rows_bytes) {
-			if (c->h_brows) { VK_HIP(hipHostFree(c->h_brows)); c->h_brows = nullptr; c->h_brows_cap = 0; }
-			VK_HIP(hipHostMalloc((void **)&c->h_brows, rows_bytes, hipHostMallocDefault));
-			c->h_brows_cap = rows_bytes;
-		}
+		if ((rc = c->h_brows.reserve(rows_bytes / 4, nullptr))) return rc;
 		rows_all = c->h_brows;
 		std::vector<int64_t> rows_idx;
 		for (int i = 0; i < n_sel; i++) rows_idx.push_back((int64_t)(uint32_t)(keys[(size_t)i] & 0xffffffffu));
