@@ -33,17 +33,11 @@ static int batch_winner_rows(vk_corpus *c, const vk_query_desc *qs, int n_querie
 	// which of a query's kk candidates are restated: its k best, and of the runners-up those the k-th could lose its place to -- a
 	// score of the scoring pass within rounding (2e-5, ten times what MFMA accumulation was seen to differ by) of the k-th's.
 	// Typically none: 10 rows per query travel instead of 18.  first[i]: where query i's candidates start in the compact list.
-	auto key_score = [](uint64_t key) {
-		const uint32_t ob = (uint32_t)(key >> 32);
-		const uint32_t bits = (ob & 0x80000000u) ? (ob & 0x7fffffffu) : ~ob;
-		float s;
-		memcpy(&s, &bits, 4);
-		return s;
-	};
+	using vk_host::key_score;
+	using vk_host::key_row;
 	std::vector<int32_t> first((size_t)n_queries + 1, 0);
 	for (int i = 0; i < n_queries; i++) {
-		int cnt = 0;
-		while (cnt < kk && keys[(size_t)i * kk + cnt] != 0) cnt++;
+		const int cnt = vk_host::count_keys(keys + (size_t)i * kk, kk);
 		int need = std::min(cnt, k);
 		if (cnt > k) {
 			const float sk = key_score(keys[(size_t)i * kk + k - 1]);
@@ -89,7 +83,7 @@ static int batch_winner_rows(vk_corpus *c, const vk_query_desc *qs, int n_querie
 		}
 		for (int j = 0; j < first[(size_t)i + 1] - first[(size_t)i]; j++) {
 			hq[(size_t)first[(size_t)i] + j] = i;
-			hk[(size_t)first[(size_t)i] + j] = (1ull << 32) | (uint64_t)(uint32_t)(keys[(size_t)i * kk + j] & 0xffffffffu);
+			hk[(size_t)first[(size_t)i] + j] = vk_host::key_of_row(key_row(keys[(size_t)i * kk + j]));
 		}
 	}
 	VK_HIP(hipMemcpyAsync(c->d_bqt, packed16 ? packed16 : qt.data(), (size_t)n_queries * c->tile_bytes, hipMemcpyHostToDevice, st));
@@ -97,10 +91,8 @@ static int batch_winner_rows(vk_corpus *c, const vk_query_desc *qs, int n_querie
 	VK_HIP(hipMemcpyAsync(c->d_bcandq, hq.data(), n_cand * 4, hipMemcpyHostToDevice, st));
 	stamp("uploads issued");
 	VkWrdParams w{};
-	w.tiles = c->d_tiles; w.sent_start = c->d_sent_start; w.sent_end = c->d_sent_end;
-	w.layout = is_static ? VK_DEV_LAYOUT_STATIC : VK_DEV_LAYOUT_CONTEXTUAL;
-	if (is_static) { w.tok_id = c->d_tok_id; w.q_ids = c->d_bqids; w.q_ids_stride = 16; }
-	w.nk32 = c->nk32; w.tail = c->tail; w.tile_bytes = c->tile_bytes; w.prec = c->prec;
+	corpus_fields_ids(w, c);
+	if (is_static) { w.q_ids = c->d_bqids; w.q_ids_stride = 16; }
 	w.qtile = c->d_bqt; w.qtile_stride = c->tile_bytes; w.cand_query = c->d_bcandq; w.nq = 1; w.len_t = qs[0].len_t;
 	w.d = c->desc.d;   // canonical similarity rows (sim_canon)
 	w.keys = c->d_bcand; w.rows_out = c->d_brows;
@@ -124,9 +116,9 @@ static int batch_winner_rows(vk_corpus *c, const vk_query_desc *qs, int n_querie
 			vk_topk_out *out = &outs[i];
 			order.clear();
 			const size_t at = (size_t)first[(size_t)i];
+			const auto row_at = [&](int j) { return (int64_t)key_row(keys[(size_t)i * kk + j]); };
 			for (int j = 0; j < first[(size_t)i + 1] - first[(size_t)i]; j++) {
-				const uint64_t key = keys[(size_t)i * kk + j];
-				const int64_t g = (int64_t)(uint32_t)(key & 0xffffffffu);
+				const int64_t g = row_at(j);
 				const int t_a = (*c->h_start)[(size_t)g], len_s = (*c->h_end)[(size_t)g] - t_a;
 				const bool vocab = is_static && q.q_token_ids && c->h_tok;
 				if (vocab) {
@@ -136,23 +128,16 @@ static int batch_winner_rows(vk_corpus *c, const vk_query_desc *qs, int n_querie
 				raw[(size_t)j] = vk_host::rwmd_from_rows(c->h_brows + (at + j) * 64 * 16, 16, len_s, q.len_t, vocab ? key_s.data() : nullptr, vocab ? key_t.data() : nullptr,
 					q.rwmd_injective != 0, q.rwmd_symmetric != 0, q.rwmd_normalize_bow != 0);
 				val[(size_t)j] = (raw[(size_t)j] / (float)q.len_t) * (q.boost ? q.boost[g] : 1.0f);
-				if (val[(size_t)j] > q.min_score) order.push_back(j);
+				order.push_back(j);
 			}
-			std::sort(order.begin(), order.end(), [&](int a, int b) {
-				if (val[(size_t)a] != val[(size_t)b]) return val[(size_t)a] > val[(size_t)b];
-				return (uint32_t)(keys[(size_t)i * kk + a] & 0xffffffffu) > (uint32_t)(keys[(size_t)i * kk + b] & 0xffffffffu);
-			});
+			vk_host::rank_above(order, q.min_score, [&](int j) { return val[(size_t)j]; }, row_at);
 			const int n_out = std::min((int)order.size(), k);
 			for (int r = 0; r < n_out; r++) {
 				const int j = order[(size_t)r];
 				out->score[r] = val[(size_t)j];
-				out->sentence[r] = (int64_t)(uint32_t)(keys[(size_t)i * kk + j] & 0xffffffffu);
+				out->sentence[r] = row_at(j);
 				if (out->raw_score) out->raw_score[r] = raw[(size_t)j];
-				if (out->mapping && out->edge_sim)
-					for (int t = 0; t < q.len_t; t++) {
-						out->mapping[(size_t)r * q.len_t + t] = -1;
-						out->edge_sim[(size_t)r * q.len_t + t] = 0.0f;
-					}
+				if (out->mapping && out->edge_sim) vk_host::no_flow(out->mapping + (size_t)r * q.len_t, out->edge_sim + (size_t)r * q.len_t, q.len_t);
 				const size_t room = out->rows_per_winner > 0 ? (size_t)out->rows_per_winner : (size_t)VK_FAST_SENT_LEN;   // rows per winner of the caller's array (>= 64)
 				memcpy(out->sim_rows + (size_t)r * room * 16, c->h_brows + (at + j) * 64 * 16, (size_t)64 * 16 * 4);
 			}
@@ -221,23 +206,16 @@ static int query_batch_shared_pass(vk_corpus_t *c, const vk_query_desc *qs, int3
 
 	// ---- common options: gap tables, DP form
 	VkScoreBatchParams p{};
-	const int ks = q0.gap_s.kind, kt = q0.gap_t.kind;
 	float *ws = keep.array<float>(kGapTable), *wt = keep.array<float>(160);   // wt[80..159]: the subadditive closure of w_t
 	if (!is_align) {
 		p.gap_mode = 4; p.rwmd_symmetric = q0.rwmd_symmetric; p.rwmd_normalize_bow = q0.rwmd_normalize_bow;
-	} else if (ks == VK_GAP_LINEAR && kt == VK_GAP_LINEAR) {
-		p.gap_mode = 0; p.gs = q0.gap_s.u; p.gt = q0.gap_t.u;
-	} else if ((ks == VK_GAP_LINEAR || ks == VK_GAP_AFFINE) && (kt == VK_GAP_LINEAR || kt == VK_GAP_AFFINE)) {
-		p.gap_mode = 1;
-		p.a_s = ks == VK_GAP_AFFINE ? q0.gap_s.u : 0.0f; p.gs = ks == VK_GAP_AFFINE ? q0.gap_s.v : q0.gap_s.u;
-		p.a_t = kt == VK_GAP_AFFINE ? q0.gap_t.u : 0.0f; p.gt = kt == VK_GAP_AFFINE ? q0.gap_t.v : q0.gap_t.u;
-		p.open_s = p.a_s + p.gs; p.open_t = p.a_t + p.gt;
-	} else p.gap_mode = 2;
+	} else {
+		const vk_host::gap_form g = vk_host::classify_gaps(q0.gap_s, q0.gap_t);
+		p.gap_mode = g.gap_mode;
+		gap_fields(p, g);
+	}
 	for (int i = 0; i < kGapTable; i++) ws[i] = (is_align && i <= c->max_len) ? gap_cost(q0.gap_s, i) : 0.0f;
-	for (int i = 0; i < 80; i++) wt[i] = (is_align && i <= max_len_t) ? gap_cost(q0.gap_t, i) : 0.0f;
-	for (int k = 0; k < 80; k++) wt[80 + k] = wt[k];   // the subadditive closure of w_t for the in-row candidates (vk_query.cpp)
-	for (int k = 2; k <= max_len_t && k < 80; k++)
-		for (int a = 1; a < k; a++) wt[80 + k] = std::min(wt[80 + k], wt[80 + a] + wt[80 + k - a]);
+	vk_host::wt_with_closure(wt, q0.gap_t, max_len_t, is_align);
 	if (p.gap_mode == 2) p.gap_mode = c->max_short_len <= 32 ? 3 : 6;
 	const int lt = max_len_t <= 4 ? 4 : max_len_t <= 8 ? 8 : max_len_t <= 12 ? 12 : 16;
 	p.s_rows_per_wave = c->max_group_tiles * 16;
@@ -276,8 +254,8 @@ static int query_batch_shared_pass(vk_corpus_t *c, const vk_query_desc *qs, int3
 		if ((rc = c->d_boost.reserve((size_t)n + 8, &c->device_bytes))) return rc;
 		VK_HIP(hipMemcpyAsync(c->d_boost, q0.boost, (size_t)n * 4, hipMemcpyHostToDevice, st));   // no long slices: rows == slices
 	}
-	p.tiles = c->d_tiles; p.sent_start = c->d_sent_start; p.sent_end = c->d_sent_end; p.n_sent = (int32_t)n;
-	p.nk32 = c->nk32; p.tail = c->tail; p.tile_bytes = c->tile_bytes;
+	corpus_fields(p, c);
+	p.n_sent = (int32_t)n;
 	p.qtiles = c->d_bq; p.locality = q0.locality; p.ws = c->d_ws; p.wt = c->d_wt + 80; p.wt0 = c->d_wt;
 	p.boost = q0.boost ? (float *)c->d_boost : nullptr; p.scores = c->d_bscores; p.raw = c->d_braw;
 	if (q0.want_flow && q0.algorithm == VK_ALG_ALIGN) p.raw = nullptr;   // the flow kernel restates the winners' aligner scores; nothing else reads the array (no submatch weights here)
@@ -324,11 +302,10 @@ static int query_batch_shared_pass(vk_corpus_t *c, const vk_query_desc *qs, int3
 		if (do_flow) {
 			for (int i = 0; i < qb; i++) {
 				VkFlowParams f{};
-				f.tiles = c->d_tiles; f.sent_start = c->d_sent_start; f.sent_end = c->d_sent_end;
-				f.layout = VK_DEV_LAYOUT_CONTEXTUAL; f.nk32 = c->nk32; f.tail = c->tail; f.tile_bytes = c->tile_bytes;
+				corpus_fields_ids(f, c);   // (contextual bf16 tiles: checked above)
 				f.qtile = c->d_bq + (size_t)i * c->tile_bytes; f.len_t = qs[base + i].len_t; f.locality = q0.locality;
 				f.gap_mode = (p.gap_mode == 3 || p.gap_mode == 6) ? 2 : p.gap_mode; f.max_len = c->max_len;
-				f.gs = p.gs; f.gt = p.gt; f.a_s = p.a_s; f.a_t = p.a_t; f.open_s = p.open_s; f.open_t = p.open_t;
+				gap_fields(f, p);
 				f.ws = c->d_ws; f.wt = c->d_wt;
 				f.d = c->desc.d;   // canonical similarity rows (sim_canon)
 				f.keys = c->d_bkeys[cur] + (size_t)i * stride;
@@ -349,34 +326,20 @@ static int query_batch_shared_pass(vk_corpus_t *c, const vk_query_desc *qs, int3
 			vk_topk_out *out = &outs[base + i];
 			// winners of this query: position in the selection, score.  With traceback the score is restated from the canonical
 			// aligner score of the flow kernel (the oracle's, bit for bit) and the winners are put in that order (vk_query).
-			std::vector<int> order;
+			const auto row_at = [&](int j) { return (int64_t)vk_host::key_row(keys[(size_t)i * kk + j]); };
+			std::vector<int> order((size_t)vk_host::count_keys(keys.data() + (size_t)i * kk, kk));
 			std::vector<float> val((size_t)kk, 0.0f);
-			for (int j = 0; j < kk; j++) {
-				const uint64_t key = keys[(size_t)i * kk + j];
-				if (key == 0) break;
-				const uint32_t ob = (uint32_t)(key >> 32);
-				const uint32_t bits = (ob & 0x80000000u) ? (ob & 0x7fffffffu) : ~ob;
-				memcpy(&val[(size_t)j], &bits, 4);
-				if (do_flow) {
-					float matched = 0.0f;
-					for (int t = 0; t < q.len_t; t++) matched += map[((size_t)i * kk + j) * 16 + t] >= 0 ? 1.0f : 0.0f;
-					const float total = (float)q.len_t, uw = powf((total - matched) / total, 0.0f);
-					const float ref = matched + uw * (total - matched);
-					const float boost = q.boost ? q.boost[(int64_t)(uint32_t)(key & 0xffffffffu)] : 1.0f;
-					val[(size_t)j] = (raw[(size_t)i * kk + j] / ref) * boost;
-					if (!(val[(size_t)j] > q.min_score)) continue;
-				}
-				order.push_back(j);
+			for (int j = 0; j < (int)order.size(); j++) {
+				order[(size_t)j] = j;
+				// (no tag weights in a batch: every matched token counts 1)
+				val[(size_t)j] = !do_flow ? vk_host::key_score(keys[(size_t)i * kk + j])
+					: vk_host::reference_score(raw[(size_t)i * kk + j], &map[((size_t)i * kk + j) * 16], q.len_t, nullptr, (float)q.len_t, 0.0f, q.boost ? q.boost[row_at(j)] : 1.0f);
 			}
-			if (do_flow) std::sort(order.begin(), order.end(), [&](int a, int b2) {
-				if (val[(size_t)a] != val[(size_t)b2]) return val[(size_t)a] > val[(size_t)b2];
-				return (uint32_t)(keys[(size_t)i * kk + a] & 0xffffffffu) > (uint32_t)(keys[(size_t)i * kk + b2] & 0xffffffffu);
-			});
+			if (do_flow) vk_host::rank_above(order, q.min_score, [&](int j) { return val[(size_t)j]; }, row_at);
 			int n_out = 0;
 			for (const int j : order) {
 				if (n_out >= k) break;
-				const uint64_t key = keys[(size_t)i * kk + j];
-				const int64_t g = (int64_t)(uint32_t)(key & 0xffffffffu);
+				const int64_t g = row_at(j);
 				out->score[n_out] = val[(size_t)j];
 				out->sentence[n_out] = g;
 				if (out->raw_score) {
@@ -712,33 +675,19 @@ static int query_batch_body(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_q
 		for (int j = 0; j < k; j++) {
 			const uint64_t key = keys[(size_t)i * k + j];
 			if (key == 0) break;
-			const uint32_t ob = (uint32_t)(key >> 32);
-			const uint32_t bits = (ob & 0x80000000u) ? (ob & 0x7fffffffu) : ~ob;
-			float s;
-			memcpy(&s, &bits, 4);
-			const int64_t g = (int64_t)(uint32_t)(key & 0xffffffffu);
+			const float s = vk_host::key_score(key);
+			const int64_t g = (int64_t)vk_host::key_row(key);
 			out->score[j] = s;
 			out->sentence[j] = g;
 			if (out->raw_score) out->raw_score[j] = (qs[i].boost ? s / qs[i].boost[g] : s) * (float)qs[i].len_t;
-			if (qs[i].want_flow && out->mapping && out->edge_sim)
-				for (int t = 0; t < qs[i].len_t; t++) {
-					out->mapping[(size_t)j * qs[i].len_t + t] = -1;
-					out->edge_sim[(size_t)j * qs[i].len_t + t] = 0.0f;
-				}
+			if (qs[i].want_flow && out->mapping && out->edge_sim) vk_host::no_flow(out->mapping + (size_t)j * qs[i].len_t, out->edge_sim + (size_t)j * qs[i].len_t, qs[i].len_t);
 			n_out++;
 		}
 		out->n_out = n_out;
 	}
 	if (canon_tr && (rc = batch_winner_rows(c, qs, n_queries, outs, keys.data(), kk, k, st, keep, tiles16.empty() ? nullptr : tiles16.data()))) return rc;
 	c->have_scores = false;
-	float ms = 0;
-	vk_timings t{};
-	if (hipEventElapsedTime(&ms, c->ev[0], c->ev[5]) == hipSuccess) t.prepare_ms = ms;
-	if (hipEventElapsedTime(&ms, c->ev[5], c->ev[1]) == hipSuccess) t.queue_ms = ms;
-	if (hipEventElapsedTime(&ms, c->ev[1], c->ev[6]) == hipSuccess) t.score_ms = ms;
-	if (hipEventElapsedTime(&ms, c->ev[6], c->ev[3]) == hipSuccess) t.topk_ms = ms;
-	if (hipEventElapsedTime(&ms, c->ev[0], c->ev[4]) == hipSuccess) t.total_ms = ms - t.queue_ms;
-	c->last = t;
+	state_timings(c, false, 6);   // (scored: the GEMM's end, before the selection)
 	return VK_OK;
 }
 

@@ -6,6 +6,8 @@
 #include "../../include/vectorian_hip.h"
 #include "vk_device.h"
 #include "vk_devbuf.h"
+#include "vk_guard.h"
+#include "vk_result_host.h"
 
 #include <algorithm>
 #include <atomic>
@@ -51,14 +53,7 @@ float bf16_to_f32(uint16_t b) {
 	return f;
 }
 
-float gap_cost(const vk_gap &g, int k) {
-	if (k <= 0) return 0.0f;
-	switch (g.kind) {
-	case VK_GAP_LINEAR: return g.u * (float)k;
-	case VK_GAP_AFFINE: return g.u + g.v * (float)k;
-	default: return (g.table && k < g.n_table) ? g.table[k] : INFINITY;
-	}
-}
+using vk_host::gap_cost;
 
 constexpr int kTopkChunk = 2048;
 constexpr int kGapTable = 640;   // entries of the gap tables sent to the device (> VK_MAX_SENT_LEN)
@@ -205,8 +200,104 @@ template <typename T> int alloc_shared(vk_corpus *c, T **p, size_t n) {
 // ring's mutex so that the peer cannot be unlinked and destroyed in between (vk_corpus.cpp)
 int vk_wait_peer_turn(vk_corpus *c, hipStream_t st);
 int vk_validate_query(const vk_corpus *c, const vk_query_desc *q, const vk_topk_out *out);
-class vk_host_keep;
 int vk_longq_query(vk_corpus *c, const vk_query_desc *q, vk_topk_out *out, vk_host_keep &keep);   // vk_longq_host.cpp
 void vk_pack_query(const vk_corpus *c, const vk_query_desc *q, std::vector<uint8_t> &tile, float *mags);
+
+// ---- steps the query paths share (vk_query.cpp, vk_longq_host.cpp, vk_batch.cpp); the rules without a device are in vk_result_host.h
+namespace {
+
+// The corpus fields every kernel parameter struct has ...
+template <typename P> void corpus_fields(P &p, const vk_corpus *c) {
+	p.tiles = c->d_tiles; p.sent_start = c->d_sent_start; p.sent_end = c->d_sent_end;
+	p.nk32 = c->nk32; p.tail = c->tail; p.tile_bytes = c->tile_bytes;
+}
+// ... and those of the structs that serve both layouts and both precisions (d_tok_id is null unless the layout is static)
+template <typename P> void corpus_fields_ids(P &p, const vk_corpus *c) {
+	corpus_fields(p, c);
+	p.tok_id = c->d_tok_id; p.prec = c->prec;
+	p.layout = c->desc.layout == VK_LAYOUT_STATIC ? VK_DEV_LAYOUT_STATIC : VK_DEV_LAYOUT_CONTEXTUAL;
+}
+// the recurrence's constants (vk_host::gap_form, or another parameter struct) into a parameter struct; gap_mode stays with the caller
+template <typename P, typename G> void gap_fields(P &p, const G &g) {
+	p.gs = g.gs; p.gt = g.gt; p.a_s = g.a_s; p.a_t = g.a_t; p.open_s = g.open_s; p.open_t = g.open_t;
+}
+
+// c->last from the events of a query: 0 start, 5 before / 1 after the wait for the peer, `scored` the scoring pass has ended (2; the
+// batched GEMM: 6), 3 selected, 4 done.  flow: whether the path has a traceback stage of its own between 3 and 4.
+void state_timings(vk_corpus *c, bool flow, int scored = 2) {
+	float ms = 0;
+	vk_timings t{};
+	if (hipEventElapsedTime(&ms, c->ev[0], c->ev[5]) == hipSuccess) t.prepare_ms = ms;
+	if (hipEventElapsedTime(&ms, c->ev[5], c->ev[1]) == hipSuccess) t.queue_ms = ms;
+	if (hipEventElapsedTime(&ms, c->ev[1], c->ev[scored]) == hipSuccess) t.score_ms = ms;
+	if (hipEventElapsedTime(&ms, c->ev[scored], c->ev[3]) == hipSuccess) t.topk_ms = ms;
+	if (flow && hipEventElapsedTime(&ms, c->ev[3], c->ev[4]) == hipSuccess) t.flow_ms = ms;
+	if (hipEventElapsedTime(&ms, c->ev[0], c->ev[4]) == hipSuccess) t.total_ms = ms - t.queue_ms;
+	c->last = t;
+}
+
+// The kk best of d_scores above `floor` as keys, best first, in *d_sel (one of d_keys[0 / 1]).
+// Wave-streaming selection (kk <= 64): n -> ceil(n / 4096) * kk keys -> ... -> kk keys
+int select_waves(vk_corpus *c, float floor, int kk, hipStream_t st, const uint64_t **d_sel) {
+	int64_t nw = 0;
+	int cur = 0;
+	VK_HIP(vk_launch_topk_wave(c->d_scores, nullptr, c->n_entries, floor, kk, 4096, c->d_keys[0], &nw, st));
+	while (nw > 1) {
+		const int64_t nkeys = nw * kk;
+		const int64_t per_wave = nkeys <= 16384 ? nkeys : 4096;
+		VK_HIP(vk_launch_topk_wave(nullptr, c->d_keys[cur], nkeys, 0.0f, kk, per_wave, c->d_keys[1 - cur], &nw, st));
+		cur = 1 - cur;
+	}
+	*d_sel = c->d_keys[cur];
+	return VK_OK;
+}
+// Block selection (kk <= VK_MAX_MATCHES): each block sorts 2,048 keys and keeps its kk best, until one block is left
+int select_blocks(vk_corpus *c, float floor, int kk, hipStream_t st, const uint64_t **d_sel) {
+	int nb = 0, cur = 0;
+	VK_HIP(vk_launch_topk_scores(c->d_scores, c->n_entries, floor, kk, c->d_keys[0], &nb, st));
+	while (nb > 1) {
+		VK_HIP(vk_launch_topk_keys(c->d_keys[cur], (int64_t)nb * kk, kk, c->d_keys[1 - cur], &nb, st));
+		cur = 1 - cur;
+	}
+	*d_sel = c->d_keys[cur];
+	return VK_OK;
+}
+
+// the caller's boost per slice as d_boost per row of the slice table (padding rows: 1)
+int upload_boost(vk_corpus *c, const float *boost, vk_host_keep &keep, hipStream_t st) {
+	const int64_t n = c->n_entries;
+	if (int rc = c->d_boost.reserve((size_t)n + 8, &c->device_bytes)) return rc;
+	if (!c->entry_sent.empty()) {
+		std::vector<float> &rows = keep.vec<float>((size_t)n);
+		for (int64_t e = 0; e < n; e++) rows[(size_t)e] = c->entry_sent[(size_t)e] >= 0 ? boost[c->entry_sent[(size_t)e]] : 1.0f;
+		boost = rows.data();
+	}
+	VK_HIP(hipMemcpyAsync(c->d_boost, boost, (size_t)n * 4, hipMemcpyHostToDevice, st));
+	return VK_OK;
+}
+
+// row of the slice table of a slice (long slices sit in padded groups); the inverse of entry_sent is built when first needed
+int64_t row_of_sentence(vk_corpus *c, int64_t s) {
+	if (c->entry_sent.empty()) return s;
+	if (c->sent_entry.empty()) {
+		c->sent_entry.assign((size_t)c->desc.n_sentences, -1);
+		for (int64_t e = 0; e < c->n_entries; e++) if (c->entry_sent[(size_t)e] >= 0) c->sent_entry[(size_t)c->entry_sent[(size_t)e]] = (int32_t)e;
+	}
+	return (int64_t)c->sent_entry[(size_t)s];
+}
+
+// the exact solver over the `count` candidates at w.keys: slices of at most 64 tokens, then (long_too) those of 65 .. 512 tokens
+int launch_wrd_exact_both(vk_corpus *c, VkWrdParams &w, int count, float *scores_to_mark, bool long_too, hipStream_t st) {
+	VK_HIP(vk_launch_wrd_exact(&w, count, scores_to_mark, st));
+	if (long_too) {
+		if (w.nq > 1)
+			if (int rc = c->d_wrdl_scratch.reserve((size_t)vk_wrd_long_blocks() * vk_wrd_long_scratch_bytes(), &c->device_bytes)) return rc;
+		w.scratch = c->d_wrdl_scratch; w.scratch_stride = (int64_t)vk_wrd_long_scratch_bytes();
+		VK_HIP(vk_launch_wrd_exact_long(&w, count, st));
+	}
+	return VK_OK;
+}
+
+} // namespace
 
 #endif

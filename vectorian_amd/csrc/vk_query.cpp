@@ -13,9 +13,14 @@
 // does not fit is refused before anything is enqueued -- with the gap mode of the launch, not a stand-in (round 2 tested mode 6 and
 // launched 5 or 7, whose strips are up to 1,280 bytes larger: a borderline shape failed in hipFuncSetAttribute instead).
 struct Score32Plan { int gap_mode, wave_tiles; bool fits, only_kernel; };
+// Exact transport (WRD, the non-relaxed WMD): a bound pass over all slices, then the exact solver on the candidates.
+static bool exact_transport(const vk_query_desc *q) { return q->algorithm == VK_ALG_WRD || (q->algorithm == VK_ALG_RWMD && q->wmd_full); }
+// ... and with the 1:n RWMD the algorithms that keep a slice's bag of words in LDS: a query of more than 16 tokens has the multi-block
+// kernel and the long slices' own kernels, no wide kernel
+static bool transport_in_lds(const vk_query_desc *q) { return exact_transport(q) || (q->algorithm == VK_ALG_RWMD && !q->rwmd_injective); }
 static Score32Plan score32_plan(const vk_corpus *c, const vk_query_desc *q) {
 	const bool is_static = c->desc.layout == VK_LAYOUT_STATIC;
-	const bool bound_pass = q->algorithm == VK_ALG_WRD || (q->algorithm == VK_ALG_RWMD && q->wmd_full);
+	const bool bound_pass = exact_transport(q);
 	const bool fill = q->algorithm == VK_ALG_RWMD && !q->wmd_full && !q->rwmd_injective;
 	const int ks = q->gap_s.kind, kt = q->gap_t.kind;
 	int gm;
@@ -49,8 +54,7 @@ int vk_validate_query(const vk_corpus *c, const vk_query_desc *q, const vk_topk_
 		if (out->sim_rows) return fail(VK_ERR_UNSUPPORTED, "queries of more than 64 tokens: similarity rows of the winners are not returned");
 		if (q->max_matches > VK_MAX_MATCHES) return fail(VK_ERR_UNSUPPORTED, "queries of more than 64 tokens: max_matches <= VK_MAX_MATCHES");
 	}
-	const bool exact_tr = q->algorithm == VK_ALG_WRD || (q->algorithm == VK_ALG_RWMD && (q->wmd_full || !q->rwmd_injective));   // multi-block kernel + kernels of their own for the long slices: no wide kernel
-	if (q->len_t > VK_FAST_QUERY_LEN && exact_tr && !score32_plan(c, q).fits)
+	if (q->len_t > VK_FAST_QUERY_LEN && transport_in_lds(q) && !score32_plan(c, q).fits)
 		return fail(VK_ERR_UNSUPPORTED, "exact transport / 1:n RWMD with a query of more than 16 tokens: the query tiles of rows this wide and one wave's similarity strip exceed the LDS of a workgroup (160 KiB)");
 	// Slices of more than VK_MAX_SENT_LEN tokens (whole documents as slices, up to VK_MAX_DOC_LEN): alignments -- the
 	// one-wave-per-slice kernel with the slice's state in global memory (vk_wide_kernel, global-state form; the same form takes a
@@ -80,7 +84,7 @@ int vk_validate_query(const vk_corpus *c, const vk_query_desc *q, const vk_topk_
 	if (q->only_slices) {
 		if (q->n_only < 1 || q->n_only > VK_MAX_MATCHES || q->n_only > out->capacity) return fail(VK_ERR_INVALID, "only_slices: n_only out of range (1 .. min(VK_MAX_MATCHES, capacity))");
 		const bool relaxed = q->algorithm == VK_ALG_RWMD && !q->wmd_full && out->sim_rows != nullptr;   // restated on the host from the rows
-		const bool exact = q->algorithm == VK_ALG_WRD || (q->algorithm == VK_ALG_RWMD && q->wmd_full);  // every listed slice solved
+		const bool exact = exact_transport(q);  // every listed slice solved
 		// (a submatch weight: alignments only -- the score of a listed slice is its aligner score over the reference score of its own
 		// traceback, metric/alignment.h:84-106, no candidate rounds; the transports' reference score does not depend on it)
 		if (!(q->algorithm == VK_ALG_ALIGN || relaxed || exact) || !q->want_flow || (q->submatch_weight != 0.0f && q->algorithm != VK_ALG_ALIGN))
@@ -197,9 +201,8 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	// the host states their SparseFlow / DenseFlow.  rows_idx: rows of the slice table, best first.
 	// what vk_wrd_exact_kernel / vk_rows_kernel need to restate the similarity rows of a slice (tag weights included)
 	auto fill_transport = [&](VkWrdParams &w) {
-		w.tiles = c->d_tiles; w.tok_id = c->d_tok_id; w.table = c->d_table; w.table_stride = (int64_t)c->n_tiles * 16 * 16;
-		w.sent_start = c->d_sent_start; w.sent_end = c->d_sent_end;
-		w.layout = is_static_l ? VK_DEV_LAYOUT_STATIC : VK_DEV_LAYOUT_CONTEXTUAL; w.nk32 = c->nk32; w.tail = c->tail; w.tile_bytes = c->tile_bytes; w.prec = c->prec;
+		corpus_fields_ids(w, c);
+		w.table = c->d_table; w.table_stride = (int64_t)c->n_tiles * 16 * 16;
 		w.qtile = c->d_qtile; w.nq = (q->len_t + 15) / 16; w.len_t = q->len_t; w.mag = c->d_mag;
 		w.d = c->desc.d; w.q_ids = is_static_l ? (int32_t *)c->d_qids : nullptr;   // canonical similarity rows (sim_canon)
 		w.ref_total = (float)q->len_t;
@@ -235,7 +238,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		if ((rc2 = c->d_wrd_raw.reserve((size_t)VK_MAX_MATCHES, &c->device_bytes))) return rc2;
 		if ((rc2 = c->d_wrd_val.reserve((size_t)VK_MAX_MATCHES, &c->device_bytes))) return rc2;
 		std::vector<uint64_t> &hk = keep.vec<uint64_t>((size_t)cnt);
-		for (int i = 0; i < cnt; i++) hk[(size_t)i] = (1ull << 32) | (uint64_t)(uint32_t)rows_idx[(size_t)i];
+		for (int i = 0; i < cnt; i++) hk[(size_t)i] = vk_host::key_of_row(rows_idx[(size_t)i]);
 		VK_HIP(hipMemcpyAsync(c->d_keys[1], hk.data(), hk.size() * 8, hipMemcpyHostToDevice, c->stream));
 		VkWrdParams w{};
 		fill_transport(w);
@@ -250,12 +253,8 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 			memcpy(w.qmass, qmass, sizeof w.qmass);
 			w.raw_out = c->d_wrd_raw; w.val_out = c->d_wrd_val; w.plan_out = c->d_plan_out;
 			VK_HIP(hipMemsetAsync(c->d_plan_out, 0, need * 4, c->stream));   // a solver writes the columns of its winner's tokens only
-			VK_HIP(vk_launch_wrd_exact(&w, cnt, nullptr, c->stream));
-			if (R > VK_FAST_SENT_LEN && c->max_len > VK_FAST_SENT_LEN) {   // winners of 65 .. R tokens: the long solver restates their plans
-				if (w.nq > 1 && (rc2 = c->d_wrdl_scratch.reserve((size_t)vk_wrd_long_blocks() * vk_wrd_long_scratch_bytes(), &c->device_bytes))) return rc2;
-				w.scratch = c->d_wrdl_scratch; w.scratch_stride = (int64_t)vk_wrd_long_scratch_bytes();
-				VK_HIP(vk_launch_wrd_exact_long(&w, cnt, c->stream));
-			}
+			// (winners of 65 .. R tokens: the long solver restates their plans)
+			if ((rc2 = launch_wrd_exact_both(c, w, cnt, nullptr, R > VK_FAST_SENT_LEN && c->max_len > VK_FAST_SENT_LEN, c->stream))) return rc2;
 			VK_HIP(hipMemcpyAsync(out->plan, c->d_plan_out, need * 4, hipMemcpyDeviceToHost, c->stream));
 		}
 		VK_HIP(hipStreamSynchronize(c->stream));
@@ -292,10 +291,9 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	VkScoreParams p{};
 	bool span_skip_raw = false;   // span-embedding path without its second output array
 	float qmass_all[VK_MAX_QUERY_LEN] = {0};   // masses of the query tokens (transport algorithms), all 64 columns
-	const int ks = q->gap_s.kind, kt = q->gap_t.kind;
 	const size_t n_ws = std::max<size_t>((size_t)kGapTable, (size_t)c->max_len + 2);   // w_s up to the longest slice
 	std::vector<float> &ws = keep.vec<float>(n_ws);
-	float *wt = keep.array<float>(160);   // wt[0..79]: w_t as given; wt[80..159]: its subadditive closure
+	float *wt = keep.array<float>(160);   // wt[0..79]: w_t as given; wt[80..159]: its subadditive closure (vk_result_host.h)
 	const bool is_align = q->algorithm == VK_ALG_ALIGN;
 	if (q->algorithm == VK_ALG_WRD) {
 		p.gap_mode = 5;
@@ -335,32 +333,15 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 			memcpy(p.qmass, qmass_all, sizeof p.qmass);
 			if (ids && q->tag_weights && q->q_tags) p.tag_s = c->d_tag;
 		}
-	} else if (ks == VK_GAP_LINEAR && kt == VK_GAP_LINEAR) {
-		p.gap_mode = 0;
-		p.gs = q->gap_s.u; p.gt = q->gap_t.u;
-	} else if ((ks == VK_GAP_LINEAR || ks == VK_GAP_AFFINE) && (kt == VK_GAP_LINEAR || kt == VK_GAP_AFFINE)) {
-		p.gap_mode = 1;
-		p.a_s = ks == VK_GAP_AFFINE ? q->gap_s.u : 0.0f;
-		p.gs = ks == VK_GAP_AFFINE ? q->gap_s.v : q->gap_s.u;
-		p.a_t = kt == VK_GAP_AFFINE ? q->gap_t.u : 0.0f;
-		p.gt = kt == VK_GAP_AFFINE ? q->gap_t.v : q->gap_t.u;
-		p.open_s = p.a_s + p.gs;
-		p.open_t = p.a_t + p.gt;
 	} else {
-		p.gap_mode = 2;
+		const vk_host::gap_form g = vk_host::classify_gaps(q->gap_s, q->gap_t);
+		p.gap_mode = g.gap_mode;
+		gap_fields(p, g);
 	}
 	for (size_t i = 0; i < n_ws; i++) ws[i] = (is_align && (int64_t)i <= c->max_len) ? gap_cost(q->gap_s, (int)i) : 0.0f;
 	if ((rc = c->d_ws.reserve(n_ws, &c->device_bytes))) return rc;
-	for (int i = 0; i < 80; i++) wt[i] = (is_align && i <= q->len_t) ? gap_cost(q->gap_t, i) : 0.0f;
-	for (int i = 80; i < 160; i++) wt[i] = 0.0f;
-	// The register-history kernels take their in-row candidates from the row's values before in-row gaps, which is the
-	// sequential recurrence with w_t replaced by its subadditive closure w* (dp_general_reg in vk_common.hip.h): wt[80..159].
-	// (Round 1 sent every table that was not strictly subadditive -- a linear cost handed over as a table, a convex one -- to the
-	// LDS-history kernel with its serial in-row chain: 12.7 ms per 1 M x 32 tokens against 2.9 ms.)
+	vk_host::wt_with_closure(wt, q->gap_t, q->len_t, is_align);
 	bool wide_sub = false;   // a long query with general gaps: the multi-block kernel takes it
-	for (int k = 0; k < 80; k++) wt[80 + k] = wt[k];
-	for (int k = 2; k <= q->len_t && k < 80; k++)
-		for (int a = 1; a < k; a++) wt[80 + k] = std::min(wt[80 + k], wt[80 + a] + wt[80 + k - a]);
 	if (p.gap_mode == 2) {
 		if (!wide_score) p.gap_mode = c->max_short_len <= 32 ? 3 : 6;
 		wide_sub = wide;
@@ -368,17 +349,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	VK_HIP(hipMemcpyAsync(c->d_ws, ws.data(), n_ws * sizeof(float), hipMemcpyHostToDevice, st));
 	VK_HIP(hipMemcpyAsync(c->d_wt, wt, 160 * sizeof(float), hipMemcpyHostToDevice, st));
 
-	std::vector<float> &boost_rows = keep.vec<float>();
-	if (q->boost) {
-		if ((rc = c->d_boost.reserve((size_t)n + 8, &c->device_bytes))) return rc;
-		const float *src = q->boost;
-		if (!c->entry_sent.empty()) {
-			boost_rows.resize((size_t)n);
-			for (int64_t e = 0; e < n; e++) boost_rows[(size_t)e] = c->entry_sent[(size_t)e] >= 0 ? q->boost[c->entry_sent[(size_t)e]] : 1.0f;
-			src = boost_rows.data();
-		}
-		VK_HIP(hipMemcpyAsync(c->d_boost, src, (size_t)n * 4, hipMemcpyHostToDevice, st));
-	}
+	if (q->boost && (rc = upload_boost(c, q->boost, keep, st))) return rc;
 
 	const bool is_static = c->desc.layout == VK_LAYOUT_STATIC;
 	const int64_t table_stride = (int64_t)c->n_tiles * 16 * 16;
@@ -397,9 +368,8 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	VK_HIP(hipEventRecord(c->ev[5], st));
 	if ((rc = vk_wait_peer_turn(c, st))) return rc;
 	VK_HIP(hipEventRecord(c->ev[1], st));
-	p.tiles = c->d_tiles; p.tok_id = c->d_tok_id; p.table = c->d_table; p.sent_start = c->d_sent_start; p.sent_end = c->d_sent_end;
-	p.n_sent = (int32_t)n; p.layout = is_static ? VK_DEV_LAYOUT_STATIC : VK_DEV_LAYOUT_CONTEXTUAL;
-	p.nk32 = c->nk32; p.tail = c->tail; p.tile_bytes = c->tile_bytes; p.prec = c->prec;
+	corpus_fields_ids(p, c);
+	p.table = c->d_table; p.n_sent = (int32_t)n;
 	p.qtile = c->d_qtile; p.len_t = q->len_t; p.locality = q->locality;
 	p.ws = c->d_ws; p.wt = c->d_wt + 80; p.wt0 = c->d_wt;
 	p.boost = q->boost ? (float *)c->d_boost : nullptr;
@@ -505,13 +475,12 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		return VK_OK;
 	};
 	if (wide || flow_doc || rwmd_long_doc) {
-		wp.tiles = c->d_tiles; wp.tok_id = c->d_tok_id; wp.table = c->d_table; wp.table_stride = table_stride;
-		wp.sent_start = c->d_sent_start; wp.sent_end = c->d_sent_end; wp.n_sent = (int32_t)n; wp.layout = p.layout;
-		wp.nk32 = c->nk32; wp.tail = c->tail; wp.tile_bytes = c->tile_bytes; wp.prec = c->prec;
+		corpus_fields_ids(wp, c);
+		wp.table = c->d_table; wp.table_stride = table_stride; wp.n_sent = (int32_t)n;
 		wp.qtile = c->d_qtile; wp.nq = nq; wp.len_t = q->len_t; wp.locality = q->locality; wp.max_len = c->max_len;
 		wp.gap_mode = (p.gap_mode == 3 || p.gap_mode == 6) ? 2 : p.gap_mode;   // (the fused kernels' register-history forms of general gaps)
 		wp.rwmd_symmetric = p.rwmd_symmetric; wp.rwmd_normalize_bow = p.rwmd_normalize_bow;
-		wp.gs = p.gs; wp.gt = p.gt; wp.a_s = p.a_s; wp.a_t = p.a_t; wp.open_s = p.open_s; wp.open_t = p.open_t;
+		gap_fields(wp, p);
 		wp.ws = c->d_ws; wp.wt = c->d_wt; wp.wt0 = c->d_wt;
 		if (wp.gap_mode == 2 && c->max_len >= 2) {   // the constant tail of w_s (a saturated table): from which k on
 			int kt = c->max_len;
@@ -526,16 +495,14 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		}
 		wp.boost = p.boost; wp.scores = c->d_scores; wp.raw = c->d_raw;
 		wp.d = c->desc.d; wp.q_ids = is_static ? (int32_t *)c->d_qids : nullptr;   // FLOW: canonical similarity rows (sim_canon)
-		{   // as for the 16-column kernel: the aligner scores of all slices only if something reads them
-			const bool exact_tr2 = q->algorithm == VK_ALG_WRD || (q->algorithm == VK_ALG_RWMD && q->wmd_full);
-			if (((is_align && q->want_flow) || exact_tr2) && !(q->submatch_weight > 0.0f) && !getenv("VK_KEEP_RAW")) wp.raw = nullptr;
-		}
+		// as for the 16-column kernel: the aligner scores of all slices only if something reads them
+		if (((is_align && q->want_flow) || exact_transport(q)) && !(q->submatch_weight > 0.0f) && !getenv("VK_KEEP_RAW")) wp.raw = nullptr;
 		if (wide_score) {
 		// 17..32 tokens with linear / affine gaps over a bf16 contextual corpus of short slices: the fused two-block kernel
 		// (affine: the prefix-scan form of F needs open_t >= extend_t, as dp_affine)
 		// (33..64 tokens: one slice per wave and four column blocks)
 		const bool rwmd_inj = q->algorithm == VK_ALG_RWMD && (p.gap_mode == 4 || p.gap_mode == 7) && !q->wmd_full;
-		const bool bound_pass = q->algorithm == VK_ALG_WRD || (q->algorithm == VK_ALG_RWMD && q->wmd_full);   // exact transport: stage 1
+		const bool bound_pass = exact_transport(q);   // stage 1
 		// exact transport over a corpus with long slices: the multi-block kernel skips them (their groups are padded, vk_corpus.cpp),
 		// vk_long_bound_kernel bounds them
 		const bool long_apart = (bound_pass || p.gap_mode == 7) && c->n_long_groups > 0;
@@ -612,10 +579,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	// the aligner scores of all slices: read by the submatch bound and, without traceback, for the winners; with traceback the
 	// flow kernel restates those of the winners
 	// (exact transport: the solver states them); a second output array costs the stream 1 % (2.90 -> 2.87 ms per 1 M x 32 x 300-d)
-	{
-		const bool exact_tr2 = q->algorithm == VK_ALG_WRD || (q->algorithm == VK_ALG_RWMD && q->wmd_full);
-		if (((is_align && q->want_flow) || exact_tr2) && !(q->submatch_weight > 0.0f) && !getenv("VK_KEEP_RAW")) p.raw = nullptr;
-	}
+	if (((is_align && q->want_flow) || exact_transport(q)) && !(q->submatch_weight > 0.0f) && !getenv("VK_KEEP_RAW")) p.raw = nullptr;
 	p.s_rows_per_wave = is_static ? (c->max_group_tokens + 15) / 16 * 16 : c->max_group_tiles * 16;
 	p.h_rows = c->max_short_len + 1;
 	const int lt = q->len_t <= 4 ? 4 : q->len_t <= 8 ? 8 : q->len_t <= 12 ? 12 : 16;   // strip rows hold the padded query columns (launch_score_lt)
@@ -670,19 +634,14 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	}
 	}
 
-	const bool exact_transport = q->algorithm == VK_ALG_WRD || (q->algorithm == VK_ALG_RWMD && q->wmd_full);
-	if (exact_transport && only) {
+	if (exact_transport(q) && only) {
 		// ---- only_slices: the listed slices solved exactly, in the caller's order (no bound pass ran, nothing is pruned)
-		if (!c->entry_sent.empty() && c->sent_entry.empty()) {
-			c->sent_entry.assign((size_t)c->desc.n_sentences, -1);
-			for (int64_t e = 0; e < n; e++) if (c->entry_sent[(size_t)e] >= 0) c->sent_entry[(size_t)c->entry_sent[(size_t)e]] = (int32_t)e;
-		}
 		const int cnt = q->n_only;
 		std::vector<uint64_t> &hk = keep.vec<uint64_t>((size_t)cnt);
 		std::vector<int64_t> rows_idx((size_t)cnt);
 		for (int i = 0; i < cnt; i++) {
-			rows_idx[(size_t)i] = c->sent_entry.empty() ? q->only_slices[i] : (int64_t)c->sent_entry[(size_t)q->only_slices[i]];
-			hk[(size_t)i] = (1ull << 32) | (uint64_t)(uint32_t)rows_idx[(size_t)i];
+			rows_idx[(size_t)i] = row_of_sentence(c, q->only_slices[i]);
+			hk[(size_t)i] = vk_host::key_of_row(rows_idx[(size_t)i]);
 		}
 		if ((rc = c->d_wrd_raw.reserve((size_t)VK_MAX_MATCHES, &c->device_bytes))) return rc;
 		if ((rc = c->d_wrd_val.reserve((size_t)VK_MAX_MATCHES, &c->device_bytes))) return rc;
@@ -695,12 +654,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		w.boost = p.boost; w.raw_out = c->d_wrd_raw; w.val_out = c->d_wrd_val; w.keys = c->d_keys[0];
 		VK_HIP(hipMemsetAsync(c->d_wrd_raw, 0xff, (size_t)cnt * 4, st));   // NaN: a slice no solver takes (empty) stays marked
 		VK_HIP(hipMemsetAsync(c->d_wrd_val, 0xff, (size_t)cnt * 4, st));
-		VK_HIP(vk_launch_wrd_exact(&w, cnt, nullptr, st));
-		if (c->max_len > VK_FAST_SENT_LEN) {
-			if (w.nq > 1 && (rc = c->d_wrdl_scratch.reserve((size_t)vk_wrd_long_blocks() * vk_wrd_long_scratch_bytes(), &c->device_bytes))) return rc;
-			w.scratch = c->d_wrdl_scratch; w.scratch_stride = (int64_t)vk_wrd_long_scratch_bytes();
-			VK_HIP(vk_launch_wrd_exact_long(&w, cnt, st));
-		}
+		if ((rc = launch_wrd_exact_both(c, w, cnt, nullptr, c->max_len > VK_FAST_SENT_LEN, st))) return rc;
 		std::vector<float> &vals = keep.vec<float>((size_t)cnt), &raws = keep.vec<float>((size_t)cnt);
 		VK_HIP(hipMemcpyAsync(vals.data(), c->d_wrd_val, (size_t)cnt * 4, hipMemcpyDeviceToHost, st));
 		VK_HIP(hipMemcpyAsync(raws.data(), c->d_wrd_raw, (size_t)cnt * 4, hipMemcpyDeviceToHost, st));
@@ -711,16 +665,12 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 			out->score[i] = empty ? -INFINITY : vals[(size_t)i];
 			out->sentence[i] = q->only_slices[i];
 			if (out->raw_score) out->raw_score[i] = empty ? -INFINITY : raws[(size_t)i];
-			if (out->mapping && out->edge_sim)
-				for (int j = 0; j < q->len_t; j++) {
-					out->mapping[i * (size_t)q->len_t + j] = -1;
-					out->edge_sim[i * (size_t)q->len_t + j] = 0.0f;
-				}
+			if (out->mapping && out->edge_sim) vk_host::no_flow(out->mapping + i * (size_t)q->len_t, out->edge_sim + i * (size_t)q->len_t, q->len_t);
 		}
 		out->n_out = cnt;
 		return VK_OK;
 	}
-	if (exact_transport) {
+	if (exact_transport(q)) {
 		// ---- stage 2: exact EMD on the candidates with the largest bounds, until the k-th best
 		// exact score is above every remaining bound (then no unsolved sentence can enter)
 		VK_HIP(hipEventRecord(c->ev[2], st));
@@ -748,37 +698,20 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		// solves the `count` candidates whose keys sit at d_keys, merges them into `best`; returns the smallest bound among them
 		auto solve = [&](const uint64_t *d_keys, int count, float *ub_min, int *n_cand_out) -> int {
 			w.keys = d_keys;
-			VK_HIP(vk_launch_wrd_exact(&w, count, c->d_scores, st));
-			if (c->max_len > VK_FAST_SENT_LEN) {   // candidates of 65 .. 512 tokens
-				if (w.nq > 1) {
-					int rc3 = c->d_wrdl_scratch.reserve((size_t)vk_wrd_long_blocks() * vk_wrd_long_scratch_bytes(), &c->device_bytes);
-					if (rc3) return rc3;
-				}
-				w.scratch = c->d_wrdl_scratch; w.scratch_stride = (int64_t)vk_wrd_long_scratch_bytes();
-				VK_HIP(vk_launch_wrd_exact_long(&w, count, st));
-			}
+			if (int rc3 = launch_wrd_exact_both(c, w, count, c->d_scores, c->max_len > VK_FAST_SENT_LEN, st)) return rc3;   // (long: candidates of 65 .. 512 tokens)
 			keys.resize((size_t)count); vals.resize((size_t)count); raws.resize((size_t)count);
 			VK_HIP(hipMemcpyAsync(keys.data(), d_keys, (size_t)count * 8, hipMemcpyDeviceToHost, st));
 			VK_HIP(hipMemcpyAsync(vals.data(), c->d_wrd_val, (size_t)count * 4, hipMemcpyDeviceToHost, st));
 			VK_HIP(hipMemcpyAsync(raws.data(), c->d_wrd_raw, (size_t)count * 4, hipMemcpyDeviceToHost, st));
 			VK_HIP(hipStreamSynchronize(st));
-			int n_cand = 0;
+			const int n_cand = vk_host::count_keys(keys.data(), count);
 			float ub = INFINITY;
-			for (int i = 0; i < count; i++) {
-				if (keys[(size_t)i] == 0) break;
-				n_cand++;
-				const uint32_t ob = (uint32_t)(keys[(size_t)i] >> 32);
-				const uint32_t bits = (ob & 0x80000000u) ? (ob & 0x7fffffffu) : ~ob;
-				float u;
-				memcpy(&u, &bits, 4);
-				ub = std::min(ub, u);
+			for (int i = 0; i < n_cand; i++) {
+				ub = std::min(ub, vk_host::key_score(keys[(size_t)i]));
 				if (vals[(size_t)i] > q->min_score)
-					best.push_back({vals[(size_t)i], raws[(size_t)i], (int64_t)(uint32_t)(keys[(size_t)i] & 0xffffffffu)});
+					best.push_back({vals[(size_t)i], raws[(size_t)i], (int64_t)vk_host::key_row(keys[(size_t)i])});
 			}
-			const auto better = [](const Cand &a, const Cand &b) {
-				if (a.val != b.val) return a.val > b.val;
-				return a.g > b.g;
-			};
+			const auto better = [](const Cand &a, const Cand &b) { return vk_host::ranks_before(a.val, a.g, b.val, b.g); };
 			if ((int)best.size() > k) {
 				std::partial_sort(best.begin(), best.begin() + k, best.end(), better);
 				best.resize((size_t)k);
@@ -788,16 +721,11 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 			return VK_OK;
 		};
 		{
-			int nb = 0, cur = 0;
-			VK_HIP(vk_launch_topk_scores(c->d_scores, n, q->min_score, M, c->d_keys[0], &nb, st));
-			while (nb > 1) {
-				const int64_t nkeys = (int64_t)nb * M;
-				VK_HIP(vk_launch_topk_keys(c->d_keys[cur], nkeys, M, c->d_keys[1 - cur], &nb, st));
-				cur = 1 - cur;
-			}
+			const uint64_t *d_first = nullptr;
+			if ((rc = select_blocks(c, q->min_score, M, st, &d_first))) return rc;
 			float ub_last = INFINITY;
 			int n_cand = 0;
-			if ((rc = solve(c->d_keys[cur], M, &ub_last, &n_cand))) return rc;
+			if ((rc = solve(d_first, M, &ub_last, &n_cand))) return rc;
 			bool done = n_cand < M || ((int)best.size() == k && best.back().val > ub_last);
 			while (!done) {
 				const float theta = (int)best.size() == k ? best.back().val : -INFINITY;
@@ -824,21 +752,10 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 			out->score[i] = best[i].val;
 			out->sentence[i] = sentence_of(best[i].g);
 			if (out->raw_score) out->raw_score[i] = best[i].raw;
-			if (q->want_flow && out->mapping && out->edge_sim)
-				for (int j = 0; j < q->len_t; j++) {
-					out->mapping[i * (size_t)q->len_t + j] = -1;
-					out->edge_sim[i * (size_t)q->len_t + j] = 0.0f;
-				}
+			if (q->want_flow && out->mapping && out->edge_sim) vk_host::no_flow(out->mapping + i * (size_t)q->len_t, out->edge_sim + i * (size_t)q->len_t, q->len_t);
 		}
 		out->n_out = (int)best.size();
-		float ms = 0;
-		vk_timings t{};
-		if (hipEventElapsedTime(&ms, c->ev[0], c->ev[5]) == hipSuccess) t.prepare_ms = ms;
-		if (hipEventElapsedTime(&ms, c->ev[5], c->ev[1]) == hipSuccess) t.queue_ms = ms;
-		if (hipEventElapsedTime(&ms, c->ev[1], c->ev[2]) == hipSuccess) t.score_ms = ms;
-		if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) t.topk_ms = ms;
-		if (hipEventElapsedTime(&ms, c->ev[0], c->ev[4]) == hipSuccess) t.total_ms = ms - t.queue_ms;
-		c->last = t;
+		state_timings(c, false);
 		return VK_OK;
 	}
 
@@ -874,11 +791,11 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 			return VK_OK;
 		}
 		VkFlowParams f{};
-		f.tiles = c->d_tiles; f.tok_id = c->d_tok_id; f.table = c->d_table; f.sent_start = c->d_sent_start; f.sent_end = c->d_sent_end;
-		f.layout = p.layout; f.nk32 = c->nk32; f.tail = c->tail; f.tile_bytes = c->tile_bytes; f.prec = c->prec;
+		corpus_fields_ids(f, c);
+		f.table = c->d_table;
 		f.qtile = c->d_qtile; f.len_t = q->len_t; f.locality = q->locality; f.gap_mode = (p.gap_mode == 3 || p.gap_mode == 6) ? 2 : p.gap_mode;
 		f.max_len = c->max_len;
-		f.gs = p.gs; f.gt = p.gt; f.a_s = p.a_s; f.a_t = p.a_t; f.open_s = p.open_s; f.open_t = p.open_t;
+		gap_fields(f, p);
 		f.ws = c->d_ws; f.wt = c->d_wt;
 		f.pos_s = p.pos_s; f.tw_keep = p.tw_keep; f.tw_threshold = p.tw_threshold;
 		memcpy(f.tw, p.tw, sizeof f.tw);
@@ -904,37 +821,21 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		std::vector<float> &raws = keep.vec<float>((size_t)M), &sims = keep.vec<float>((size_t)M * ostride);
 		std::vector<int16_t> &maps = keep.vec<int16_t>((size_t)M * ostride);
 		for (;;) {
-			int nb = 0, cur = 0;
-			VK_HIP(vk_launch_topk_scores(c->d_scores, n, q->min_score, M, c->d_keys[0], &nb, st));
-			while (nb > 1) {
-				const int64_t nkeys = (int64_t)nb * M;
-				VK_HIP(vk_launch_topk_keys(c->d_keys[cur], nkeys, M, c->d_keys[1 - cur], &nb, st));
-				cur = 1 - cur;
-			}
-			if ((rc = launch_flow(c->d_keys[cur], M))) return rc;
-			VK_HIP(vk_launch_mark(c->d_keys[cur], M, c->d_scores, st));
-			VK_HIP(hipMemcpyAsync(keys.data(), c->d_keys[cur], (size_t)M * 8, hipMemcpyDeviceToHost, st));
+			const uint64_t *d_cand = nullptr;
+			if ((rc = select_blocks(c, q->min_score, M, st, &d_cand))) return rc;
+			if ((rc = launch_flow(d_cand, M))) return rc;
+			VK_HIP(vk_launch_mark(d_cand, M, c->d_scores, st));
+			VK_HIP(hipMemcpyAsync(keys.data(), d_cand, (size_t)M * 8, hipMemcpyDeviceToHost, st));
 			VK_HIP(hipMemcpyAsync(raws.data(), c->d_out_raw, (size_t)M * 4, hipMemcpyDeviceToHost, st));
 			VK_HIP(hipMemcpyAsync(maps.data(), c->d_out_map, maps.size() * 2, hipMemcpyDeviceToHost, st));
 			VK_HIP(hipMemcpyAsync(sims.data(), c->d_out_sim, sims.size() * 4, hipMemcpyDeviceToHost, st));
 			VK_HIP(hipStreamSynchronize(st));
-			int n_cand = 0;
+			const int n_cand = vk_host::count_keys(keys.data(), M);
 			float ub_last = INFINITY;
-			for (int i = 0; i < M; i++) {
-				if (keys[(size_t)i] == 0) break;
-				n_cand++;
-				const uint32_t ob = (uint32_t)(keys[(size_t)i] >> 32);
-				const uint32_t bits = (ob & 0x80000000u) ? (ob & 0x7fffffffu) : ~ob;
-				memcpy(&ub_last, &bits, 4);
-				const int64_t row = (int64_t)(uint32_t)(keys[(size_t)i] & 0xffffffffu);
-				// reference_score (metric/alignment.h:84-106) with the matched weight of this traceback, in float as upstream
-				float matched = 0.0f;
-				for (int j = 0; j < q->len_t; j++)
-					if (maps[(size_t)i * ostride + j] >= 0) matched += (q->tag_weights && is_align) ? q->tag_weights[j] : 1.0f;
-				const float uw = powf((total - matched) / total, wsub);
-				const float ref = matched + uw * (total - matched);
-				const float boost = q->boost ? q->boost[sentence_of(row)] : 1.0f;
-				const float val = (raws[(size_t)i] / ref) * boost;
+			for (int i = 0; i < n_cand; i++) {
+				ub_last = vk_host::key_score(keys[(size_t)i]);
+				const int64_t row = (int64_t)vk_host::key_row(keys[(size_t)i]);
+				const float val = vk_host::reference_score(raws[(size_t)i], &maps[(size_t)i * ostride], q->len_t, q->tag_weights, total, wsub, q->boost ? q->boost[sentence_of(row)] : 1.0f);
 				if (val > q->min_score) {
 					Cand cd{val, raws[(size_t)i], row, {}, {}};
 					cd.map.assign(maps.begin() + (size_t)i * ostride, maps.begin() + (size_t)i * ostride + q->len_t);
@@ -942,10 +843,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 					best.push_back(std::move(cd));
 				}
 			}
-			std::sort(best.begin(), best.end(), [](const Cand &a, const Cand &b) {
-				if (a.val != b.val) return a.val > b.val;
-				return a.row > b.row;
-			});
+			std::sort(best.begin(), best.end(), [](const Cand &a, const Cand &b) { return vk_host::ranks_before(a.val, a.row, b.val, b.row); });
 			if ((int)best.size() > k) best.resize((size_t)k);
 			if (n_cand < M) break;
 			if ((int)best.size() == k && best.back().val > ub_last) break;
@@ -970,14 +868,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 			float no_mass[VK_MAX_QUERY_LEN] = {0};
 			if ((rc = transport_flows(rows_idx, false, no_mass, 0, 0))) return rc;
 		}
-		float ms = 0;
-		vk_timings t{};
-		if (hipEventElapsedTime(&ms, c->ev[0], c->ev[5]) == hipSuccess) t.prepare_ms = ms;
-		if (hipEventElapsedTime(&ms, c->ev[5], c->ev[1]) == hipSuccess) t.queue_ms = ms;
-		if (hipEventElapsedTime(&ms, c->ev[1], c->ev[2]) == hipSuccess) t.score_ms = ms;
-		if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) t.topk_ms = ms;
-		if (hipEventElapsedTime(&ms, c->ev[0], c->ev[4]) == hipSuccess) t.total_ms = ms - t.queue_ms;
-		c->last = t;
+		state_timings(c, false);
 		return VK_OK;
 	}
 
@@ -1004,20 +895,13 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	if ((rc = c->d_out_sim.reserve((size_t)kk * 64, &c->device_bytes))) return rc;
 	if ((rc = c->d_out_map.reserve((size_t)kk * 64, &c->device_bytes))) return rc;
 	const float sel_floor = (do_flow || canon_tr) ? q->min_score - 1e-5f * std::max(1.0f, std::fabs(q->min_score)) : q->min_score;
-	int cur = 0;
 	if (only) {
 		// keys of the listed slices, in the caller's order (rows of the slice table: long slices sit in padded groups)
-		if (!c->entry_sent.empty() && c->sent_entry.empty()) {
-			c->sent_entry.assign((size_t)c->desc.n_sentences, -1);
-			for (int64_t e = 0; e < n; e++) if (c->entry_sent[(size_t)e] >= 0) c->sent_entry[(size_t)c->entry_sent[(size_t)e]] = (int32_t)e;
-		}
 		std::vector<uint64_t> &hk = keep.vec<uint64_t>((size_t)q->n_only);
-		for (int i = 0; i < q->n_only; i++) {
-			const int64_t row = c->sent_entry.empty() ? q->only_slices[i] : (int64_t)c->sent_entry[(size_t)q->only_slices[i]];
-			hk[(size_t)i] = (1ull << 32) | (uint64_t)(uint32_t)row;
-		}
+		for (int i = 0; i < q->n_only; i++) hk[(size_t)i] = vk_host::key_of_row(row_of_sentence(c, q->only_slices[i]));
 		VK_HIP(hipMemcpyAsync(c->d_keys[0], hk.data(), hk.size() * 8, hipMemcpyHostToDevice, st));
 		VK_HIP(hipStreamSynchronize(st));   // `hk` leaves scope
+		d_sel = c->d_keys[0];
 	} else if (kk > VK_MAX_MATCHES) {
 		// more matches than the block selection keeps per 2,048 keys: the keys of all n rows, sorted
 		if ((rc = c->d_sort[0].reserve((size_t)n + 64, &c->device_bytes))) return rc;
@@ -1028,28 +912,9 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		if ((rc = c->d_sort_temp.reserve(temp_bytes, &c->device_bytes))) return rc;
 		VK_HIP(vk_launch_sort_all(c->d_scores, n, sel_floor, c->d_sort[0], c->d_sort[1], c->d_sort_temp, &temp_bytes, &sorted, st));
 		d_sel = sorted;
-	} else if (kk <= 64) {
-		// wave-streaming selection: n -> ceil(n/4096) * k keys -> ... -> k keys
-		int64_t nw = 0;
-		VK_HIP(vk_launch_topk_wave(c->d_scores, nullptr, n, sel_floor, kk, 4096, c->d_keys[0], &nw, st));
-		while (nw > 1) {
-			const int64_t nkeys = nw * kk;
-			const int64_t per_wave = nkeys <= 16384 ? nkeys : 4096;
-			VK_HIP(vk_launch_topk_wave(nullptr, c->d_keys[cur], nkeys, 0.0f, kk, per_wave, c->d_keys[1 - cur], &nw, st));
-			cur = 1 - cur;
-		}
-	} else {
-		int nb = 0;
-		VK_HIP(vk_launch_topk_scores(c->d_scores, n, sel_floor, kk, c->d_keys[0], &nb, st));
-		while (nb > 1) {
-			const int64_t nkeys = (int64_t)nb * kk;
-			VK_HIP(vk_launch_topk_keys(c->d_keys[cur], nkeys, kk, c->d_keys[1 - cur], &nb, st));
-			cur = 1 - cur;
-		}
-	}
+	} else if ((rc = kk <= 64 ? select_waves(c, sel_floor, kk, st, &d_sel) : select_blocks(c, sel_floor, kk, st, &d_sel))) return rc;
 
 	// ---- flow of the winners ------------------------------------------------
-	if (!d_sel) d_sel = c->d_keys[cur];
 	VK_HIP(hipEventRecord(c->ev[3], st));
 	if (do_flow && (rc = launch_flow(d_sel, kk))) return rc;
 	VK_HIP(hipEventRecord(c->ev[4], st));
@@ -1066,43 +931,26 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	}
 	VK_HIP(hipStreamSynchronize(st));
 
-	int n_sel = 0;
-	for (int i = 0; i < kk; i++) {
-		if (keys[(size_t)i] == 0) break;
-		n_sel++;
-	}
+	const int n_sel = vk_host::count_keys(keys.data(), kk);
 	// order[i]: position among the selected slices of the i-th result
 	std::vector<int> order((size_t)n_sel);
 	std::vector<float> val((size_t)std::max(n_sel, 1));
 	for (int i = 0; i < n_sel; i++) {
 		order[(size_t)i] = i;
-		const uint32_t ob = (uint32_t)(keys[(size_t)i] >> 32);
-		const uint32_t bits = (ob & 0x80000000u) ? (ob & 0x7fffffffu) : ~ob;
-		memcpy(&val[(size_t)i], &bits, 4);
+		val[(size_t)i] = vk_host::key_score(keys[(size_t)i]);
 	}
+	const auto row_at = [&](int i) { return (int64_t)vk_host::key_row(keys[(size_t)i]); };
+	const auto rank_restated = [&]() {   // the k best of the restated scores, in the order of a result set (listed slices keep the caller's order)
+		if (!only) vk_host::rank_above(order, q->min_score, [&](int i) { return val[(size_t)i]; }, row_at);
+		return std::min((int)order.size(), only ? q->n_only : k);
+	};
 	int n_out = n_sel;
 	if (do_flow) {
-		// Score of a winner from its canonical aligner score (match/match.h:295-307, reference_score metric/alignment.h:84-106),
-		// operation by operation as the oracle's vko_score: matched weight of this traceback, pow(., submatch_weight = 0) = 1
-		const float total = p.ref_total;
-		for (int i = 0; i < n_sel; i++) {
-			float matched = 0.0f;
-			for (int j = 0; j < q->len_t; j++)
-				if (map[(size_t)i * ostride + j] >= 0) matched += q->tag_weights ? q->tag_weights[j] : 1.0f;
-			const float uw = powf((total - matched) / total, only ? q->submatch_weight : 0.0f);   // (searches with a submatch weight take the candidate rounds above)
-			const float ref = matched + uw * (total - matched);
-			const int64_t row = (int64_t)(uint32_t)(keys[(size_t)i] & 0xffffffffu);
-			const float boost = q->boost ? q->boost[sentence_of(row)] : 1.0f;
-			val[(size_t)i] = (raw[(size_t)i] / ref) * boost;
-		}
-		if (!only) {
-			order.erase(std::remove_if(order.begin(), order.end(), [&](int i) { return !(val[(size_t)i] > q->min_score); }), order.end());
-			std::sort(order.begin(), order.end(), [&](int a, int b) {   // the total order of the result set: score, then slice, descending
-				if (val[(size_t)a] != val[(size_t)b]) return val[(size_t)a] > val[(size_t)b];
-				return (uint32_t)(keys[(size_t)a] & 0xffffffffu) > (uint32_t)(keys[(size_t)b] & 0xffffffffu);
-			});
-		}
-		n_out = std::min((int)order.size(), only ? q->n_only : k);
+		// the winners' scores from their canonical aligner scores (searches with a submatch weight take the candidate rounds above)
+		for (int i = 0; i < n_sel; i++)
+			val[(size_t)i] = vk_host::reference_score(raw[(size_t)i], &map[(size_t)i * ostride], q->len_t, q->tag_weights, p.ref_total,
+				only ? q->submatch_weight : 0.0f, q->boost ? q->boost[sentence_of(row_at(i))] : 1.0f);
+		n_out = rank_restated();
 	}
 	// canon_tr: similarity rows of every selected slice -- in the handle's pinned staging (a std::vector made the copy of a document
 	// corpus's winners, 12 MB for 18 x 5,056 rows x 32 columns, go through the runtime's bounce buffers: 2 - 4 ms of a 5.7 ms query)
@@ -1113,7 +961,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		if ((rc = c->h_brows.reserve(rows_bytes / 4, nullptr))) return rc;
 		rows_all = c->h_brows;
 		std::vector<int64_t> rows_idx;
-		for (int i = 0; i < n_sel; i++) rows_idx.push_back((int64_t)(uint32_t)(keys[(size_t)i] & 0xffffffffu));
+		for (int i = 0; i < n_sel; i++) rows_idx.push_back(row_at(i));
 		float no_mass[VK_MAX_QUERY_LEN] = {0};
 		if ((rc = transport_flows(rows_idx, false, no_mass, 0, 0, rows_all))) return rc;
 		// vocabulary keys (static layout): token ids, or (id, tag) pairs when the similarity is tag-weighted (alignment/bow.h:106-127, 150-176)
@@ -1144,14 +992,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 				vocab ? key_s.data() : nullptr, vocab ? key_t.data() : nullptr, q->rwmd_injective != 0, q->rwmd_symmetric != 0, q->rwmd_normalize_bow != 0);
 			val[(size_t)i] = (raw[(size_t)i] / total) * boost;   // reference_score with every query token matched: the sum of the weights (match.h:165-176)
 		}
-		if (!only) {
-			order.erase(std::remove_if(order.begin(), order.end(), [&](int i) { return !(val[(size_t)i] > q->min_score); }), order.end());
-			std::sort(order.begin(), order.end(), [&](int a, int b) {
-				if (val[(size_t)a] != val[(size_t)b]) return val[(size_t)a] > val[(size_t)b];
-				return (uint32_t)(keys[(size_t)a] & 0xffffffffu) > (uint32_t)(keys[(size_t)b] & 0xffffffffu);
-			});
-		}
-		n_out = std::min((int)order.size(), only ? q->n_only : k);
+		n_out = rank_restated();
 	}
 	std::vector<float> &raw_sel = keep.vec<float>((size_t)std::max(n_out, 1));
 	if (!do_flow && !(canon_tr && n_sel > 0) && out->raw_score && n_out > 0) {
@@ -1160,19 +1001,17 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 			std::vector<float> &all_raw = keep.vec<float>((size_t)n);
 			VK_HIP(hipMemcpyAsync(all_raw.data(), c->d_raw, (size_t)n * 4, hipMemcpyDeviceToHost, st));
 			VK_HIP(hipStreamSynchronize(st));
-			for (int i = 0; i < n_out; i++) raw_sel[(size_t)i] = all_raw[(size_t)(uint32_t)(keys[(size_t)i] & 0xffffffffu)];
+			for (int i = 0; i < n_out; i++) raw_sel[(size_t)i] = all_raw[(size_t)row_at(i)];
 		} else for (int i = 0; i < n_out; i++) {
-			const int64_t g = (int64_t)(uint32_t)(keys[(size_t)i] & 0xffffffffu);
-			if (!span_skip_raw) VK_HIP(hipMemcpyAsync(&raw_sel[(size_t)i], c->d_raw + g, 4, hipMemcpyDeviceToHost, st));
+			if (!span_skip_raw) VK_HIP(hipMemcpyAsync(&raw_sel[(size_t)i], c->d_raw + row_at(i), 4, hipMemcpyDeviceToHost, st));
 		}
 		VK_HIP(hipStreamSynchronize(st));
 	}
 	for (int i = 0; i < n_out; i++) {
 		const int src = order[(size_t)i];
-		const uint64_t key = keys[(size_t)src];
 		const float s = val[(size_t)src];
 		out->score[i] = s;
-		out->sentence[i] = sentence_of((int64_t)(uint32_t)(key & 0xffffffffu));
+		out->sentence[i] = sentence_of(row_at(src));
 		if (out->raw_score) out->raw_score[i] = (do_flow || canon_tr) ? raw[(size_t)src] : span_skip_raw ? s : raw_sel[(size_t)i];
 		if (do_flow) {
 			for (int j = 0; j < q->len_t; j++) {
@@ -1180,11 +1019,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 				out->edge_sim[(size_t)i * q->len_t + j] = sim[(size_t)src * ostride + j];
 			}
 		} else if (q->want_flow && out->mapping && out->edge_sim) {
-			// transport flows of the winners (SparseFlow / DenseFlow) are not produced yet
-			for (int j = 0; j < q->len_t; j++) {
-				out->mapping[(size_t)i * q->len_t + j] = -1;
-				out->edge_sim[(size_t)i * q->len_t + j] = 0.0f;
-			}
+			vk_host::no_flow(out->mapping + (size_t)i * q->len_t, out->edge_sim + (size_t)i * q->len_t, q->len_t);
 		}
 	}
 	out->n_out = n_out;
@@ -1194,20 +1029,12 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 			memcpy(out->sim_rows + (size_t)i * rows_R * rows_W, rows_all + (size_t)order[(size_t)i] * rows_R * rows_W, (size_t)rows_R * rows_W * 4);
 	} else if ((q->algorithm == VK_ALG_RWMD || (is_align && rows_on_request)) && n_out > 0) {
 		std::vector<int64_t> rows_idx;
-		for (int i = 0; i < n_out; i++) rows_idx.push_back((int64_t)(uint32_t)(keys[(size_t)order[(size_t)i]] & 0xffffffffu));
+		for (int i = 0; i < n_out; i++) rows_idx.push_back(row_at(order[(size_t)i]));
 		float no_mass[VK_MAX_QUERY_LEN] = {0};
 		if ((rc = transport_flows(rows_idx, false, no_mass, 0, 0))) return rc;
 	}
 
-	float ms = 0;
-	vk_timings t{};
-	if (hipEventElapsedTime(&ms, c->ev[0], c->ev[5]) == hipSuccess) t.prepare_ms = ms;
-	if (hipEventElapsedTime(&ms, c->ev[5], c->ev[1]) == hipSuccess) t.queue_ms = ms;
-	if (hipEventElapsedTime(&ms, c->ev[1], c->ev[2]) == hipSuccess) t.score_ms = ms;
-	if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) t.topk_ms = ms;
-	if (hipEventElapsedTime(&ms, c->ev[3], c->ev[4]) == hipSuccess) t.flow_ms = ms;
-	if (hipEventElapsedTime(&ms, c->ev[0], c->ev[4]) == hipSuccess) t.total_ms = ms - t.queue_ms;
-	c->last = t;
+	state_timings(c, true);
 	return VK_OK;
 }
 
@@ -1232,10 +1059,7 @@ int vk_merge_topk(const vk_topk_out *sets, int32_t n_sets, int32_t len_t, int32_
 	// as -inf; the kernels never produce one, degenerate vectors score 0)
 	for (int s = 0; s < n_sets; s++)
 		for (int i = 0; i < sets[s].n_out; i++) all.push_back({sets[s].score[i] == sets[s].score[i] ? sets[s].score[i] : -INFINITY, sets[s].sentence[i], s, i});
-	std::sort(all.begin(), all.end(), [](const Ref &a, const Ref &b) {
-		if (a.score != b.score) return a.score > b.score;
-		return a.sent > b.sent;
-	});
+	std::sort(all.begin(), all.end(), [](const Ref &a, const Ref &b) { return vk_host::ranks_before(a.score, a.sent, b.score, b.sent); });
 	const int n_out = (int)std::min<size_t>(all.size(), (size_t)max_matches);
 	for (int i = 0; i < n_out; i++) {
 		const Ref &r = all[(size_t)i];
@@ -1307,10 +1131,7 @@ int vk_merge_records(const int32_t *records, int32_t n_sets, int32_t len_t, int3
 		all.push_back(e);
 	}
 	// the order of vk_merge_topk (and of the selection on one GPU): score descending, ties by slice index descending
-	std::sort(all.begin(), all.end(), [](const Ref &a, const Ref &b) {
-		if (a.score != b.score) return a.score > b.score;
-		return a.sent > b.sent;
-	});
+	std::sort(all.begin(), all.end(), [](const Ref &a, const Ref &b) { return vk_host::ranks_before(a.score, a.sent, b.score, b.sent); });
 	const int n_out = (int)std::min<size_t>(all.size(), (size_t)k);
 	for (int i = 0; i < n_out; i++) {
 		const int32_t *r = all[(size_t)i].rec;

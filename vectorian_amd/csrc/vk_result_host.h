@@ -1,0 +1,118 @@
+// vk_result_host.h -- from "the selected keys and their tracebacks" to a result set: the host-side rules every query path shares
+// (vk_query.cpp, vk_batch.cpp, vk_longq_host.cpp).  One definition each of the selection keys' encoding, the order of a result set,
+// the score of a winner restated from its traceback, and the forms of the gap costs the kernels are launched with.
+// Host only, no HIP types: tests/test_result_host.py compiles it with g++ and holds each rule against its statement in numpy (CPU tier).
+#ifndef VK_RESULT_HOST_H
+#define VK_RESULT_HOST_H
+
+#include "../../include/vectorian_hip.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+namespace vk_host {
+
+// ---- selection keys: (orderable(score) << 32) | row of the slice table; 0 = empty slot.  Keys compare as unsigned 64-bit numbers in
+// the order of a result set (score, then row).  The encoder is float_orderable, vk_select.hip:17 (and vk_doc.hip:36): a set sign bit
+// flips every bit, a clear one sets the sign bit.  key_score inverts it bit for bit.
+inline float key_score(uint64_t key) {
+	const uint32_t ob = (uint32_t)(key >> 32);
+	const uint32_t bits = (ob & 0x80000000u) ? (ob & 0x7fffffffu) : ~ob;
+	float s;
+	memcpy(&s, &bits, 4);
+	return s;
+}
+inline uint32_t key_row(uint64_t key) { return (uint32_t)(key & 0xffffffffu); }
+// the key that names a listed row to the traceback / rows / solver kernels (they read the row only; any non-zero score field)
+inline uint64_t key_of_row(int64_t row) { return (1ull << 32) | (uint64_t)(uint32_t)row; }
+// the selected keys of `cap` slots: up to the first empty one
+inline int count_keys(const uint64_t *keys, int cap) {
+	int n = 0;
+	while (n < cap && keys[n] != 0) n++;
+	return n;
+}
+
+// ---- the total order of a result set: score descending, ties by slice index descending (match/match_impl.h:8-42); admission is
+// score > min_score (metric/alignment.h:284), so a score equal to min_score is out.  Scores must not be NaN (a strict weak order):
+// the merges of records from other ranks map NaN to -inf before they come here.
+inline bool ranks_before(float score_a, int64_t slice_a, float score_b, int64_t slice_b) {
+	if (score_a != score_b) return score_a > score_b;
+	return slice_a > slice_b;
+}
+// `order` holds positions i with score(i) and slice(i): drops those not above min_score, sorts the rest into the order above
+template <typename Score, typename Slice> void rank_above(std::vector<int> &order, float min_score, Score score, Slice slice) {
+	order.erase(std::remove_if(order.begin(), order.end(), [&](int i) { return !(score(i) > min_score); }), order.end());
+	std::sort(order.begin(), order.end(), [&](int a, int b) { return ranks_before(score(a), (int64_t)slice(a), score(b), (int64_t)slice(b)); });
+}
+
+// ---- the score of a winner from its canonical aligner score `raw` and its traceback (match/match.h:295-307; reference_score,
+// metric/alignment.h:84-106), operation by operation in float as the oracle's vko_score: the matched weight of THIS traceback (query
+// token j counts tag_weights[j], or 1 without tag weights; total is their sum over the query), pow((total - matched) / total, w),
+// ref = matched + that * (total - matched), (raw / ref) * boost.  map_row: the winner's mapping, -1 = unmatched.
+// (A copy that added `matched += cond ? 1.0f : 0.0f` gave the same floats: x + 0.0f == x for the sums of non-negative terms here.)
+inline float reference_score(float raw, const int16_t *map_row, int len_t, const float *tag_weights, float total, float submatch_weight, float boost) {
+	float matched = 0.0f;
+	for (int j = 0; j < len_t; j++)
+		if (map_row[j] >= 0) matched += tag_weights ? tag_weights[j] : 1.0f;
+	const float uw = powf((total - matched) / total, submatch_weight);
+	const float ref = matched + uw * (total - matched);
+	return (raw / ref) * boost;
+}
+
+// a winner without a stated flow (transports: SparseFlow / DenseFlow are stated from the similarity rows, not here)
+inline void no_flow(int16_t *map_row, float *sim_row, int len_t) {
+	for (int j = 0; j < len_t; j++) {
+		map_row[j] = -1;
+		sim_row[j] = 0.0f;
+	}
+}
+
+// ---- gap costs
+inline float gap_cost(const vk_gap &g, int k) {
+	if (k <= 0) return 0.0f;
+	switch (g.kind) {
+	case VK_GAP_LINEAR: return g.u * (float)k;
+	case VK_GAP_AFFINE: return g.u + g.v * (float)k;
+	default: return (g.table && k < g.n_table) ? g.table[k] : INFINITY;
+	}
+}
+
+// The form of the recurrence a pair of gap costs is aligned with: 0 both linear (gs, gt per token); 1 linear / affine (a_* to open,
+// g* per token, open_* their sum; a linear side opens at 0); 2 a table on either side (every field 0: the kernels read the tables).
+// The callers copy the fields into their parameter struct.
+struct gap_form { int gap_mode = 2; float gs = 0.0f, gt = 0.0f, a_s = 0.0f, a_t = 0.0f, open_s = 0.0f, open_t = 0.0f; };
+inline gap_form classify_gaps(const vk_gap &s, const vk_gap &t) {
+	gap_form f;
+	if (s.kind == VK_GAP_LINEAR && t.kind == VK_GAP_LINEAR) {
+		f.gap_mode = 0;
+		f.gs = s.u; f.gt = t.u;
+	} else if ((s.kind == VK_GAP_LINEAR || s.kind == VK_GAP_AFFINE) && (t.kind == VK_GAP_LINEAR || t.kind == VK_GAP_AFFINE)) {
+		f.gap_mode = 1;
+		f.a_s = s.kind == VK_GAP_AFFINE ? s.u : 0.0f;
+		f.gs = s.kind == VK_GAP_AFFINE ? s.v : s.u;
+		f.a_t = t.kind == VK_GAP_AFFINE ? t.u : 0.0f;
+		f.gt = t.kind == VK_GAP_AFFINE ? t.v : t.u;
+		f.open_s = f.a_s + f.gs;
+		f.open_t = f.a_t + f.gt;
+	}
+	return f;
+}
+
+// wt[0..79]: w_t as given, up to the query's length (0 beyond it, and throughout when the query is no alignment); wt[80..159]: its
+// subadditive closure w*[k] = min(w[k], min over a of w*[a] + w*[k - a]).  The register-history kernels take their in-row candidates
+// from the row's values before in-row gaps, which is the sequential recurrence with w_t replaced by w* (dp_general_reg in
+// vk_common.hip.h).  (Round 1 sent every table that was not strictly subadditive -- a linear cost handed over as a table, a convex
+// one -- to the LDS-history kernel with its serial in-row chain: 12.7 ms per 1 M x 32 tokens against 2.9 ms.)
+inline void wt_with_closure(float *wt, const vk_gap &gap_t, int len_t, bool is_align) {
+	for (int i = 0; i < 80; i++) wt[i] = (is_align && i <= len_t) ? gap_cost(gap_t, i) : 0.0f;
+	for (int k = 0; k < 80; k++) wt[80 + k] = wt[k];
+	for (int k = 2; k <= len_t && k < 80; k++)
+		for (int a = 1; a < k; a++) wt[80 + k] = std::min(wt[80 + k], wt[80 + a] + wt[80 + k - a]);
+}
+
+} // namespace vk_host
+
+#endif
