@@ -201,8 +201,8 @@ typedef struct {
  * recorded on the handle's stream */
 typedef struct {
 	float prepare_ms;   /* query upload + static table (if any) */
-	float score_ms;     /* the fused similarity + DP kernel (dominant) */
-	float topk_ms;      /* bounded result set selection */
+	float score_ms;     /* the fused similarity + DP kernel (dominant); a pruned query (8-bit bound pass): the bound pass */
+	float topk_ms;      /* bounded result set selection; a pruned query: the contenders' exact scores as well */
 	float flow_ms;      /* traceback of the winners */
 	float total_ms;     /* first to last event, without queue_ms: the device time this query took once it had its turn */
 	float queue_ms;     /* several handles on one corpus (vk_corpus_view): time this query's scoring kernel waited on the

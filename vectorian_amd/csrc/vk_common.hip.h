@@ -43,6 +43,8 @@
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
 typedef __attribute__((ext_vector_type(4))) short bf16x4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(4))) int i32x4;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 #define VK_NEG_INF (-__builtin_inff())
 #define VK_RUN 4   // consecutive groups of 4 slices per wave turn (vk_score_kernel); 1, 2 and 8 measured the same on aligned 32-token slices
@@ -186,6 +188,32 @@ __device__ __forceinline__ f32x4 sim_tile_qlds(const uint8_t *__restrict__ qlds,
 	}
 	acc[0] = clip01(acc[0]); acc[1] = clip01(acc[1]); acc[2] = clip01(acc[2]); acc[3] = clip01(acc[3]);
 	return acc;
+}
+
+// The 8-bit bound pass (MODE 7): a shadow tile is NK blocks of 1 KiB in the operand order of v_mfma_i32_16x16x64_i8 (K = 64 per
+// step, 16 bytes per lane like the bf16 blocks), then 16 x (s_x, e_x).  The integer product is exact (|I| <= 64 NK 127^2 < 2^24, so
+// its float is exact too); the cell is an upper bound of the exact kernel's clipped cosine:
+//   ub = clip01((s_x cs_j) I + e_x ca_j + cb_j),   cs / ca / cb: vk_host::bound_cell_constants, zero for columns past the query.
+// C/D layout as mfma_f32_16x16x32_bf16: lane l holds token l & 15, query columns 4 (l >> 4) + r.
+// The query's blocks and the constants behind them (cs[16], ca[16], cb[16]) are staged in LDS by the kernel, NK KiB + 192 bytes, and
+// read per K-step / per tile like MODE 3's: in registers they took the kernel with general gaps to 160 VGPRs, three waves per SIMD
+// then leave 32 and no neighbour kernel (the rounds, the peer's selection and traceback) finds room beside it; from LDS, and under the
+// budget of vk_score_m7.hip, 110 .. 122 by query width (the figures are there).
+template <int NK>
+__device__ __forceinline__ f32x4 sim_tile_i8(const uint8_t *__restrict__ qlds, const uint8_t *__restrict__ tile, int lane) {
+	i32x4 x[NK > 0 ? NK : 1];
+#pragma unroll
+	for (int t = 0; t < NK; t++) x[t] = __builtin_nontemporal_load(reinterpret_cast<const i32x4 *>(tile + t * 1024 + lane * 16));
+	const f32x2 m = __builtin_nontemporal_load(reinterpret_cast<const f32x2 *>(tile + NK * 1024 + (lane & 15) * 8));   // (s_x, e_x) of the lane's token
+	i32x4 acc = {0, 0, 0, 0};
+#pragma unroll
+	for (int t = 0; t < NK; t++) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(*reinterpret_cast<const i32x4 *>(qlds + t * 1024 + lane * 16), x[t], acc, 0, 0, 0);
+	const float *cst = reinterpret_cast<const float *>(qlds + NK * 1024) + (lane >> 4) * 4;
+	const f32x4 cs = *reinterpret_cast<const f32x4 *>(cst), ca = *reinterpret_cast<const f32x4 *>(cst + 16), cb = *reinterpret_cast<const f32x4 *>(cst + 32);
+	f32x4 ub;
+#pragma unroll
+	for (int r = 0; r < 4; r++) ub[r] = clip01(((m[0] * cs[r]) * (float)acc[r] + m[1] * ca[r]) + cb[r]);
+	return ub;
 }
 
 // fp32 unit rows (VK_PREC_F32, the reference's own precision), NB16 blocks of 16 features known at compile time: all the

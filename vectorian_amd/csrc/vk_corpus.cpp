@@ -429,6 +429,32 @@ int vk_corpus_set_slices(vk_corpus_t *c, const int64_t *start, const int64_t *en
 	return set_slices_impl(c, start, end, n_sentences, false);
 }
 
+// The 8-bit shadow of the token rows: contextual bf16 rows of 289 .. 304 features (d_pad = 304: the exact kernel's 300-d
+// specialisation rescores the contenders, the form every test and measurement runs),
+// every slice within VK_FAST_SENT_LEN tokens.  Never an error: without the memory (or with a row that is not finite) the corpus has
+// no shadow and its queries take the exact pass.
+static void build_shadow(vk_corpus *c) {
+	const int mode = bound_pass_mode();
+	if (mode < 0 || (mode == 0 && c->desc.n_sentences < kBoundPassMinSentences)) return;
+	if (c->desc.layout != VK_LAYOUT_CONTEXTUAL || c->prec != 0 || c->nk32 != 10 || c->tail != 1 || c->max_len > VK_FAST_SENT_LEN || c->n_entries < 1) return;
+	const int nk64 = 5, tile_bytes = nk64 * 1024 + 128;
+	const size_t bytes = (size_t)c->n_tiles * tile_bytes;
+	uint8_t *sh = nullptr;
+	if (c->d_counter.reserve(4, &c->device_bytes) || alloc_shared(c, &sh, bytes)) { (void)hipGetLastError(); return; }
+	uint32_t stats[4] = {0, 0, 1, 0};
+	const bool ran = vk_launch_shadow(c->d_tiles, c->n_tiles, c->rows_total, c->desc.d, c->tile_bytes, nk64, sh, c->d_counter, c->stream) == hipSuccess
+		&& hipMemcpyAsync(stats, c->d_counter, 16, hipMemcpyDeviceToHost, c->stream) == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;
+	if (!ran || stats[2] != 0) {
+		(void)hipGetLastError();
+		c->shared->release(sh);
+		c->device_bytes -= (int64_t)bytes;
+		return;
+	}
+	c->shadow = sh; c->shadow_nk64 = nk64; c->shadow_tile_bytes = tile_bytes;
+	memcpy(&c->shadow_n, &stats[0], 4);
+	memcpy(&c->shadow_x, &stats[1], 4);
+}
+
 int vk_corpus_finalize(vk_corpus_t *c) {
 	if (!c) return fail(VK_ERR_INVALID, "null argument");
 	if (c->rows_appended != c->rows_total) return fail(VK_ERR_STATE, "not all vectors were appended");
@@ -437,6 +463,7 @@ int vk_corpus_finalize(vk_corpus_t *c) {
 	VK_HIP(hipSetDevice(c->device));
 	c->d_stage.reset();
 	VK_HIP(hipStreamSynchronize(c->stream));
+	build_shadow(c);
 	c->finalized = true;
 	return VK_OK;
 }
@@ -548,6 +575,13 @@ int vk_last_scores(vk_corpus_t *c, float *scores, int64_t n) {
 	if (!c->have_scores) return fail(VK_ERR_STATE, "no query has run on this corpus");
 	if (n != c->desc.n_sentences) return fail(VK_ERR_INVALID, "n differs from n_sentences");
 	VK_HIP(hipSetDevice(c->device));
+	if (c->bp.pruned) {
+		// the last query scored its contenders only (bound pass): its exact pass over every slice now, once -- the query
+		// tile, the gap tables and the boost are still in their workspaces
+		VK_HIP(vk_launch_score(&c->bp.full, c->bp.full_grid, c->bp.full_smem, c->stream));
+		VK_HIP(hipStreamSynchronize(c->stream));
+		c->bp.pruned = false;
+	}
 	if (c->entry_sent.empty()) {
 		VK_HIP(hipMemcpy(scores, c->d_scores, (size_t)n * 4, hipMemcpyDeviceToHost));
 		return VK_OK;
@@ -556,6 +590,41 @@ int vk_last_scores(vk_corpus_t *c, float *scores, int64_t n) {
 	VK_HIP(hipMemcpy(rows.data(), c->d_scores, rows.size() * 4, hipMemcpyDeviceToHost));
 	for (int64_t e = 0; e < c->n_entries; e++)
 		if (c->entry_sent[(size_t)e] >= 0) scores[c->entry_sent[(size_t)e]] = rows[(size_t)e];
+	return VK_OK;
+}
+
+// Internal (tests; not part of the ABI): the bounds of the last query's bound pass per slice (null: none wanted; n = n_sentences) and
+// counters[7] -- the last query: bound pass ran, candidates of round 1 and of round 2, fell back to the full pass; since the handle
+// was made: queries with a bound pass, fallbacks, candidates of round 2.
+int vk_bound_pass_state(vk_corpus_t *c, float *bounds, int64_t n, int64_t *counters) {
+	if (!c || !counters) return fail(VK_ERR_INVALID, "null argument");
+	const int64_t v[7] = {c->bp.ran, c->bp.round1, c->bp.round2, c->bp.fell_back, c->bp.queries, c->bp.fallbacks, c->bp.survivors};
+	memcpy(counters, v, sizeof v);
+	if (!bounds) return VK_OK;
+	if (!c->bp.ran) return fail(VK_ERR_STATE, "the last query ran no bound pass");
+	if (n != c->desc.n_sentences) return fail(VK_ERR_INVALID, "n differs from n_sentences");
+	VK_HIP(hipSetDevice(c->device));
+	std::vector<float> rows((size_t)c->n_entries);
+	VK_HIP(hipMemcpy(rows.data(), c->d_ub, rows.size() * 4, hipMemcpyDeviceToHost));
+	for (int64_t e = 0; e < c->n_entries; e++) {
+		const int64_t sent = c->entry_sent.empty() ? e : (int64_t)c->entry_sent[(size_t)e];
+		if (sent >= 0) bounds[sent] = rows[(size_t)e];
+	}
+	return VK_OK;
+}
+
+// Internal (tests): one v_mfma_i32_16x16x64_i8 on 16 x 64 int8 query rows and 16 x 64 int8 token rows (host, row-major), packed as
+// the shadow packs its blocks: out[16 j + i] = q[j] . x[i]
+int vk_i8_tile_probe(const int8_t *q, const int8_t *x, int32_t *out) {
+	if (!q || !x || !out) return fail(VK_ERR_INVALID, "null argument");
+	vk_devbuf<uint8_t> buf;
+	if (int rc = buf.reserve(4096, nullptr)) return rc;
+	uint8_t *d = buf;
+	VK_HIP(hipMemcpy(d, q, 1024, hipMemcpyHostToDevice));
+	VK_HIP(hipMemcpy(d + 1024, x, 1024, hipMemcpyHostToDevice));
+	VK_HIP(vk_launch_i8_probe((const int8_t *)d, (const int8_t *)d + 1024, (int32_t *)(d + 2048), nullptr));
+	VK_HIP(hipDeviceSynchronize());
+	VK_HIP(hipMemcpy(out, d + 2048, 1024, hipMemcpyDeviceToHost));
 	return VK_OK;
 }
 

@@ -18,6 +18,8 @@
 #define VK_DEV_MAX_LONG_LEN 512       // longer slices: one per wave, second launch
 #define VK_DEV_MAX_QUERY_LEN 16        // fused kernels: one 16-column block
 #define VK_DEV_MAX_WIDE_QUERY_LEN 64   // vk_wide_kernel: lane = query column
+#define VK_DEV_BOUND_CONST_BYTES 256   // MODE 7: LDS behind the 8-bit query tile for the cells' constants (3 x 16 floats, padded);
+                                       // the kernel steps over it and the host sizes the launch by it
 
 struct VkScoreParams {
 	// corpus
@@ -31,6 +33,8 @@ struct VkScoreParams {
 	int32_t nk32, tail, tile_bytes;
 	int32_t prec;              // 0: bf16 tiles (nk32 K-steps of 32); 1: fp32 tiles (nk32 blocks of 16 features)
 	int32_t q_lds;             // MODE 1: bytes of the query tile staged at the start of the dynamic LDS (0: read through L1 / L2)
+	int32_t bound_i8;          // 1: `tiles` is the 8-bit shadow (nk32 K-steps of 64 int8, tile_bytes = nk32 KiB + 128) and `qtile` its query tile
+	                           // with the cells' constants behind it: scores are upper bounds (MODE 7)
 	int32_t q_mode3;           // 300-d bf16 rows: 1 = query tile in LDS (MODE 3, 136 VGPRs with general gaps), 0 = in registers (MODE 0, 160);
 	                           // 300-d fp32 rows: 1 = the specialised form (MODE 4), 0 = the generic loop (MODE 1)
 	const int32_t *group_list; // null: all groups of 4 slices; else the groups holding one long slice each (64-thread blocks)
@@ -340,6 +344,18 @@ size_t vk_wide_lds_demand(int32_t max_len, int32_t nq, int32_t gap_mode, int32_t
 size_t vk_wide_scratch_bytes(int32_t max_len, int32_t nq, int32_t gap_mode, int32_t flow, int32_t ring);
 int32_t vk_wide_gs_blocks(int32_t max_len, int32_t nq, int32_t gap_mode, int32_t flow_k, int64_t n_sent, int32_t ring);
 int32_t vk_wide_ring_rows(int32_t nq, int32_t gap_mode, int32_t ws_tail);
+// the 8-bit shadow of a bf16 contextual corpus (vk_pack.hip): stats = 4 words (largest |s xq|, largest |x| as float bits; not finite)
+hipError_t vk_launch_shadow(const uint8_t *tiles, int64_t n_tiles, int64_t rows_total, int32_t d, int32_t tile_bytes, int32_t nk64,
+	uint8_t *shadow, uint32_t *stats, hipStream_t stream);
+hipError_t vk_launch_i8_probe(const int8_t *q, const int8_t *x, int32_t *out, hipStream_t stream);
+// rows of the keys (up to the first empty slot of `n`) as groups of four rows of the slice table (vk_score_kernel's group_list)
+// theta on the device: the score of *theta_key (floor_excl when that slot is empty)
+hipError_t vk_launch_select_ge_key(const float *scores, int64_t n, const uint64_t *theta_key, float floor_excl, uint64_t *keys_out,
+	uint32_t *counter, uint32_t cap, hipStream_t stream);
+// the rows of `keys` keyed by scores[row] (0: empty slot, or not above floor_excl)
+hipError_t vk_launch_rekey(const uint64_t *keys, int32_t n, const float *scores, float floor_excl, uint64_t *out, hipStream_t stream);
+hipError_t vk_launch_topk_unsorted(const uint64_t *in, int32_t n, int32_t k, uint64_t *out, hipStream_t stream);   // n, k <= 2048: one block's full sort
+hipError_t vk_launch_key_groups(const uint64_t *keys, int32_t n, int32_t *groups, hipStream_t stream);
 hipError_t vk_launch_pack(const void *in, int32_t dtype_bf16, int64_t n_rows, int32_t d, int32_t d_pad, int64_t row0,
 	uint8_t *tiles, float *mag_out, int32_t normalize, int32_t prec, hipStream_t stream);
 // queries of 17..32 tokens, linear / affine gaps (vk_score32.hip)

@@ -58,6 +58,17 @@ using vk_host::gap_cost;
 constexpr int kTopkChunk = 2048;
 constexpr int kGapTable = 640;   // entries of the gap tables sent to the device (> VK_MAX_SENT_LEN)
 constexpr int64_t kStageBytes = 64ll << 20;
+// The 8-bit bound pass.  VK_BOUND_PASS, read at finalize and per query: "off" no shadow and no bound pass, "force" both
+// whatever the corpus size, anything else the default -- from kBoundPassMinSentences slices on.  1,000,000 is the one size at which
+// the path has been measured against the exact pass (1.8 x); smaller corpora pay the shadow's + 54 % bytes, one more
+// host synchronisation and about ten small launches per query for a gain nobody has measured, so they stay on the exact pass
+// unless the caller asks (force).  Lower it only from a sweep of sizes recorded under profiles/.
+constexpr int64_t kBoundPassMinSentences = 1000000;
+constexpr int64_t kBoundRound2Floor = 1024; // round 2 rescores up to max(n / 16, this) slices; more: the full exact pass instead
+inline int bound_pass_mode() {
+	const char *e = getenv("VK_BOUND_PASS");
+	return !e ? 0 : !strcmp(e, "off") ? -1 : !strcmp(e, "force") ? 1 : 0;
+}
 
 } // namespace
 
@@ -118,6 +129,11 @@ struct vk_corpus_shape {
 	// `shared` the block this handle allocates into (a view: its source's), `vectors_of` the block of the source of a filtered
 	// static corpus (its vocabulary tiles and magnitudes).  The raw pointers above are aliases into these blocks.
 	std::shared_ptr<vk_devblock> shared, vectors_of;
+	// the 8-bit shadow of the token rows (null: none), in `shared` like the tiles: shadow_nk64 K-steps of 64 int8 per tile of
+	// shadow_tile_bytes, and the corpus-wide constants of the bound -- shadow_n >= every |s_x xq|, shadow_x >= every |x|
+	const uint8_t *shadow = nullptr;
+	int shadow_nk64 = 0, shadow_tile_bytes = 0;
+	float shadow_n = 0.0f, shadow_x = 0.0f;
 };
 
 // The handle: the shape above and what is this handle's alone.  Every workspace is a vk_devbuf (vk_devbuf.h): sized by reserve() where
@@ -159,6 +175,15 @@ struct vk_corpus : vk_corpus_shape {
 	int64_t bl_empty = 0;        // slices without tokens (in no bucket: their scores stay -inf)
 	// batched relaxed WMD over the static layout (vk_rwmd_static32_kernel): the rows of the slice table by length bucket (1..32 /
 	// 33..64 tokens; null lists when every slice has exactly 32 tokens), the batch's similarity table and its diagonal cells
+	// the bound pass (vk_query.cpp score_bounded): the query's 8-bit tile, the bound of every row, the groups its rounds rescore
+	vk_devbuf<uint8_t> d_qtile8; vk_devbuf<float> d_ub; vk_devbuf<int32_t> d_bound_groups; vk_devbuf<uint64_t> d_bound_keys;
+	struct bound_state {
+		bool pruned = false;          // d_scores holds the contenders' scores only: vk_last_scores runs `full` first
+		VkScoreParams full{}; int full_grid = 0; size_t full_smem = 0;   // the exact pass of the last query (its workspaces stay until the next)
+		int64_t ran = 0, round1 = 0, round2 = 0, fell_back = 0;           // the last query: bound pass ran, candidates of the rounds, full pass after all
+		int64_t queries = 0, fallbacks = 0, survivors = 0;                // since the handle was made
+		vk_host::bound_backoff backoff;                                    // default mode: when the handle stops trying (vk_result_host.h)
+	} bp;
 	vk_devbuf<int32_t> d_sb_id[2]; int64_t sb_n[2] = {0, 0}; bool sb_built = false; int64_t sb_empty = 0;
 	vk_devbuf<uint16_t> d_btable;
 	vk_devbuf<int64_t> d_bfix;
@@ -201,7 +226,8 @@ template <typename T> int alloc_shared(vk_corpus *c, T **p, size_t n) {
 int vk_wait_peer_turn(vk_corpus *c, hipStream_t st);
 int vk_validate_query(const vk_corpus *c, const vk_query_desc *q, const vk_topk_out *out);
 int vk_longq_query(vk_corpus *c, const vk_query_desc *q, vk_topk_out *out, vk_host_keep &keep);   // vk_longq_host.cpp
-void vk_pack_query(const vk_corpus *c, const vk_query_desc *q, std::vector<uint8_t> &tile, float *mags);
+// tile8: with a shadow, the query's 8-bit tile and the cells' constants behind it (left empty when a row is not finite)
+void vk_pack_query(const vk_corpus *c, const vk_query_desc *q, std::vector<uint8_t> &tile, float *mags, std::vector<uint8_t> *tile8 = nullptr);
 
 // ---- steps the query paths share (vk_query.cpp, vk_longq_host.cpp, vk_batch.cpp); the rules without a device are in vk_result_host.h
 namespace {
@@ -229,7 +255,7 @@ void state_timings(vk_corpus *c, bool flow, int scored = 2) {
 	vk_timings t{};
 	if (hipEventElapsedTime(&ms, c->ev[0], c->ev[5]) == hipSuccess) t.prepare_ms = ms;
 	if (hipEventElapsedTime(&ms, c->ev[5], c->ev[1]) == hipSuccess) t.queue_ms = ms;
-	if (hipEventElapsedTime(&ms, c->ev[1], c->ev[scored]) == hipSuccess) t.score_ms = ms;
+	if (hipEventElapsedTime(&ms, c->ev[1], c->ev[scored]) == hipSuccess) t.score_ms = ms;   // (a pruned query: the bound pass; its rounds count below)
 	if (hipEventElapsedTime(&ms, c->ev[scored], c->ev[3]) == hipSuccess) t.topk_ms = ms;
 	if (flow && hipEventElapsedTime(&ms, c->ev[3], c->ev[4]) == hipSuccess) t.flow_ms = ms;
 	if (hipEventElapsedTime(&ms, c->ev[0], c->ev[4]) == hipSuccess) t.total_ms = ms - t.queue_ms;
@@ -252,9 +278,9 @@ int select_waves(vk_corpus *c, float floor, int kk, hipStream_t st, const uint64
 	return VK_OK;
 }
 // Block selection (kk <= VK_MAX_MATCHES): each block sorts 2,048 keys and keeps its kk best, until one block is left
-int select_blocks(vk_corpus *c, float floor, int kk, hipStream_t st, const uint64_t **d_sel) {
+int select_blocks(vk_corpus *c, float floor, int kk, hipStream_t st, const uint64_t **d_sel, const float *scores = nullptr) {
 	int nb = 0, cur = 0;
-	VK_HIP(vk_launch_topk_scores(c->d_scores, c->n_entries, floor, kk, c->d_keys[0], &nb, st));
+	VK_HIP(vk_launch_topk_scores(scores ? scores : (const float *)c->d_scores, c->n_entries, floor, kk, c->d_keys[0], &nb, st));
 	while (nb > 1) {
 		VK_HIP(vk_launch_topk_keys(c->d_keys[cur], (int64_t)nb * kk, kk, c->d_keys[1 - cur], &nb, st));
 		cur = 1 - cur;
@@ -264,8 +290,15 @@ int select_blocks(vk_corpus *c, float floor, int kk, hipStream_t st, const uint6
 }
 
 // the caller's boost per slice as d_boost per row of the slice table (padding rows: 1)
-int upload_boost(vk_corpus *c, const float *boost, vk_host_keep &keep, hipStream_t st) {
+// (nonneg: also answers whether every slice's boost is >= 0 -- the bound pass needs it; one more pass over the caller's array, vectorised)
+int upload_boost(vk_corpus *c, const float *boost, vk_host_keep &keep, hipStream_t st, bool *nonneg = nullptr) {
 	const int64_t n = c->n_entries;
+	if (nonneg) {
+		float least = 0.0f;
+		bool nan = false;
+		for (int64_t s = 0; s < c->desc.n_sentences; s++) { least = std::min(least, boost[s]); nan = nan || boost[s] != boost[s]; }
+		*nonneg = !(least < 0.0f) && !nan;
+	}
 	if (int rc = c->d_boost.reserve((size_t)n + 8, &c->device_bytes)) return rc;
 	if (!c->entry_sent.empty()) {
 		std::vector<float> &rows = keep.vec<float>((size_t)n);

@@ -84,6 +84,84 @@ __global__ __launch_bounds__(256) void vk_pack_rows_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// The 8-bit shadow of a bf16 contextual corpus, built once at vk_corpus_finalize.  A shadow tile is 16 rows like a token
+// tile: nk64 blocks of 1 KiB in the operand order of v_mfma_i32_16x16x64_i8 (block t, lane 16 g + i: row i, features 64 t + 16 g .. + 15;
+// features >= d are zero), then 16 x (s_x, e_x) as floats.  One thread per row; the arithmetic is vk_host::quantize_row_i8
+// (vk_result_host.h) statement for statement.  stats[0] / [1]: the largest |s_x xq| / |x| of the corpus as float bits (non-negative
+// floats order as their bits), stats[2]: some element is not finite (no shadow then).
+// ---------------------------------------------------------------------------
+
+__device__ __forceinline__ float quant_up_dev(double x) {
+	if (!(x > 0.0)) return 0.0f;
+	const float f = (float)(x * (1.0 + 1e-6));
+	return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, f) + 1u);   // nextafterf(f, +inf) of a positive finite float
+}
+
+__global__ __launch_bounds__(256) void vk_shadow_kernel(const uint8_t *__restrict__ tiles, int64_t n_tiles, int64_t rows_total, int32_t d,
+	int32_t tile_bytes, int32_t nk64, uint8_t *__restrict__ shadow, uint32_t *__restrict__ stats) {
+	const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (row >= n_tiles * 16) return;
+	const int i = (int)(row & 15);
+	const uint8_t *src = tiles + (row >> 4) * (int64_t)tile_bytes;
+	const int64_t sh_bytes = (int64_t)nk64 * 1024 + 128;
+	uint8_t *dst = shadow + (row >> 4) * sh_bytes;
+	const int dk = row < rows_total ? d : 0;   // rows past the corpus (the tile's padding, the zero tile): zeros
+	float m = 0.0f;
+	bool bad = false;
+	for (int k = 0; k < dk; k++) {
+		const float x = tile_elem(src, i, k, 0);
+		bad = bad || !(fabsf(x) <= 3.4028234e38f);
+		m = fmaxf(m, fabsf(x));
+	}
+	const float s = m / 127.0f;
+	double e2 = 0.0, n2 = 0.0, a2 = 0.0;
+	for (int c = 0; c < nk64 * 4; c++) {   // chunks of 16 features: block c >> 2, lane group c & 3
+		uint32_t w[4] = {0u, 0u, 0u, 0u};
+		for (int j = 0; j < 16; j++) {
+			const int k = c * 16 + j;
+			if (k >= dk) break;
+			const float x = tile_elem(src, i, k, 0);
+			int v = 0;
+			if (s > 0.0f) v = (int)fminf(127.0f, fmaxf(-127.0f, nearbyintf(x / s)));
+			const double xs = (double)s * (double)v, dd = (double)x - xs;
+			e2 += dd * dd; n2 += xs * xs; a2 += (double)x * (double)x;
+			w[j >> 2] |= ((uint32_t)v & 255u) << ((j & 3) * 8);
+		}
+		*reinterpret_cast<uint4 *>(dst + (c >> 2) * 1024 + ((c & 3) * 16 + i) * 16) = uint4{w[0], w[1], w[2], w[3]};
+	}
+	const float e = quant_up_dev(sqrt(e2)), nn = quant_up_dev(sqrt(n2)), a = quant_up_dev(sqrt(a2));
+	*reinterpret_cast<float2 *>(dst + (int64_t)nk64 * 1024 + i * 8) = float2{s, e};
+	if (bad) atomicOr(stats + 2, 1u);
+	else {
+		atomicMax(stats + 0, __builtin_bit_cast(uint32_t, nn));
+		atomicMax(stats + 1, __builtin_bit_cast(uint32_t, a));
+	}
+}
+
+extern "C" hipError_t vk_launch_shadow(const uint8_t *tiles, int64_t n_tiles, int64_t rows_total, int32_t d, int32_t tile_bytes, int32_t nk64,
+	uint8_t *shadow, uint32_t *stats, hipStream_t stream) {
+	hipError_t e = hipMemsetAsync(stats, 0, 16, stream);
+	if (e != hipSuccess) return e;
+	vk_shadow_kernel<<<(unsigned)((n_tiles * 16 + 255) / 256), 256, 0, stream>>>(tiles, n_tiles, rows_total, d, tile_bytes, nk64, shadow, stats);
+	return hipGetLastError();
+}
+
+// One v_mfma_i32_16x16x64_i8 on a query tile and a token tile of 16 rows x 64 int8 each, row-major in, packed as the shadow packs
+// them: out[16 j + i] = sum_k q[j][k] x[i][k].  The lane map of the operands, checked with exact integers (tests/test_gpu_bound_pass.py).
+__global__ void vk_i8_probe_kernel(const int8_t *__restrict__ q, const int8_t *__restrict__ x, int32_t *__restrict__ out) {
+	const int lane = threadIdx.x, g = lane >> 4, i = lane & 15;
+	const i32x4 a = *reinterpret_cast<const i32x4 *>(q + i * 64 + g * 16);
+	const i32x4 b = *reinterpret_cast<const i32x4 *>(x + i * 64 + g * 16);
+	i32x4 acc = {0, 0, 0, 0};
+	acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, acc, 0, 0, 0);
+	for (int r = 0; r < 4; r++) out[(4 * g + r) * 16 + i] = acc[r];
+}
+extern "C" hipError_t vk_launch_i8_probe(const int8_t *q, const int8_t *x, int32_t *out, hipStream_t stream) {
+	vk_i8_probe_kernel<<<1, 64, 0, stream>>>(q, x, out);
+	return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // static layout: per-query similarity table [V_pad x 16] (metric/static.cpp:9-78)
 // ---------------------------------------------------------------------------
 

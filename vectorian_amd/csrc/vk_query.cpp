@@ -147,7 +147,7 @@ int vk_validate_query(const vk_corpus *c, const vk_query_desc *q, const vk_topk_
 
 // Vectors.normalized for the query rows, then bf16 (RNE), then tile order (16 rows,
 // rows >= len_t zero).  Same arithmetic as oracle/vk_oracle.c vko_normalize_rows_bf16.
-void vk_pack_query(const vk_corpus *c, const vk_query_desc *q, std::vector<uint8_t> &tile, float *mags) {
+void vk_pack_query(const vk_corpus *c, const vk_query_desc *q, std::vector<uint8_t> &tile, float *mags, std::vector<uint8_t> *tile8) {
 	const int d = c->desc.d;
 	tile.assign((size_t)c->tile_bytes * (size_t)((q->len_t + 15) / 16), 0);   // tile i / 16 holds row i % 16
 	std::vector<float> row((size_t)d);
@@ -179,6 +179,100 @@ void vk_pack_query(const vk_corpus *c, const vk_query_desc *q, std::vector<uint8
 			memcpy(&tile[off], &b, 2);
 		}
 	}
+	// The bound pass: the rows as stored (bf16) quantized like the shadow's, in the operand order of the 8-bit MFMA (block
+	// k / 64, lane 16 ((k % 64) / 16) + row, byte k % 16), then cs[16], ca[16], cb[16] -- zeros for the rows past the query, so that
+	// their cells are the exact kernel's zeros.
+	if (!tile8 || !c->shadow || c->prec || q->len_t > VK_FAST_QUERY_LEN) return;
+	const int nk64 = c->shadow_nk64;
+	std::vector<uint8_t> t8((size_t)nk64 * 1024 + 3 * 16 * 4, 0);
+	std::vector<int8_t> xq((size_t)d);
+	float *cst = reinterpret_cast<float *>(t8.data() + (size_t)nk64 * 1024);
+	for (int i = 0; i < q->len_t; i++) {
+		for (int k = 0; k < d; k++) {
+			uint16_t b;
+			memcpy(&b, &tile[(size_t)(k >> 5) * 1024 + (size_t)(((k & 31) >> 3) * 16 + i) * 16 + (size_t)(k & 7) * 2], 2);
+			row[(size_t)k] = bf16_to_f32(b);
+			if (!(std::fabs(row[(size_t)k]) <= 3.4028234e38f)) return;   // not finite: no bound for this query
+		}
+		const vk_host::quant_meta m = vk_host::quantize_row_i8(row.data(), d, xq.data());
+		for (int k = 0; k < d; k++) t8[(size_t)(k >> 6) * 1024 + (size_t)(((k & 63) >> 4) * 16 + i) * 16 + (size_t)(k & 15)] = (uint8_t)xq[(size_t)k];
+		vk_host::bound_cell_constants(m, c->shadow_n, c->shadow_x, nk64 * 64, &cst[i], &cst[16 + i], &cst[32 + i]);
+	}
+	tile8->swap(t8);
+}
+
+// The bound pass and its two rounds in place of the exact pass `p` over every slice: afterwards d_scores (and d_raw when
+// p.raw) hold today's floats for every slice that can be among the kk best above sel_floor, and something below the kk-th best
+// (-inf, or the exact score of a contender's neighbour in its group of four) everywhere else.  Records ev[2] right after the bound
+// kernel: the peer's turn begins there.  smem_list: the dynamic LDS of the exact kernel with one wave per workgroup (group_list).
+static int score_bounded(vk_corpus *c, const VkScoreParams &p, int grid, size_t smem, size_t smem_bound, size_t smem_list, int kk, float sel_floor,
+	vk_host_keep &keep, hipStream_t st, const uint64_t **d_sel) {
+	*d_sel = nullptr;
+	const int64_t n = c->n_entries;
+	vk_corpus::bound_state &b = c->bp;
+	const int64_t most = std::max<int64_t>(n / 16, kBoundRound2Floor);   // slices round 2 may rescore
+	// Round 1 takes the M largest bounds, M >= 2 kk where a block of the selection holds that many.  THE largest, through the block
+	// selection (sorts of 2,048 keys in LDS, a few stages): then theta >= (the kk-th largest bound) - slack >= (the kk-th best exact
+	// score) - slack, whatever the order of the rows, which is what tests/test_gpu_bound_pass.py holds round 2 against.  (The wave
+	// selection's last stage is one wave's serial work and starves beside the peer's bound pass: 1.4 ms where 0.16 ms were measured alone.)
+	const int M = kk <= 32 ? 64 : kk <= 256 ? 512 : VK_MAX_MATCHES;
+	int rc;
+	if ((rc = c->d_ub.reserve((size_t)n + 8, &c->device_bytes))) return rc;
+	if ((rc = c->d_bound_groups.reserve((size_t)std::max<int64_t>(most, kTopkChunk), &c->device_bytes))) return rc;
+	if ((rc = c->d_bound_keys.reserve((size_t)2 * kTopkChunk, &c->device_bytes))) return rc;
+	if ((rc = c->d_counter.reserve(4, &c->device_bytes))) return rc;
+	VkScoreParams pb = p;
+	pb.tiles = c->shadow; pb.nk32 = c->shadow_nk64; pb.tail = 0; pb.tile_bytes = c->shadow_tile_bytes; pb.bound_i8 = 1;
+	pb.q_mode3 = 0; pb.q_lds = 0; pb.qtile = c->d_qtile8; pb.scores = c->d_ub; pb.raw = nullptr;
+	VK_HIP(vk_launch_score(&pb, grid, smem_bound, st));
+	VK_HIP(hipEventRecord(c->ev[2], st));
+	c->ev2_recorded = true;
+	b.ran = 1; b.queries++;
+	VK_HIP(hipMemsetD32Async(static_cast<hipDeviceptr_t>(c->d_scores), (int)0xff800000u, (size_t)n, st));
+	if (p.raw) VK_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p.raw), (int)0xff800000u, (size_t)n, st));
+	VkScoreParams pl = p;
+	pl.group_list = c->d_bound_groups;
+	// round 1: their groups scored exactly; theta = the kk-th best of those exact scores (the floor when there
+	// are fewer), which stays on the device: round 2 follows without a trip to the host
+	const uint64_t *d_first = nullptr;
+	if ((rc = select_blocks(c, sel_floor, M, st, &d_first, c->d_ub))) return rc;
+	VK_HIP(vk_launch_key_groups(d_first, M, c->d_bound_groups, st));
+	pl.n_list = M;
+	VK_HIP(vk_launch_score(&pl, M, smem_list, st));
+	uint64_t *d_exact = c->d_bound_keys, *d_best = c->d_bound_keys + kTopkChunk;
+	VK_HIP(vk_launch_rekey(d_first, M, c->d_scores, sel_floor, d_exact, st));
+	VK_HIP(vk_launch_topk_unsorted(d_exact, M, kk, d_best, st));   // (one block: its kk best, sorted)
+	// round 2: every slice whose bound reaches theta (those of round 1 among them: the same floats again)
+	VK_HIP(vk_launch_select_ge_key(c->d_ub, n, d_best + (kk - 1), sel_floor, c->d_keys[0], c->d_counter, (uint32_t)most, st));
+	uint32_t &count = *keep.array<uint32_t>(1);
+	VK_HIP(hipMemcpyAsync(&count, c->d_counter, 4, hipMemcpyDeviceToHost, st));
+	VK_HIP(hipStreamSynchronize(st));
+	b.round1 = M;
+	bool fell = false;
+	if ((int64_t)count > most) {
+		fell = true;   // the bounds do not separate the contenders: the exact pass over every slice, as without a shadow
+		VK_HIP(vk_launch_score(&p, grid, smem, st));
+	} else if (count > 0) {
+		VK_HIP(vk_launch_key_groups(c->d_keys[0], (int32_t)count, c->d_bound_groups, st));
+		pl.n_list = (int32_t)count;
+		VK_HIP(vk_launch_score(&pl, (int32_t)count, smem_list, st));
+	}
+	if (!fell && count <= (uint32_t)kTopkChunk) {
+		// the kk best are among the slices of round 2 (a slice that reaches theta has a bound that does): selected from those keys by one
+		// block -- the same keys in the same order as the selection over every row's score gives
+		VK_HIP(vk_launch_rekey(c->d_keys[0], (int32_t)count, c->d_scores, sel_floor, d_exact, st));
+		VK_HIP(vk_launch_topk_unsorted(d_exact, (int32_t)count, kk, d_best, st));
+		*d_sel = d_best;
+	}
+	b.round2 = count;
+	if (!fell) b.survivors += count;
+	b.fell_back = fell ? 1 : 0;
+	if (fell) b.fallbacks++;
+	// most of the last eight bound passes fell back: the next 64 queries go without one (worst case)
+	if (bound_pass_mode() == 0) b.backoff.record(fell);
+	b.pruned = !fell;
+	b.full = p; b.full_grid = grid; b.full_smem = smem;
+	return VK_OK;
 }
 
 // One query.  Every host buffer that is the source or the destination of an asynchronous copy lives in `keep`, which the entry point
@@ -187,6 +281,7 @@ void vk_pack_query(const vk_corpus *c, const vk_query_desc *q, std::vector<uint8
 static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_host_keep &keep) {
 	int rc = VK_OK;
 	VK_HIP(hipSetDevice(c->device));
+	c->bp.pruned = false; c->bp.ran = c->bp.round1 = c->bp.round2 = c->bp.fell_back = 0;
 	if (q->len_t > VK_MAX_QUERY_LEN) return vk_longq_query(c, q, out, keep);   // 65 .. 512 tokens (vk_longq_host.cpp)
 	hipStream_t st = c->stream;
 	const int64_t n = c->n_entries;           // rows of the slice table (== n_sentences unless long slices were padded)
@@ -285,8 +380,20 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	// (... and the slices of 65 .. 512 tokens that general gaps send through the one-wave-per-slice pass)
 	const bool doc_fast = (xlong || rwmd_long_doc || (long_via_wide && !getenv("VK_NO_DOC_MID"))) && !wide_score && (q->algorithm == VK_ALG_ALIGN || q->algorithm == VK_ALG_RWMD) && !getenv("VK_NO_DOC_KERNEL");
 	const int nq = (q->len_t + 15) / 16;
-	vk_pack_query(c, q, qtile, qmags);
+	// the bound pass can take this query: alignment of at most 16 tokens over a corpus with a shadow, nothing that changes a
+	// cell or the reference score per slice (tag weights, submatch weight), every slice scored; the boost is checked where it is uploaded
+	const int bound_mode = bound_pass_mode();
+	bool bound_ok = c->shadow && bound_mode >= 0 && (bound_mode > 0 || c->desc.n_sentences >= kBoundPassMinSentences) && q->algorithm == VK_ALG_ALIGN &&
+		q->len_t <= VK_FAST_QUERY_LEN && q->submatch_weight == 0.0f && !q->tag_weights && !only && c->n_long_groups == 0 && c->max_len <= VK_FAST_SENT_LEN;
+	if (bound_ok && bound_mode == 0 && !c->bp.backoff.take()) bound_ok = false;
+	std::vector<uint8_t> &qtile8 = keep.vec<uint8_t>();
+	vk_pack_query(c, q, qtile, qmags, bound_ok ? &qtile8 : nullptr);
 	VK_HIP(hipMemcpyAsync(c->d_qtile, qtile.data(), qtile.size(), hipMemcpyHostToDevice, st));
+	bound_ok = bound_ok && !qtile8.empty();
+	if (bound_ok) {
+		if ((rc = c->d_qtile8.reserve(qtile8.size(), &c->device_bytes))) return rc;
+		VK_HIP(hipMemcpyAsync(c->d_qtile8, qtile8.data(), qtile8.size(), hipMemcpyHostToDevice, st));
+	}
 
 	VkScoreParams p{};
 	bool span_skip_raw = false;   // span-embedding path without its second output array
@@ -349,7 +456,9 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	VK_HIP(hipMemcpyAsync(c->d_ws, ws.data(), n_ws * sizeof(float), hipMemcpyHostToDevice, st));
 	VK_HIP(hipMemcpyAsync(c->d_wt, wt, 160 * sizeof(float), hipMemcpyHostToDevice, st));
 
-	if (q->boost && (rc = upload_boost(c, q->boost, keep, st))) return rc;
+	bool boost_nonneg = true;   // a score is monotone in its cells only under a boost >= 0: looked at where the boost is uploaded
+	if (q->boost && (rc = upload_boost(c, q->boost, keep, st, bound_ok ? &boost_nonneg : nullptr))) return rc;
+	bound_ok = bound_ok && boost_nonneg;
 
 	const bool is_static = c->desc.layout == VK_LAYOUT_STATIC;
 	const int64_t table_stride = (int64_t)c->n_tiles * 16 * 16;
@@ -361,6 +470,17 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 			VK_HIP(vk_launch_table(c->d_tiles, c->d_qtile + (size_t)t * c->tile_bytes, (int32_t)c->n_tiles, c->nk32, c->tail, c->tile_bytes,
 				c->d_table + t * table_stride, q->q_token_ids ? c->d_qids + t * 16 : nullptr, std::min(16, q->len_t - t * 16), c->desc.vocab_size, c->prec, st));
 	}
+
+	// ---- the size of the selection (known before the scoring pass: the bound pass prunes against it)
+	const bool do_flow = q->want_flow && is_align;
+	// Relaxed word mover's distance: likewise -- the rows of the winners come back in the canonical arithmetic (vk_rows_kernel) and
+	// the host restates each winner's score from them in the reference's order of operations (vk_transport_host.h): the scores of the
+	// result set are the oracle's floats, whichever kernel ranked the slices (per query, batched GEMM, a shard of the corpus).
+	const bool canon_tr = q->algorithm == VK_ALG_RWMD && !q->wmd_full && q->want_flow && out->sim_rows != nullptr;
+	constexpr int kCanonMargin = 8;
+	// (57 .. 64 matches: the margin takes the selection to the k > 64 path; beyond VK_MAX_MATCHES: every score is sorted, never more winners than rows)
+	const int kk = only ? q->n_only : (int)std::min<int64_t>(!(do_flow || canon_tr) ? k : (k <= VK_MAX_MATCHES ? std::min(k + kCanonMargin, VK_MAX_MATCHES) : k + kCanonMargin), std::max<int64_t>(n, 1));
+	const float sel_floor = (do_flow || canon_tr) ? q->min_score - 1e-5f * std::max(1.0f, std::fabs(q->min_score)) : q->min_score;
 
 	// ---- the fused scoring kernel ------------------------------------------
 	// handles on one corpus take turns: this scoring kernel starts when the peer's has finished (its selection and
@@ -407,6 +527,8 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		p.qid_bits = c->d_qbits; p.tag_s = c->d_tag; p.slices_overlap = c->overlapping ? 1 : 0;
 		for (int j = 0; j < VK_FAST_QUERY_LEN; j++) p.qkey[j] = qkey_all[j];
 	}
+	bool bounded = false;   // the scoring pass was the bound pass and its rounds (score_bounded)
+	const uint64_t *d_sel_bounded = nullptr;   // ... which selected the kk best among their candidates already
 	VkWideParams wp{};
 	// Winners of 65 .. 512 tokens under linear / affine gaps (scored by the fused kernel's long pass): their tracebacks on vk_doc_kernel's
 	// sweep as well -- vk_flow_kernel fills such a matrix row by row in LDS (8,000 slices of 300 .. 512 tokens: 1.6 ms of a 2.8 ms query)
@@ -608,7 +730,17 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	if (smem > 160 * 1024) return fail(VK_ERR_UNSUPPORTED, "LDS demand exceeds 160 KiB per workgroup");
 	const int64_t n_groups = (n + 3) / 4;
 	const int grid = (int)std::min<int64_t>((n_groups + 3) / 4, (int64_t)1 << 20);   // capped to residency by the launcher
-	if (!only) VK_HIP(vk_launch_score(&p, grid, smem, st));
+	// the 8-bit bound pass and exact scores of the contenders only, or the exact pass over every slice
+	bounded = bound_ok && kk <= VK_MAX_MATCHES && (p.gap_mode == 0 || p.gap_mode == 1 || p.gap_mode == 3 || p.gap_mode == 6);
+	if (bounded) {
+		// the bound kernel: the four waves' strips as above, and in place of the exact kernel's query tile the 8-bit one with the
+		// cells' constants behind it -- the region MODE 7 of vk_score_kernel steps over (NK32 KiB + VK_DEV_BOUND_CONST_BYTES)
+		const size_t smem_strips = smem - qlds - (size_t)p.q_lds;
+		const size_t smem_bound = smem_strips + (size_t)c->shadow_nk64 * 1024 + VK_DEV_BOUND_CONST_BYTES;
+		// the exact kernel over a group_list: one wave per workgroup, its strip and the exact query tile
+		const size_t smem_list = (size_t)lds_floats * 4 + qlds + (size_t)p.q_lds;
+		if ((rc = score_bounded(c, p, grid, smem, smem_bound, smem_list, kk, sel_floor, keep, st, &d_sel_bounded))) return rc;
+	} else if (!only) VK_HIP(vk_launch_score(&p, grid, smem, st));
 	if (c->n_long_groups > 0 && !only && !long_via_wide && !rwmd_long_doc) {
 		// slices longer than VK_FAST_SENT_LEN: one per wave, one wave per workgroup, LDS strip for the longest;
 		// general gaps take the LDS-history form (the four DPP rows share one history: only row 0 is active)
@@ -873,7 +1005,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	}
 
 	// ---- bounded result set -------------------------------------------------
-	VK_HIP(hipEventRecord(c->ev[2], st));
+	if (!bounded) VK_HIP(hipEventRecord(c->ev[2], st));   // (a pruned query recorded it after its bound pass)
 	c->ev2_recorded = true;
 	const bool rows_on_request = out->sim_rows != nullptr;   // alignments: similarity rows of the winners only on request (debug hook)
 	// Alignments with traceback: the scores of the scoring pass rest on MFMA cosines and differ from the oracle's in the last
@@ -881,20 +1013,11 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	// oracle's, bit for bit).  So that the result SET is the oracle's too, a few runners-up are retraced with the winners
 	// (kCanonMargin more slices; the floor of the selection is lowered by the rounding slack likewise) and the k best canonical
 	// scores are kept: exact unless more than kCanonMargin slices sit within rounding (~2e-6) of the k-th score.
-	const bool do_flow = q->want_flow && is_align;
-	// Relaxed word mover's distance: likewise -- the rows of the winners come back in the canonical arithmetic (vk_rows_kernel) and
-	// the host restates each winner's score from them in the reference's order of operations (vk_transport_host.h): the scores of the
-	// result set are the oracle's floats, whichever kernel ranked the slices (per query, batched GEMM, a shard of the corpus).
-	const bool canon_tr = q->algorithm == VK_ALG_RWMD && !q->wmd_full && q->want_flow && out->sim_rows != nullptr;
-	constexpr int kCanonMargin = 8;
-	// (57 .. 64 matches: the margin takes the selection to the k > 64 path; beyond VK_MAX_MATCHES: every score is sorted, never more winners than rows)
-	const int kk = only ? q->n_only : (int)std::min<int64_t>(!(do_flow || canon_tr) ? k : (k <= VK_MAX_MATCHES ? std::min(k + kCanonMargin, VK_MAX_MATCHES) : k + kCanonMargin), std::max<int64_t>(n, 1));
 	const uint64_t *d_sel = nullptr;   // the selected keys on the device, best first
 	// the winners' device arrays: grown to this result set
 	if ((rc = c->d_out_raw.reserve((size_t)kk, &c->device_bytes))) return rc;
 	if ((rc = c->d_out_sim.reserve((size_t)kk * 64, &c->device_bytes))) return rc;
 	if ((rc = c->d_out_map.reserve((size_t)kk * 64, &c->device_bytes))) return rc;
-	const float sel_floor = (do_flow || canon_tr) ? q->min_score - 1e-5f * std::max(1.0f, std::fabs(q->min_score)) : q->min_score;
 	if (only) {
 		// keys of the listed slices, in the caller's order (rows of the slice table: long slices sit in padded groups)
 		std::vector<uint64_t> &hk = keep.vec<uint64_t>((size_t)q->n_only);
@@ -912,7 +1035,8 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		if ((rc = c->d_sort_temp.reserve(temp_bytes, &c->device_bytes))) return rc;
 		VK_HIP(vk_launch_sort_all(c->d_scores, n, sel_floor, c->d_sort[0], c->d_sort[1], c->d_sort_temp, &temp_bytes, &sorted, st));
 		d_sel = sorted;
-	} else if ((rc = kk <= 64 ? select_waves(c, sel_floor, kk, st, &d_sel) : select_blocks(c, sel_floor, kk, st, &d_sel))) return rc;
+	} else if (d_sel_bounded) d_sel = d_sel_bounded;
+	else if ((rc = kk <= 64 ? select_waves(c, sel_floor, kk, st, &d_sel) : select_blocks(c, sel_floor, kk, st, &d_sel))) return rc;
 
 	// ---- flow of the winners ------------------------------------------------
 	VK_HIP(hipEventRecord(c->ev[3], st));

@@ -113,6 +113,57 @@ inline void wt_with_closure(float *wt, const vk_gap &gap_t, int len_t, bool is_a
 		for (int a = 1; a < k; a++) wt[80 + k] = std::min(wt[80 + k], wt[80 + a] + wt[80 + k - a]);
 }
 
+// ---- the 8-bit bound pass: the quantizer of one row x (the bf16 values as stored, handed over as floats).
+// s = max|x| / 127, xq[k] = round(x[k] / s) (to nearest even, within -127 .. 127); e >= |x - s xq|, n >= |s xq|, a >= |x| (Euclidean
+// norms, summed in double in k order, then rounded UP to float: quant_up).  A row of zeros gives zeros throughout.  The shadow's builder
+// (vk_shadow_kernel, vk_pack.hip) is this function statement for statement.
+struct quant_meta { float s = 0.0f, e = 0.0f, n = 0.0f, a = 0.0f; };
+inline float quant_up(double x) {
+	if (!(x > 0.0)) return 0.0f;
+	return std::nextafterf((float)(x * (1.0 + 1e-6)), INFINITY);
+}
+inline quant_meta quantize_row_i8(const float *x, int d, int8_t *xq) {
+	float m = 0.0f;
+	for (int k = 0; k < d; k++) m = std::max(m, std::fabs(x[k]));
+	quant_meta r;
+	r.s = m / 127.0f;
+	double e2 = 0.0, n2 = 0.0, a2 = 0.0;
+	for (int k = 0; k < d; k++) {
+		int v = 0;
+		if (r.s > 0.0f) v = (int)std::min(127.0f, std::max(-127.0f, std::nearbyintf(x[k] / r.s)));
+		xq[k] = (int8_t)v;
+		const double xs = (double)r.s * (double)v, dd = (double)x[k] - xs;
+		e2 += dd * dd; n2 += xs * xs; a2 += (double)x[k] * (double)x[k];
+	}
+	r.e = quant_up(std::sqrt(e2)); r.n = quant_up(std::sqrt(n2)); r.a = quant_up(std::sqrt(a2));
+	return r;
+}
+// The constants of query column j in a cell of the bound pass, ub = clip01((s_x cs) I + e_x ca + cb) (I the exact integer product):
+// cs = s_q, ca = a_q, cb = e_q N + gamma, with N >= every |s_x xq| of the corpus and X >= every |x| of it.  gamma:
+// twice d_pad 2^-24 a_q X for the fp32 accumulation of the exact kernel's MFMA cosine and the five roundings of the bound's own
+// evaluation, plus 2e-6 absolute for the same roundings near zero.  Rounded up.
+inline void bound_cell_constants(const quant_meta &q, float N, float X, int d_pad, float *cs, float *ca, float *cb) {
+	const double gamma = 2.0 * (double)d_pad * std::ldexp(1.0, -24) * (double)q.a * (double)X + 2e-6;
+	*cs = q.s; *ca = q.a;
+	*cb = quant_up((double)q.e * (double)N + gamma);
+}
+
+// When a handle stops trying the bound pass: after 5 fallbacks to the full pass among its last 8 bound passes the next 64
+// queries go without one.  A stream of queries whose bounds never separate thus pays at most 8 wasted bound passes per 72 queries.
+// take(): does this query try the bound pass; record(): how the bound pass of a query that took it ended.
+struct bound_backoff {
+	uint32_t recent = 0;   // fallbacks among the last 8 bound passes, one bit each
+	int skip = 0;          // queries still to go without a bound pass
+	bool take() {
+		if (skip > 0) { skip--; return false; }
+		return true;
+	}
+	void record(bool fell_back) {
+		recent = ((recent << 1) | (fell_back ? 1u : 0u)) & 0xffu;
+		if (fell_back && __builtin_popcount(recent) >= 5) { skip = 64; recent = 0; }
+	}
+};
+
 } // namespace vk_host
 
 #endif

@@ -14,6 +14,8 @@
 //   MODE 4: contextual layout, fp32 tiles of NK32 blocks of 16 features (compile time), query tile staged in LDS
 //   MODE 5: MODE 1 for bf16 rows of 256 features and more: eight K-steps in flight instead of four
 //   MODE 6: MODE 1 for fp32 rows (any d but the 300 of MODE 4)
+//   MODE 7: the 8-bit shadow of a contextual bf16 corpus, NK32 K-steps of 64 int8 (here NK32 counts those): every cell an upper bound of
+//           the cosine MODE 0 / 3 compute, so the score is an upper bound of theirs (the bound pass)
 // GAP: 0 linear, 1 affine, 2 general (LDS history, serial in-row chain),
 //      3 general, sentences <= 32 tokens, strictly subadditive w_t (register history),
 //      4 relaxed word mover's distance (no DP: row / column minima of 1 - S),
@@ -23,8 +25,15 @@
 // LT: padded query length (4, 8, 12, 16).
 // ---------------------------------------------------------------------------
 
+// VK_SCORE_VGPRS (vk_score_m7.hip): a register budget for every kernel of the unit
+#ifdef VK_SCORE_VGPRS
+#define VK_SCORE_KERNEL_ATTR __attribute__((amdgpu_num_vgpr(VK_SCORE_VGPRS)))
+#else
+#define VK_SCORE_KERNEL_ATTR
+#endif
+
 template <int MODE, int NK32, bool TAIL, int GAP, int LT>
-__global__ __launch_bounds__(256) void vk_score_kernel(VkScoreParams p) {
+__global__ __launch_bounds__(256) VK_SCORE_KERNEL_ATTR void vk_score_kernel(VkScoreParams p) {
 	extern __shared__ float4 vk_smem4[];
 	float *smem = reinterpret_cast<float *>(vk_smem4);
 	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -36,6 +45,14 @@ __global__ __launch_bounds__(256) void vk_score_kernel(VkScoreParams p) {
 			vk_smem4[i] = *reinterpret_cast<const float4 *>(p.qtile + i * 16);
 		__syncthreads();
 		smem += NK32 * 256;
+	}
+	// MODE 7: the 8-bit query tile and the cells' constants behind it (NK32 KiB + 192 bytes, in a region of NK32 KiB +
+	// VK_DEV_BOUND_CONST_BYTES, which the host adds to the launch's dynamic LDS: vk_query.cpp, smem_bound)
+	if constexpr (MODE == 7) {
+		for (int i = threadIdx.x; i < NK32 * 64 + 12; i += blockDim.x)
+			vk_smem4[i] = *reinterpret_cast<const float4 *>(p.qtile + i * 16);
+		__syncthreads();
+		smem += NK32 * 256 + VK_DEV_BOUND_CONST_BYTES / 4;
 	}
 	// MODE 1 (any d, fp32 tiles): the same staging with a runtime size; the K loop then reads the query with ds_read instead of
 	// going through L1 for every token tile
@@ -163,6 +180,7 @@ __global__ __launch_bounds__(256) void vk_score_kernel(VkScoreParams p) {
 				if constexpr (MODE == 0) acc = sim_tile<NK32, TAIL>(qf, tp, lane);
 				else if constexpr (MODE == 3) acc = sim_tile_qlds<NK32, TAIL>(qlds, tp, lane);
 				else if constexpr (MODE == 4) acc = sim_tile_f32_qlds<NK32>(qlds, tp, lane);
+				else if constexpr (MODE == 7) acc = sim_tile_i8<NK32>(qlds, tp, lane);
 				else {
 					// two calls, not one with a selected pointer: an LDS-or-global pointer is a flat pointer, and flat loads count
 					// on both wait counters -- every batch of tile loads would be waited for in full
@@ -295,8 +313,10 @@ static hipError_t launch_sized(K kernel, const VkScoreParams &p, int want_blocks
 	// narrow rows (d <= 96) are not a stream either: a slice is 6 KB or less and the DP dominates -- 64-d, 32 tokens: 3.4 TB/s at
 	// 3 per CU, 4.8 TB/s at 5; 96-d: 3.7 against 5.4 TB/s.  129..224-d: 4 per CU stream 4-8 % faster than 3 (6.4 against
 	// 6.0 TB/s); 128-d and 256..1536-d: 3 per CU within 2 % of the best setting (tools/sweep_dims.py, profiles/r02_sweep_dims*.jsonl)
-	const bool dp_bound = p.layout == VK_DEV_LAYOUT_STATIC || p.nk32 <= 3;
-	const int stream_cap = (p.nk32 >= 5 && p.nk32 <= 7) ? 4 : 3;
+	const bool dp_bound = p.layout == VK_DEV_LAYOUT_STATIC || (p.nk32 <= 3 && !p.bound_i8);
+	// the 8-bit shadow (MODE 7, 328-byte rows; 1 M x 32 tokens, general gaps): 1.58 - 1.61 ms at 3 per CU, 1.60 - 1.65 at 4, 1.70 at 5, 1.80 at 2 --
+	// and three waves per SIMD of its 120 VGPRs leave room for the rounds' exact kernel beside it (vk_score_m7.hip)
+	const int stream_cap = (!p.bound_i8 && p.nk32 >= 5 && p.nk32 <= 7) ? 4 : 3;
 	if (occ > stream_cap && !dp_bound && !bound_pass) occ = stream_cap;   // the static layout is DP-bound, not a stream: keep full residency
 	// 768-d rows: a wave already keeps 24 KiB of loads in flight per tile; one workgroup per CU measured fastest
 	// (ragged 8..64 tokens, 400 k sentences: 3.37 ms at 1, 3.45 ms at 2 per CU)

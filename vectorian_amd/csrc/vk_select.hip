@@ -210,10 +210,16 @@ extern "C" hipError_t vk_launch_submatch_bound(const float *raw, const float *bo
 
 // all slices whose bound can still enter the result set: keys (bound, row) of the rows with
 // theta <= bound and bound > floor, appended in no particular order; *counter = how many qualify
+// (theta_key: theta is the score of that key on the device -- the k-th best of a round that has not come back to the host -- or
+// floor_excl when the slot is empty)
 __global__ void vk_select_ge_kernel(const float *__restrict__ scores, int64_t n, float theta, float floor_excl,
-	uint64_t *__restrict__ keys_out, uint32_t *__restrict__ counter, uint32_t cap) {
+	uint64_t *__restrict__ keys_out, uint32_t *__restrict__ counter, uint32_t cap, const uint64_t *__restrict__ theta_key) {
 	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
+	if (theta_key) {
+		const uint32_t ob = (uint32_t)(*theta_key >> 32);
+		theta = *theta_key ? __builtin_bit_cast(float, (ob & 0x80000000u) ? (ob & 0x7fffffffu) : ~ob) : floor_excl;   // float_orderable inverted
+	}
 	const float sc = scores[i];
 	if (sc >= theta && sc > floor_excl) {
 		const uint32_t at = atomicAdd(counter, 1u);
@@ -225,7 +231,55 @@ extern "C" hipError_t vk_launch_select_ge(const float *scores, int64_t n, float 
 	uint32_t *counter, uint32_t cap, hipStream_t stream) {
 	hipError_t e = hipMemsetAsync(counter, 0, 4, stream);
 	if (e != hipSuccess) return e;
-	vk_select_ge_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(scores, n, theta, floor_excl, keys_out, counter, cap);
+	vk_select_ge_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(scores, n, theta, floor_excl, keys_out, counter, cap, nullptr);
+	return hipGetLastError();
+}
+
+extern "C" hipError_t vk_launch_select_ge_key(const float *scores, int64_t n, const uint64_t *theta_key, float floor_excl, uint64_t *keys_out,
+	uint32_t *counter, uint32_t cap, hipStream_t stream) {
+	hipError_t e = hipMemsetAsync(counter, 0, 4, stream);
+	if (e != hipSuccess) return e;
+	vk_select_ge_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(scores, n, 0.0f, floor_excl, keys_out, counter, cap, theta_key);
+	return hipGetLastError();
+}
+
+// the keys' rows keyed anew by `scores` (0: an empty slot, or a score not above floor_excl)
+__global__ void vk_rekey_kernel(const uint64_t *__restrict__ keys, int32_t n, const float *__restrict__ scores, float floor_excl,
+	uint64_t *__restrict__ out) {
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	uint64_t key = 0;
+	if (keys[i]) {
+		const uint32_t row = (uint32_t)keys[i];
+		const float sc = scores[row];
+		if (sc > floor_excl) key = ((uint64_t)float_orderable(sc) << 32) | row;
+	}
+	out[i] = key;
+}
+
+// the k best of at most 2,048 keys in any order (one block, full sort), best first
+extern "C" hipError_t vk_launch_topk_unsorted(const uint64_t *in, int32_t n, int32_t k, uint64_t *out, hipStream_t stream) {
+	if (n > VK_TOPK_CHUNK || k > VK_TOPK_CHUNK) return hipErrorInvalidValue;
+	vk_topk_keys_kernel<<<1, 256, 0, stream>>>(in, n, k, out, 0);
+	return hipGetLastError();
+}
+
+extern "C" hipError_t vk_launch_rekey(const uint64_t *keys, int32_t n, const float *scores, float floor_excl, uint64_t *out, hipStream_t stream) {
+	if (n <= 0) return hipSuccess;
+	vk_rekey_kernel<<<(n + 255) / 256, 256, 0, stream>>>(keys, n, scores, floor_excl, out);
+	return hipGetLastError();
+}
+
+__global__ void vk_key_groups_kernel(const uint64_t *__restrict__ keys, int32_t n, int32_t *__restrict__ groups) {
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	// (an empty slot -- the selection found fewer -- repeats group 0: scored once more, the same floats)
+	groups[i] = keys[i] ? (int32_t)((uint32_t)keys[i] >> 2) : 0;
+}
+
+extern "C" hipError_t vk_launch_key_groups(const uint64_t *keys, int32_t n, int32_t *groups, hipStream_t stream) {
+	if (n <= 0) return hipSuccess;
+	vk_key_groups_kernel<<<(n + 255) / 256, 256, 0, stream>>>(keys, n, groups);
 	return hipGetLastError();
 }
 
