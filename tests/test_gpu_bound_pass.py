@@ -7,7 +7,9 @@ VK_BOUND_PASS=off (no shadow: the exact pass over every slice) -- and asserts
   (d) the counters say the bound pass ran and did not fall back to the full pass (unless the case is about the fallback).
 Shapes: 4,000 x 32 tokens (whole tiles, 1,000 groups: four workgroup rounds), 3,000 slices of 1..64 tokens with empty ones among them
 (slices across tile borders, both register-history depths), 37 slices of 1..3 tokens (fewer slices than candidates of round 1).  All
-300-d, the compile-time form of the bound kernel.  The lane map of the 8-bit MFMA is checked with exact integers.
+300-d, the compile-time form of the bound kernel; its width edges on a corpus of their own: 289, 303 and 304 features (15, one and no
+padded feature in the last half block of the exact tiles; the shadow's fifth K-step of 64 holds 33, 47 and 48 live bytes) through (a) .. (e),
+and 288 and 305 features, where no shadow may exist.  The lane map of the 8-bit MFMA is checked with exact integers.
   (e) The bound exceeds the exact score by no more than the derived delta, and round 2 holds no more slices than follows from the exact
 scores and delta (round2_limit): every case of every shape, so that a bound that got worse (a larger gamma, a coarser quantizer) fails here; on the 4,000 x 32 shape 10-token queries at
 k <= 10 also stay within 1 % of the slices.
@@ -50,7 +52,7 @@ class _Env:
 
 def _corpus(hip, X, off):
 	Xb = synth.to_bf16_bits(synth.normalize_rows(X))
-	c = hip.Corpus(layout=hip.VK_LAYOUT_CONTEXTUAL, d=D, n_tokens=Xb.shape[0], n_sentences=len(off) - 1)
+	c = hip.Corpus(layout=hip.VK_LAYOUT_CONTEXTUAL, d=Xb.shape[1], n_tokens=Xb.shape[0], n_sentences=len(off) - 1)
 	c.append_vectors(Xb, normalize=False)
 	c.set_sentences(off)
 	c.finalize()
@@ -217,6 +219,59 @@ def test_pruned_query_is_the_exact_query(hip, request, shape, len_t, gap):
 				cnt = check(hip, pair, qv, locality=locality, gap_s=gs, gap_t=gt, max_matches=k, min_score=0.0 if locality == 0 else -1e9)
 				if shape == "uniform" and len_t == 10 and k <= 10:
 					assert cnt[2] <= pair.n // 100, cnt
+
+
+def ragged_with_empties(d, n, seed):
+	"""n slices of 1..64 tokens, five of them emptied in place (first, inside a group, last)"""
+	corpus = synth.make_contextual_corpus(n - 5, 1, 64, V, d, seed=seed)
+	off = corpus["sent_off"]
+	at = np.array([0, 7, (n - 5) // 2, n - 6, n - 5])
+	corpus["sent_off"] = np.insert(off, at, off[at])
+	assert len(corpus["sent_off"]) - 1 == n and (np.diff(corpus["sent_off"]) == 0).sum() == 5
+	return corpus
+
+
+@pytest.mark.parametrize("d", (289, 303, 304))
+def test_width_edges_of_the_shadow(hip, d):
+	"""every width that builds a shadow shares the 300-d forms (d_pad = 304): the widest, with no padding in the half block, the
+	narrowest, with 15 padded features and d % 4 == 1, and one short of the widest -- every case through (a) .. (e)"""
+	pair = Pair(hip, ragged_with_empties(d, 1500, seed=50 + d))
+	try:
+		for len_t in (4, 16):
+			for qv in case_queries(pair.corpus, len_t):
+				for gap in sorted(GAPS):
+					gs, gt = GAPS[gap]
+					for locality in (0, 1):
+						check(hip, pair, qv, locality=locality, gap_s=gs, gap_t=gt, max_matches=10, min_score=0.0 if locality == 0 else -1e9)
+	finally:
+		pair.close()
+
+
+@pytest.mark.parametrize("d", (288, 305))
+def test_no_shadow_beside_its_widths(hip, d):
+	"""d_pad = 288 and d_pad = 320: VK_BOUND_PASS=force builds no shadow (the same bytes on the device as with `off`), no bound pass
+	runs, and the results are the exact pass's"""
+	corpus = ragged_with_empties(d, 1500, seed=50 + d)
+	with _Env("off"):
+		exact = _corpus(hip, corpus["X"], corpus["sent_off"])
+	with _Env("force"):
+		forced = _corpus(hip, corpus["X"], corpus["sent_off"])
+	try:
+		assert forced.device_bytes == exact.device_bytes
+		for len_t in (4, 16):
+			for qv in case_queries(corpus, len_t):
+				for gap in sorted(GAPS):
+					gs, gt = GAPS[gap]
+					kw = dict(locality=0, gap_s=gs, gap_t=gt, max_matches=10)
+					with _Env("force"):
+						got = forced.query(qv, **kw)
+						assert state(hip, forced, bounds=False)[1][0] == 0
+					with _Env("off"):
+						ref = exact.query(qv, **kw)
+					same_results(got, ref)
+	finally:
+		forced.close()
+		exact.close()
 
 
 def test_a_frequent_word_falls_back(hip, uniform):

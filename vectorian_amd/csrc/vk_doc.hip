@@ -103,11 +103,12 @@ __global__ __launch_bounds__(64) void vk_doc_kernel(VkWideParams p) {
 	// contextual scoring over bf16 rows of up to 12 K-steps: the query's A fragments in registers for the whole launch
 	constexpr int NKP = 12;
 	const int nfull = p.tail ? p.nk32 - 1 : p.nk32;
+	const int ln16 = (nfull > 0 ? lane : (lane & 31)) * 16;   // d <= 16 (nfull == 0): block 0 IS the half block, 512 bytes -- a full block's lanes 32..63 would read past the tile
 	constexpr bool regs = SRC == 0;
 	bf16x8 qf[NKP], qh = {0, 0, 0, 0, 0, 0, 0, 0};
 	if constexpr (regs) {
 #pragma unroll
-		for (int i = 0; i < NKP; i++) qf[i] = *reinterpret_cast<const bf16x8 *>(p.qtile + (i < nfull ? i : 0) * 1024 + lane * 16);
+		for (int i = 0; i < NKP; i++) qf[i] = *reinterpret_cast<const bf16x8 *>(p.qtile + (i < nfull ? i : 0) * 1024 + ln16);
 		qh = load_half_block(p.qtile + (p.tail ? nfull : 0) * 1024, lane, false);
 	}
 
@@ -175,7 +176,7 @@ __global__ __launch_bounds__(64) void vk_doc_kernel(VkWideParams p) {
 			const uint8_t *tp = p.tiles + (int64_t)k * p.tile_bytes;
 #pragma unroll
 			for (int i = 0; i < NKP; i++)   // (K-steps the row does not have re-read its first one: unconditional loads)
-				xn[i] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8 *>(tp + (i < nfull ? i : 0) * 1024 + lane * 16));
+				xn[i] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8 *>(tp + (i < nfull ? i : 0) * 1024 + ln16));
 			xh = load_half_block(tp + (p.tail ? nfull : 0) * 1024, lane, true);
 		};
 		auto tile_values = [&](int k) -> f32x4 {   // contextual: S of tile k (from the registers, or loaded here), tag weights applied

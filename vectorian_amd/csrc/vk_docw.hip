@@ -77,6 +77,7 @@ __global__ __launch_bounds__(64) void vk_docw_kernel(VkWideParams p) {
 		const int k_first = t_a >> 4, k_last = (t_b - 1) >> 4;
 		constexpr int NKP = 12;
 		const int nfull = p.tail ? p.nk32 - 1 : p.nk32;
+		const int ln16 = (nfull > 0 ? lane : (lane & 31)) * 16;   // d <= 16 (nfull == 0): block 0 IS the half block, 512 bytes -- a full block's lanes 32..63 would read past the tile
 		bf16x8 xn[SRC == 0 ? NKP : 1], xh = {0, 0, 0, 0, 0, 0, 0, 0};
 		auto tile_load = [&](int k) {   // SRC 0: the K-steps of tile k into registers
 			if constexpr (SRC == 0) {
@@ -84,7 +85,7 @@ __global__ __launch_bounds__(64) void vk_docw_kernel(VkWideParams p) {
 				const uint8_t *tp = p.tiles + (int64_t)k * p.tile_bytes;
 #pragma unroll
 				for (int i = 0; i < NKP; i++)   // (K-steps the row does not have re-read its first one: unconditional loads)
-					xn[i] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8 *>(tp + (i < nfull ? i : 0) * 1024 + lane * 16));
+					xn[i] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8 *>(tp + (i < nfull ? i : 0) * 1024 + ln16));
 				xh = load_half_block(tp + (p.tail ? nfull : 0) * 1024, lane, true);
 			}
 		};
@@ -97,7 +98,7 @@ __global__ __launch_bounds__(64) void vk_docw_kernel(VkWideParams p) {
 					const uint8_t *qb = p.qtile + (int64_t)b * p.tile_bytes;
 					bf16x8 qf[NKP];
 #pragma unroll
-					for (int i = 0; i < NKP; i++) qf[i] = *reinterpret_cast<const bf16x8 *>(qb + (i < nfull ? i : 0) * 1024 + lane * 16);
+					for (int i = 0; i < NKP; i++) qf[i] = *reinterpret_cast<const bf16x8 *>(qb + (i < nfull ? i : 0) * 1024 + ln16);
 					const bf16x8 qh = load_half_block(qb + (p.tail ? nfull : 0) * 1024, lane, false);
 #pragma unroll
 					for (int i = 0; i < NKP; i++)
@@ -534,6 +535,7 @@ __global__ __launch_bounds__(64) void vk_docg_kernel(VkWideParams p) {
 		const int k_first = t_a >> 4, k_last = (t_b - 1) >> 4;
 		constexpr int NKP = 12;
 		const int nfull = p.tail ? p.nk32 - 1 : p.nk32;
+		const int ln16 = (nfull > 0 ? lane : (lane & 31)) * 16;   // d <= 16 (nfull == 0): block 0 IS the half block, 512 bytes -- a full block's lanes 32..63 would read past the tile
 		bf16x8 xn[SRC == 0 ? NKP : 1], xh = {0, 0, 0, 0, 0, 0, 0, 0};
 		auto tile_load = [&](int k) {   // SRC 0: the K-steps of tile k into registers
 			if constexpr (SRC == 0) {
@@ -541,7 +543,7 @@ __global__ __launch_bounds__(64) void vk_docg_kernel(VkWideParams p) {
 				const uint8_t *tp = p.tiles + (int64_t)k * p.tile_bytes;
 #pragma unroll
 				for (int i = 0; i < NKP; i++)
-					xn[i] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8 *>(tp + (i < nfull ? i : 0) * 1024 + lane * 16));
+					xn[i] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8 *>(tp + (i < nfull ? i : 0) * 1024 + ln16));
 				xh = load_half_block(tp + (p.tail ? nfull : 0) * 1024, lane, true);
 			}
 		};
@@ -557,7 +559,7 @@ __global__ __launch_bounds__(64) void vk_docg_kernel(VkWideParams p) {
 						const uint8_t *qb = p.qtile + (int64_t)b * p.tile_bytes;
 						bf16x8 qf[NKP];
 #pragma unroll
-						for (int i = 0; i < NKP; i++) qf[i] = *reinterpret_cast<const bf16x8 *>(qb + (i < nfull ? i : 0) * 1024 + lane * 16);
+						for (int i = 0; i < NKP; i++) qf[i] = *reinterpret_cast<const bf16x8 *>(qb + (i < nfull ? i : 0) * 1024 + ln16);
 						const bf16x8 qh = load_half_block(qb + (p.tail ? nfull : 0) * 1024, lane, false);
 #pragma unroll
 						for (int i = 0; i < NKP; i++)

@@ -464,6 +464,7 @@ __global__ __launch_bounds__(64) void vk_wide_kernel(VkWideParams p) {
 		constexpr int NKP = 12;
 		constexpr bool PIPE = GSM == 1 && !FLOW && (GAPT == 0 || GAPT == 1 || GAPT == 4);
 		const int nfull = p.tail ? p.nk32 - 1 : p.nk32;
+		const int ln16 = (nfull > 0 ? lane : (lane & 31)) * 16;   // d <= 16 (nfull == 0): block 0 IS the half block, 512 bytes -- a full block's lanes 32..63 would read past the tile
 		const bool pipe = PIPE && !is_static && p.prec == 0 && p.nk32 <= NKP;
 		bf16x8 xn[NKP], xh = {0, 0, 0, 0, 0, 0, 0, 0};
 		auto tile_load = [&](int base) {
@@ -471,7 +472,7 @@ __global__ __launch_bounds__(64) void vk_wide_kernel(VkWideParams p) {
 				const uint8_t *tp = p.tiles + (int64_t)(base >> 4) * p.tile_bytes;
 #pragma unroll
 				for (int i = 0; i < NKP; i++)   // (K-steps the row does not have re-read its first one: unconditional loads, no copies of xn kept alive)
-					xn[i] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8 *>(tp + (i < nfull ? i : 0) * 1024 + lane * 16));
+					xn[i] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8 *>(tp + (i < nfull ? i : 0) * 1024 + ln16));
 				xh = load_half_block(tp + (p.tail ? nfull : 0) * 1024, lane, true);
 			}
 		};
