@@ -229,6 +229,7 @@ static int query_batch_shared_pass(vk_corpus_t *c, const vk_query_desc *qs, int3
 	if (const char *e = getenv("VK_BATCH_QB")) qb_max = std::max(2, std::min(4, atoi(e)));   // tuning aid
 	while (qb_max > 1 && smem_of(qb_max) > 160 * 1024) qb_max--;
 	if (qb_max < 2) return VK_ERR_UNSUPPORTED;
+	c->batch_state[VK_BS_ROUTE] = 2; c->batch_state[VK_BS_QB_MAX] = qb_max; c->batch_state[VK_BS_LT] = lt; c->batch_state[VK_BS_GAP_MODE] = p.gap_mode;
 	p.n_strips = qb_max;
 	p.lds_floats_per_wave = qb_max * strip + hist;
 	auto smem_for = [&](int qb) { return (size_t)qb * c->tile_bytes + (size_t)p.lds_floats_per_wave * 4 * 4; };
@@ -411,6 +412,8 @@ static int build_batch_layout(vk_corpus *c, int gran) {
 // Every host buffer that is the source or the destination of an asynchronous copy lives in `keep` (owned by vk_query_batch below,
 // which drains the stream before the buffers die when this body fails or is aborted: vk_guard.h).
 static int query_batch_body(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_queries, vk_topk_out *outs, vk_host_keep &keep) {
+	// what the last batch recorded is forgotten: each route below states its own
+	std::fill(std::begin(c->batch_state), std::end(c->batch_state), (int64_t)0);
 	// the GEMM path: injective RWMD, contextual layout, one sentence length (multiple of 16), common options
 	// (uniform corpora of 16 / 32 / 48 / 64-token sentences run on the resident tiles; any other corpus of slices of at most 64
 	// tokens on a padded copy, bucket by bucket)
@@ -438,6 +441,7 @@ static int query_batch_body(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_q
 	if (!gemm) {
 		const int rcb = query_batch_shared_pass(c, qs, n_queries, outs, keep);
 		if (rcb != VK_ERR_UNSUPPORTED) return rcb;
+		c->batch_state[VK_BS_ROUTE] = 1;
 		for (int i = 0; i < n_queries; i++) {
 			const int rc = vk_query(c, &qs[i], &outs[i]);   // polls the query's abort flag
 			if (rc) {
@@ -600,6 +604,12 @@ static int query_batch_body(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_q
 	p.n_qtiles = n_qtiles; p.qpt = qpt; p.q_inv_len = d_qinv; p.q_param = d_qparam; p.dense = dense ? 1 : 0;
 	p.late_mask = wide32 ? 0 : 4;   // waves w and w + 4 of a workgroup share a SIMD (768-d rows: one wave per SIMD, nobody to alternate with)
 	if (const char *e = getenv("VK_BATCH32_LATE_MASK")) p.late_mask = atoi(e);   // tuning aid
+	{
+		int64_t *st = c->batch_state;
+		st[VK_BS_ROUTE] = 3; st[VK_BS_STAT] = stat; st[VK_BS_STAT_UNIFORM32] = stat_uniform32; st[VK_BS_UNIFORM16] = uniform16;
+		st[VK_BS_B32] = b32; st[VK_BS_R32] = r32; st[VK_BS_GRAN] = gran; st[VK_BS_WIDE32] = wide32; st[VK_BS_DENSE] = dense;
+		st[VK_BS_QPT] = qpt; st[VK_BS_N_QTILES] = n_qtiles; st[VK_BS_UNIFORM_LEN] = c->uniform_len; st[VK_BS_LATE_MASK] = p.late_mask;
+	}
 	if (stat) {
 		// ---- the static layout: table of the batch over the vocabulary, its diagonal cells, then the gather pass per length bucket
 		const int64_t v_rows = (int64_t)((c->n_tiles + 1) / 2) * 32;

@@ -613,6 +613,14 @@ int vk_bound_pass_state(vk_corpus_t *c, float *bounds, int64_t n, int64_t *count
 	return VK_OK;
 }
 
+// Internal (tests; not part of the ABI): which route the last vk_query_batch on this handle took and in which form -- state[VK_BS_COUNT]
+// in the order of vk_batch_state_index (all zero: no batch yet)
+int vk_batch_state(vk_corpus_t *c, int64_t *state) {
+	if (!c || !state) return fail(VK_ERR_INVALID, "null argument");
+	memcpy(state, c->batch_state, sizeof c->batch_state);
+	return VK_OK;
+}
+
 // Internal (tests): one v_mfma_i32_16x16x64_i8 on 16 x 64 int8 query rows and 16 x 64 int8 token rows (host, row-major), packed as
 // the shadow packs its blocks: out[16 j + i] = q[j] . x[i]
 int vk_i8_tile_probe(const int8_t *q, const int8_t *x, int32_t *out) {

@@ -136,6 +136,16 @@ struct vk_corpus_shape {
 	float shadow_n = 0.0f, shadow_x = 0.0f;
 };
 
+// vk_corpus::batch_state by index (the internal export vk_batch_state hands the array out in this order; the tests name the
+// entries in the same order).  Route: 1 query by query, 2 the shared pass, 3 the GEMM pass.
+enum vk_batch_state_index {
+	VK_BS_ROUTE,
+	VK_BS_QB_MAX, VK_BS_LT, VK_BS_GAP_MODE,                                                     // the shared pass
+	VK_BS_STAT, VK_BS_STAT_UNIFORM32, VK_BS_UNIFORM16, VK_BS_B32, VK_BS_R32, VK_BS_GRAN,        // the GEMM pass
+	VK_BS_WIDE32, VK_BS_DENSE, VK_BS_QPT, VK_BS_N_QTILES, VK_BS_UNIFORM_LEN, VK_BS_LATE_MASK,
+	VK_BS_COUNT
+};
+
 // The handle: the shape above and what is this handle's alone.  Every workspace is a vk_devbuf (vk_devbuf.h): sized by reserve() where
 // it is needed, counted in device_bytes while it lives, freed with the handle.
 struct vk_corpus : vk_corpus_shape {
@@ -189,6 +199,9 @@ struct vk_corpus : vk_corpus_shape {
 	vk_devbuf<int64_t> d_bfix;
 	vk_devbuf<int32_t> d_bqids;   // token ids of a batch's queries, 16 per query (the winners' rows: sim[id(t_j)][j] = 1)
 	vk_devbuf<uint64_t> d_sort[2]; vk_devbuf<uint8_t> d_sort_temp;   // result sets beyond VK_MAX_MATCHES: all keys, sorted
+	// route and form of the last vk_query_batch on this handle (vk_batch_state in vk_corpus.cpp, for the tests; host integers only),
+	// addressed by VK_BS_*: the route, then the shared pass's three, then the GEMM pass's twelve
+	int64_t batch_state[VK_BS_COUNT] = {};
 	hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // 0 start, 5 before / 1 after the wait for the peer's kernel, 2 scored (the peer's turn), 3 selected, 4 done; 6: the batched GEMM has ended (its turn ends after the selection)
 	vk_timings last{};
 	bool have_scores = false;
