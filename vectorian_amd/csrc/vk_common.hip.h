@@ -199,15 +199,45 @@ __device__ __forceinline__ f32x4 sim_tile_qlds(const uint8_t *__restrict__ qlds,
 // read per K-step / per tile like MODE 3's: in registers they took the kernel with general gaps to 160 VGPRs, three waves per SIMD
 // then leave 32 and no neighbour kernel (the rounds, the peer's selection and traceback) finds room beside it; from LDS, and under the
 // budget of vk_score_m7.hip, 110 .. 122 by query width (the figures are there).
+//
+// `live` (wave-uniform, 1 .. 4): the 16-lane quarters of the LAST block that hold features, ceil((d - 64 (NK - 1)) / 16).  Lanes
+// >= 16 live issue no load for that block and feed the MFMA a zero register instead.  Exact: vk_shadow_kernel writes zeros for every
+// feature past d, so the bytes not fetched are zeros, and 0 * q = 0 whatever the query tile holds there (vk_pack_query leaves zeros
+// too).  300-d rows: live = 3, 256 of a tile's 5,248 bytes (two whole 128-byte lines) are never requested.
+// At most VK_I8_STEPS blocks are in flight: the five of the 300-d form all at once as before; twelve (768-d) in two batches of six
+// that DRAIN -- the first batch's loads are waited for in full (vmcnt(0)) and consumed before the second batch is issued, the scheduling
+// barriers keep the compiler from hoisting the second batch (registers).  Not a rolling pipeline: between the batches a wave has no
+// load in flight, the other waves of the CU cover it (6.4 TB/s at two workgroups per CU).
+#define VK_I8_STEPS 6
 template <int NK>
-__device__ __forceinline__ f32x4 sim_tile_i8(const uint8_t *__restrict__ qlds, const uint8_t *__restrict__ tile, int lane) {
-	i32x4 x[NK > 0 ? NK : 1];
-#pragma unroll
-	for (int t = 0; t < NK; t++) x[t] = __builtin_nontemporal_load(reinterpret_cast<const i32x4 *>(tile + t * 1024 + lane * 16));
-	const f32x2 m = __builtin_nontemporal_load(reinterpret_cast<const f32x2 *>(tile + NK * 1024 + (lane & 15) * 8));   // (s_x, e_x) of the lane's token
+__device__ __forceinline__ i32x4 dot_tile_i8(const uint8_t *__restrict__ qlds, const uint8_t *__restrict__ tile, int lane, int live) {
+	constexpr int CH = NK <= VK_I8_STEPS ? NK : VK_I8_STEPS;
+	static_assert(NK >= 1 && NK % CH == 0, "whole batches of K-steps");
 	i32x4 acc = {0, 0, 0, 0};
 #pragma unroll
-	for (int t = 0; t < NK; t++) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(*reinterpret_cast<const i32x4 *>(qlds + t * 1024 + lane * 16), x[t], acc, 0, 0, 0);
+	for (int t0 = 0; t0 < NK; t0 += CH) {
+		i32x4 x[CH];
+#pragma unroll
+		for (int i = 0; i < CH; i++) {
+			const i32x4 *src = reinterpret_cast<const i32x4 *>(tile + (t0 + i) * 1024 + lane * 16);
+			if (t0 + i == NK - 1) {
+				x[i] = i32x4{0, 0, 0, 0};
+				if (lane < 16 * live) x[i] = __builtin_nontemporal_load(src);
+			} else x[i] = __builtin_nontemporal_load(src);
+		}
+		if constexpr (NK > CH) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+		for (int i = 0; i < CH; i++)
+			acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(*reinterpret_cast<const i32x4 *>(qlds + (t0 + i) * 1024 + lane * 16), x[i], acc, 0, 0, 0);
+		if constexpr (NK > CH) __builtin_amdgcn_sched_barrier(0);
+	}
+	return acc;
+}
+
+template <int NK>
+__device__ __forceinline__ f32x4 sim_tile_i8(const uint8_t *__restrict__ qlds, const uint8_t *__restrict__ tile, int lane, int live) {
+	const f32x2 m = __builtin_nontemporal_load(reinterpret_cast<const f32x2 *>(tile + NK * 1024 + (lane & 15) * 8));   // (s_x, e_x) of the lane's token
+	const i32x4 acc = dot_tile_i8<NK>(qlds, tile, lane, live);
 	const float *cst = reinterpret_cast<const float *>(qlds + NK * 1024) + (lane >> 4) * 4;
 	const f32x4 cs = *reinterpret_cast<const f32x4 *>(cst), ca = *reinterpret_cast<const f32x4 *>(cst + 16), cb = *reinterpret_cast<const f32x4 *>(cst + 32);
 	f32x4 ub;

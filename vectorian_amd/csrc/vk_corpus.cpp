@@ -429,15 +429,18 @@ int vk_corpus_set_slices(vk_corpus_t *c, const int64_t *start, const int64_t *en
 	return set_slices_impl(c, start, end, n_sentences, false);
 }
 
-// The 8-bit shadow of the token rows: contextual bf16 rows of 289 .. 304 features (d_pad = 304: the exact kernel's 300-d
-// specialisation rescores the contenders, the form every test and measurement runs),
+// The 8-bit shadow of the token rows: contextual bf16 rows whose exact kernel is one of the two compile-time forms that
+// rescore the contenders -- 289 .. 304 features (d_pad = 304, the 300-d form: five K-steps of 64 int8, 5,248 bytes per tile) and
+// 753 .. 768 features (d_pad = 768, the 768-d form: twelve K-steps, 12,416 bytes per tile) --
 // every slice within VK_FAST_SENT_LEN tokens.  Never an error: without the memory (or with a row that is not finite) the corpus has
 // no shadow and its queries take the exact pass.
 static void build_shadow(vk_corpus *c) {
 	const int mode = bound_pass_mode();
 	if (mode < 0 || (mode == 0 && c->desc.n_sentences < kBoundPassMinSentences)) return;
-	if (c->desc.layout != VK_LAYOUT_CONTEXTUAL || c->prec != 0 || c->nk32 != 10 || c->tail != 1 || c->max_len > VK_FAST_SENT_LEN || c->n_entries < 1) return;
-	const int nk64 = 5, tile_bytes = nk64 * 1024 + 128;
+	if (c->desc.layout != VK_LAYOUT_CONTEXTUAL || c->prec != 0 || c->max_len > VK_FAST_SENT_LEN || c->n_entries < 1) return;
+	const int nk64 = (c->nk32 == 10 && c->tail == 1) ? 5 : (c->nk32 == 24 && c->tail == 0) ? 12 : 0;
+	if (nk64 == 0) return;
+	const int tile_bytes = nk64 * 1024 + 128;
 	const size_t bytes = (size_t)c->n_tiles * tile_bytes;
 	uint8_t *sh = nullptr;
 	if (c->d_counter.reserve(4, &c->device_bytes) || alloc_shared(c, &sh, bytes)) { (void)hipGetLastError(); return; }
@@ -451,6 +454,7 @@ static void build_shadow(vk_corpus *c) {
 		return;
 	}
 	c->shadow = sh; c->shadow_nk64 = nk64; c->shadow_tile_bytes = tile_bytes;
+	c->shadow_live = (c->desc.d - 64 * (nk64 - 1) + 15) / 16;   // 1 .. 4 (d_pad - 15 <= d <= d_pad for both forms)
 	memcpy(&c->shadow_n, &stats[0], 4);
 	memcpy(&c->shadow_x, &stats[1], 4);
 }
@@ -633,6 +637,28 @@ int vk_i8_tile_probe(const int8_t *q, const int8_t *x, int32_t *out) {
 	VK_HIP(vk_launch_i8_probe((const int8_t *)d, (const int8_t *)d + 1024, (int32_t *)(d + 2048), nullptr));
 	VK_HIP(hipDeviceSynchronize());
 	VK_HIP(hipMemcpy(out, d + 2048, 1024, hipMemcpyDeviceToHost));
+	return VK_OK;
+}
+
+// Internal (tests): one shadow tile of nk64 K-steps (5 or 12) through the bound kernel's own product (dot_tile_i8, vk_common.hip.h) with
+// `live` quarters of the last block fetched.  q, x: 16 rows x 64 nk64 int8 each (host, row-major), packed as the shadow packs its
+// blocks: out[16 j + i] = q[j] . x[i] over the features the kernel reads
+int vk_i8_bound_tile_probe(const int8_t *q, const int8_t *x, int32_t nk64, int32_t live, int32_t *out) {
+	if (!q || !x || !out) return fail(VK_ERR_INVALID, "null argument");
+	if ((nk64 != 5 && nk64 != 12) || live < 1 || live > 4) return fail(VK_ERR_INVALID, "nk64 is 5 or 12, live 1 .. 4");
+	const size_t tb = (size_t)nk64 * 1024;
+	vk_devbuf<uint8_t> buf;
+	if (int rc = buf.reserve(2 * tb + 1024, nullptr)) return rc;
+	uint8_t *d = buf;
+	std::vector<uint8_t> pk(2 * tb);
+	for (int side = 0; side < 2; side++)
+		for (int i = 0; i < 16; i++)
+			for (int k = 0; k < nk64 * 64; k++)
+				pk[side * tb + (size_t)(k >> 6) * 1024 + (size_t)(((k & 63) >> 4) * 16 + i) * 16 + (size_t)(k & 15)] = (uint8_t)(side ? x : q)[(size_t)i * nk64 * 64 + k];
+	VK_HIP(hipMemcpy(d, pk.data(), 2 * tb, hipMemcpyHostToDevice));
+	VK_HIP(vk_launch_i8_bound_probe(d, d + tb, nk64, live, (int32_t *)(d + 2 * tb), nullptr));
+	VK_HIP(hipDeviceSynchronize());
+	VK_HIP(hipMemcpy(out, d + 2 * tb, 1024, hipMemcpyDeviceToHost));
 	return VK_OK;
 }
 

@@ -35,6 +35,7 @@ struct VkScoreParams {
 	int32_t q_lds;             // MODE 1: bytes of the query tile staged at the start of the dynamic LDS (0: read through L1 / L2)
 	int32_t bound_i8;          // 1: `tiles` is the 8-bit shadow (nk32 K-steps of 64 int8, tile_bytes = nk32 KiB + 128) and `qtile` its query tile
 	                           // with the cells' constants behind it: scores are upper bounds (MODE 7)
+	int32_t bound_live;        // MODE 7: the 16-lane quarters of a shadow tile's last block that hold features (1 .. 4); the rest is not fetched
 	int32_t q_mode3;           // 300-d bf16 rows: 1 = query tile in LDS (MODE 3, 136 VGPRs with general gaps), 0 = in registers (MODE 0, 160);
 	                           // 300-d fp32 rows: 1 = the specialised form (MODE 4), 0 = the generic loop (MODE 1)
 	const int32_t *group_list; // null: all groups of 4 slices; else the groups holding one long slice each (64-thread blocks)
@@ -347,6 +348,8 @@ int32_t vk_wide_ring_rows(int32_t nq, int32_t gap_mode, int32_t ws_tail);
 // the 8-bit shadow of a bf16 contextual corpus (vk_pack.hip): stats = 4 words (largest |s xq|, largest |x| as float bits; not finite)
 hipError_t vk_launch_shadow(const uint8_t *tiles, int64_t n_tiles, int64_t rows_total, int32_t d, int32_t tile_bytes, int32_t nk64,
 	uint8_t *shadow, uint32_t *stats, hipStream_t stream);
+// one shadow tile through dot_tile_i8<nk64> (5 or 12) with `live` quarters of the last block fetched: out[16 j + i] (vk_pack.hip; tests)
+hipError_t vk_launch_i8_bound_probe(const uint8_t *qtile8, const uint8_t *tile8, int32_t nk64, int32_t live, int32_t *out, hipStream_t stream);
 hipError_t vk_launch_i8_probe(const int8_t *q, const int8_t *x, int32_t *out, hipStream_t stream);
 // rows of the keys (up to the first empty slot of `n`) as groups of four rows of the slice table (vk_score_kernel's group_list)
 // theta on the device: the score of *theta_key (floor_excl when that slot is empty)

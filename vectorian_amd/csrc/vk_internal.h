@@ -133,6 +133,7 @@ struct vk_corpus_shape {
 	// shadow_tile_bytes, and the corpus-wide constants of the bound -- shadow_n >= every |s_x xq|, shadow_x >= every |x|
 	const uint8_t *shadow = nullptr;
 	int shadow_nk64 = 0, shadow_tile_bytes = 0;
+	int shadow_live = 4;   // quarters of a tile's last block that hold features: ceil((d - 64 (shadow_nk64 - 1)) / 16); the bound kernel fetches only those
 	float shadow_n = 0.0f, shadow_x = 0.0f;
 };
 

@@ -161,6 +161,27 @@ extern "C" hipError_t vk_launch_i8_probe(const int8_t *q, const int8_t *x, int32
 	return hipGetLastError();
 }
 
+// One shadow tile against one 8-bit query tile, both in the shadow's block order already, through the bound kernel's own product:
+// the query tile staged in LDS as MODE 7 stages it, dot_tile_i8<NK> with `live` quarters of the last block fetched
+// (tests/test_gpu_bound_live_bytes.py: the bytes of the dead quarters must not reach the product).
+template <int NK>
+__global__ __launch_bounds__(64) void vk_i8_bound_probe_kernel(const uint8_t *__restrict__ qtile8, const uint8_t *__restrict__ tile8, int32_t live,
+	int32_t *__restrict__ out) {
+	__shared__ float4 qlds4[NK * 64];
+	const int lane = threadIdx.x;
+	for (int i = lane; i < NK * 64; i += 64) qlds4[i] = *reinterpret_cast<const float4 *>(qtile8 + i * 16);
+	__syncthreads();
+	const i32x4 acc = dot_tile_i8<NK>(reinterpret_cast<const uint8_t *>(qlds4), tile8, lane, live);
+	for (int r = 0; r < 4; r++) out[(4 * (lane >> 4) + r) * 16 + (lane & 15)] = acc[r];
+}
+extern "C" hipError_t vk_launch_i8_bound_probe(const uint8_t *qtile8, const uint8_t *tile8, int32_t nk64, int32_t live, int32_t *out, hipStream_t stream) {
+	if (live < 1 || live > 4) return hipErrorInvalidValue;
+	if (nk64 == 5) vk_i8_bound_probe_kernel<5><<<1, 64, 0, stream>>>(qtile8, tile8, live, out);
+	else if (nk64 == 12) vk_i8_bound_probe_kernel<12><<<1, 64, 0, stream>>>(qtile8, tile8, live, out);
+	else return hipErrorInvalidValue;
+	return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------
 // static layout: per-query similarity table [V_pad x 16] (metric/static.cpp:9-78)
 // ---------------------------------------------------------------------------

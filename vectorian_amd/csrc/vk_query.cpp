@@ -222,7 +222,7 @@ static int score_bounded(vk_corpus *c, const VkScoreParams &p, int grid, size_t 
 	if ((rc = c->d_bound_keys.reserve((size_t)2 * kTopkChunk, &c->device_bytes))) return rc;
 	if ((rc = c->d_counter.reserve(4, &c->device_bytes))) return rc;
 	VkScoreParams pb = p;
-	pb.tiles = c->shadow; pb.nk32 = c->shadow_nk64; pb.tail = 0; pb.tile_bytes = c->shadow_tile_bytes; pb.bound_i8 = 1;
+	pb.tiles = c->shadow; pb.nk32 = c->shadow_nk64; pb.tail = 0; pb.tile_bytes = c->shadow_tile_bytes; pb.bound_i8 = 1; pb.bound_live = c->shadow_live;
 	pb.q_mode3 = 0; pb.q_lds = 0; pb.qtile = c->d_qtile8; pb.scores = c->d_ub; pb.raw = nullptr;
 	VK_HIP(vk_launch_score(&pb, grid, smem_bound, st));
 	VK_HIP(hipEventRecord(c->ev[2], st));

@@ -180,7 +180,7 @@ __global__ __launch_bounds__(256) VK_SCORE_KERNEL_ATTR void vk_score_kernel(VkSc
 				if constexpr (MODE == 0) acc = sim_tile<NK32, TAIL>(qf, tp, lane);
 				else if constexpr (MODE == 3) acc = sim_tile_qlds<NK32, TAIL>(qlds, tp, lane);
 				else if constexpr (MODE == 4) acc = sim_tile_f32_qlds<NK32>(qlds, tp, lane);
-				else if constexpr (MODE == 7) acc = sim_tile_i8<NK32>(qlds, tp, lane);
+				else if constexpr (MODE == 7) acc = sim_tile_i8<NK32>(qlds, tp, lane, p.bound_live);
 				else {
 					// two calls, not one with a selected pointer: an LDS-or-global pointer is a flat pointer, and flat loads count
 					// on both wait counters -- every batch of tile loads would be waited for in full
@@ -316,6 +316,7 @@ static hipError_t launch_sized(K kernel, const VkScoreParams &p, int want_blocks
 	const bool dp_bound = p.layout == VK_DEV_LAYOUT_STATIC || (p.nk32 <= 3 && !p.bound_i8);
 	// the 8-bit shadow (MODE 7, 328-byte rows; 1 M x 32 tokens, general gaps): 1.58 - 1.61 ms at 3 per CU, 1.60 - 1.65 at 4, 1.70 at 5, 1.80 at 2 --
 	// and three waves per SIMD of its 120 VGPRs leave room for the rounds' exact kernel beside it (vk_score_m7.hip)
+	// the 12-step shadow (768-d rows, 1 M slices of 8 .. 64 tokens, 64-row history): LDS and registers admit two per CU -- 4.40 ms; one: 5.98 ms
 	const int stream_cap = (!p.bound_i8 && p.nk32 >= 5 && p.nk32 <= 7) ? 4 : 3;
 	if (occ > stream_cap && !dp_bound && !bound_pass) occ = stream_cap;   // the static layout is DP-bound, not a stream: keep full residency
 	// 768-d rows: a wave already keeps 24 KiB of loads in flight per tile; one workgroup per CU measured fastest

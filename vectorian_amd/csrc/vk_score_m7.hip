@@ -7,18 +7,27 @@
 // one this was measured on.  Without the budget the 12-column form allocated 128 (118 + 4 AGPRs for the MFMA result), three waves left
 // 128, and the exact kernel waited for the peer's whole bound pass (1.47 ms in the trace).  13 - 16 query tokens: 122 allocates 128 with
 // the budget too, so there the rescoring waits its turn behind the peer's bound pass; results are the same, the overlap is lost.
+// The twelve-step form (768-d rows) takes 117 / 121 / 125 / 125 under the same budget: from 8 columns on it allocates 128 like the
+// 16-column form above (DESIGN 11.3 has the whole table).
 #define VK_SCORE_VGPRS 120
 #include "vk_score.hip.h"
 
-// 257 .. 320 features (five K-steps of 64 int8); alignments over slices of at most 64 tokens only: the gap modes of the main launch
+// 289 .. 304 features (five K-steps of 64 int8) and 753 .. 768 (twelve, two batches of six in flight: dot_tile_i8); alignments over
+// slices of at most 64 tokens only: the gap modes of the main launch
 extern "C" hipError_t vk_launch_score_m7w(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
-extern "C" hipError_t vk_launch_score_m7(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream) {
-	if (p->nk32 != 5) return hipErrorInvalidValue;
+template <int NK64>
+static hipError_t launch_m7(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream) {
 	switch (p->gap_mode) {
-	case 0: return launch_score_lt<7, 5, false, 0>(*p, grid, smem_bytes, stream);
-	case 1: return launch_score_lt<7, 5, false, 1>(*p, grid, smem_bytes, stream);
-	case 3: return launch_score_lt<7, 5, false, 3>(*p, grid, smem_bytes, stream);
+	case 0: return launch_score_lt<7, NK64, false, 0>(*p, grid, smem_bytes, stream);
+	case 1: return launch_score_lt<7, NK64, false, 1>(*p, grid, smem_bytes, stream);
+	case 3: return launch_score_lt<7, NK64, false, 3>(*p, grid, smem_bytes, stream);
 	case 6: return vk_launch_score_m7w(p, grid, smem_bytes, stream);
 	default: return hipErrorInvalidValue;
 	}
+}
+extern "C" hipError_t vk_launch_score_m7(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream) {
+	if (p->bound_live < 1 || p->bound_live > 4) return hipErrorInvalidValue;
+	if (p->nk32 == 5) return launch_m7<5>(p, grid, smem_bytes, stream);
+	if (p->nk32 == 12) return launch_m7<12>(p, grid, smem_bytes, stream);
+	return hipErrorInvalidValue;
 }

@@ -3,5 +3,6 @@
 #include "vk_score.hip.h"
 
 extern "C" hipError_t vk_launch_score_m7w(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream) {
+	if (p->nk32 == 12) return launch_score_lt<7, 12, false, 6>(*p, grid, smem_bytes, stream);
 	return launch_score_lt<7, 5, false, 6>(*p, grid, smem_bytes, stream);
 }
