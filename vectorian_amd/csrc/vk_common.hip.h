@@ -246,6 +246,69 @@ __device__ __forceinline__ f32x4 sim_tile_i8(const uint8_t *__restrict__ qlds, c
 	return ub;
 }
 
+// The 6-bit bound pass (MODE 8): the shadow holds E2M3 codes, the product is v_mfma_scale_f32_16x16x128_f8f6f4 with
+// both formats E2M3 (cbsz = blgp = 2) and both E8M0 scales 127 (x 1).  Lane l holds token l & 15 and K elements 32 (l >> 4) + j,
+// j = 0 .. 31, code j at bits 6 j .. 6 j + 5 of six registers; a K-step of 128 features is stored as a 1 KiB part (each lane's first
+// four registers, one dwordx4 per lane) and a 512-byte part (its last two, one dwordx2): both loads contiguous across the wave.
+// Every product of two grid values is a multiple of 1 / 64 and |sum| <= 384 * 56.25: at most 21 significant bits, exact in fp32 in any
+// order (tests/test_gpu_bound6_product.py holds 64 x the result against the integer product, cell for cell).
+// The last K-step of a corpus tile keeps `live6` 16-lane quarters (both parts that much shorter): lanes >= 16 live6 issue no load and
+// feed zeros, whatever the query tile (every K-step whole, in LDS) holds there.  All loads go up front: 4.5 KiB at most per wave.
+typedef __attribute__((ext_vector_type(8))) int i32x8;
+typedef __attribute__((ext_vector_type(2))) int i32x2;
+__device__ __forceinline__ i32x8 fp6_operand(const i32x4 lo, const i32x2 hi) {
+	return i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], 0, 0};
+}
+template <bool META = false>
+__device__ __forceinline__ f32x4 dot_tile_fp6(const uint8_t *__restrict__ qlds, const uint8_t *__restrict__ tile, int lane, int live6, f32x2 *meta = nullptr) {
+	i32x4 lo[VK_DEV_FP6_STEPS];
+	i32x2 hi[VK_DEV_FP6_STEPS];
+	// The lane's offsets and the scale operand are made anew for every tile (the empty asm hides that they never change): hoisted out
+	// of the kernel's loops they stay live through the DP and the 12-column form with general gaps takes 123 registers, past the
+	// budget of 120 (vk_score_m8.hip).  Three VALU instructions per tile.
+	uint32_t o16 = (uint32_t)lane * 16u;
+	asm volatile("" : "+v"(o16));
+	const uint32_t o8 = o16 >> 1;
+	int one = 0x7f7f7f7f;   // E8M0 127 in every byte: x 1
+	asm volatile("" : "+v"(one));
+#pragma unroll
+	for (int t = 0; t < VK_DEV_FP6_STEPS; t++) {
+		const uint8_t *step = tile + t * VK_DEV_FP6_STEP_BYTES;
+		if (t == VK_DEV_FP6_STEPS - 1) {
+			lo[t] = i32x4{0, 0, 0, 0}; hi[t] = i32x2{0, 0};
+			if (lane < 16 * live6) {
+				lo[t] = __builtin_nontemporal_load(reinterpret_cast<const i32x4 *>(step + o16));
+				hi[t] = __builtin_nontemporal_load(reinterpret_cast<const i32x2 *>(step + live6 * 256 + o8));
+			}
+		} else {
+			lo[t] = __builtin_nontemporal_load(reinterpret_cast<const i32x4 *>(step + o16));
+			hi[t] = __builtin_nontemporal_load(reinterpret_cast<const i32x2 *>(step + 1024 + o8));
+		}
+	}
+	// (s_x, e_x) of the lane's token, behind the tile's own loads and in front of the MFMAs that wait for them
+	if constexpr (META) *meta = __builtin_nontemporal_load(reinterpret_cast<const f32x2 *>(tile + (VK_DEV_FP6_TILE_BYTES(live6) - 128) + (lane & 15) * 8));
+	f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+	for (int t = 0; t < VK_DEV_FP6_STEPS; t++) {
+		const uint8_t *qs = qlds + t * VK_DEV_FP6_STEP_BYTES;
+		const i32x8 q = fp6_operand(*reinterpret_cast<const i32x4 *>(qs + o16), *reinterpret_cast<const i32x2 *>(qs + 1024 + o8));
+		acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(q, fp6_operand(lo[t], hi[t]), acc, 2, 2, 0, one, 0, one);
+	}
+	return acc;
+}
+
+// the cell is sim_tile_i8's with the MFMA's float in place of (float) I; the 16 x (s_x, e_x) follow the tile's K-steps
+__device__ __forceinline__ f32x4 sim_tile_fp6(const uint8_t *__restrict__ qlds, const uint8_t *__restrict__ tile, int lane, int live6) {
+	f32x2 m;
+	const f32x4 acc = dot_tile_fp6<true>(qlds, tile, lane, live6, &m);
+	const float *cst = reinterpret_cast<const float *>(qlds + VK_DEV_FP6_QTILE_BYTES) + (lane >> 4) * 4;
+	const f32x4 cs = *reinterpret_cast<const f32x4 *>(cst), ca = *reinterpret_cast<const f32x4 *>(cst + 16), cb = *reinterpret_cast<const f32x4 *>(cst + 32);
+	f32x4 ub;
+#pragma unroll
+	for (int r = 0; r < 4; r++) ub[r] = clip01(((m[0] * cs[r]) * acc[r] + m[1] * ca[r]) + cb[r]);
+	return ub;
+}
+
 // fp32 unit rows (VK_PREC_F32, the reference's own precision), NB16 blocks of 16 features known at compile time: all the
 // tile's loads are issued up front (NB16 KiB in flight per wave, as the bf16 form keeps its whole tile in flight; the generic
 // loop below holds 4 KiB), the query tile is read from LDS block by block, four v_mfma_f32_16x16x4_f32 per block -- exact fp32

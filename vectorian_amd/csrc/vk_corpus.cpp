@@ -438,14 +438,20 @@ static void build_shadow(vk_corpus *c) {
 	const int mode = bound_pass_mode();
 	if (mode < 0 || (mode == 0 && c->desc.n_sentences < kBoundPassMinSentences)) return;
 	if (c->desc.layout != VK_LAYOUT_CONTEXTUAL || c->prec != 0 || c->max_len > VK_FAST_SENT_LEN || c->n_entries < 1) return;
-	const int nk64 = (c->nk32 == 10 && c->tail == 1) ? 5 : (c->nk32 == 24 && c->tail == 0) ? 12 : 0;
+	int nk64 = (c->nk32 == 10 && c->tail == 1) ? 5 : (c->nk32 == 24 && c->tail == 0) ? 12 : 0;
 	if (nk64 == 0) return;
-	const int tile_bytes = nk64 * 1024 + 128;
+	// the 300-d form in six bits: three K-steps of 128 E2M3 codes, of the last only the quarters of 32 that hold features
+	const bool six = nk64 == 5 && bound_bits_wanted(mode) == 6;
+	const int live6 = (c->desc.d - 128 * (VK_DEV_FP6_STEPS - 1) + 31) / 32;   // 2 for 289 .. 304 features
+	if (six) nk64 = VK_DEV_FP6_STEPS;
+	const int tile_bytes = six ? VK_DEV_FP6_TILE_BYTES(live6) : nk64 * 1024 + 128;
 	const size_t bytes = (size_t)c->n_tiles * tile_bytes;
 	uint8_t *sh = nullptr;
 	if (c->d_counter.reserve(4, &c->device_bytes) || alloc_shared(c, &sh, bytes)) { (void)hipGetLastError(); return; }
 	uint32_t stats[4] = {0, 0, 1, 0};
-	const bool ran = vk_launch_shadow(c->d_tiles, c->n_tiles, c->rows_total, c->desc.d, c->tile_bytes, nk64, sh, c->d_counter, c->stream) == hipSuccess
+	const hipError_t launched = six ? vk_launch_shadow6(c->d_tiles, c->n_tiles, c->rows_total, c->desc.d, c->tile_bytes, live6, sh, c->d_counter, c->stream)
+		: vk_launch_shadow(c->d_tiles, c->n_tiles, c->rows_total, c->desc.d, c->tile_bytes, nk64, sh, c->d_counter, c->stream);
+	const bool ran = launched == hipSuccess
 		&& hipMemcpyAsync(stats, c->d_counter, 16, hipMemcpyDeviceToHost, c->stream) == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;
 	if (!ran || stats[2] != 0) {
 		(void)hipGetLastError();
@@ -454,7 +460,8 @@ static void build_shadow(vk_corpus *c) {
 		return;
 	}
 	c->shadow = sh; c->shadow_nk64 = nk64; c->shadow_tile_bytes = tile_bytes;
-	c->shadow_live = (c->desc.d - 64 * (nk64 - 1) + 15) / 16;   // 1 .. 4 (d_pad - 15 <= d <= d_pad for both forms)
+	c->shadow_bits = six ? 6 : 8;
+	c->shadow_live = six ? live6 : (c->desc.d - 64 * (nk64 - 1) + 15) / 16;   // 1 .. 4 (d_pad - 15 <= d <= d_pad for both forms)
 	memcpy(&c->shadow_n, &stats[0], 4);
 	memcpy(&c->shadow_x, &stats[1], 4);
 }
@@ -617,6 +624,14 @@ int vk_bound_pass_state(vk_corpus_t *c, float *bounds, int64_t n, int64_t *count
 	return VK_OK;
 }
 
+// Internal (tests; not part of the ABI): the format of the handle's shadow -- 0 none, 8 int8 (MODE 7), 6 E2M3 (MODE 8) -- which is
+// the format of every bound pass vk_bound_pass_state reports on
+int vk_bound_pass_bits(vk_corpus_t *c, int64_t *bits) {
+	if (!c || !bits) return fail(VK_ERR_INVALID, "null argument");
+	*bits = c->shadow ? c->shadow_bits : 0;
+	return VK_OK;
+}
+
 // Internal (tests; not part of the ABI): which route the last vk_query_batch on this handle took and in which form -- state[VK_BS_COUNT]
 // in the order of vk_batch_state_index (all zero: no batch yet)
 int vk_batch_state(vk_corpus_t *c, int64_t *state) {
@@ -659,6 +674,30 @@ int vk_i8_bound_tile_probe(const int8_t *q, const int8_t *x, int32_t nk64, int32
 	VK_HIP(vk_launch_i8_bound_probe(d, d + tb, nk64, live, (int32_t *)(d + 2 * tb), nullptr));
 	VK_HIP(hipDeviceSynchronize());
 	VK_HIP(hipMemcpy(out, d + 2 * tb, 1024, hipMemcpyDeviceToHost));
+	return VK_OK;
+}
+
+// Internal (tests): one tile through the 6-bit bound kernel's own product (dot_tile_fp6, vk_common.hip.h).  q, x: 16 rows x 384 E2M3
+// codes each (host, row-major, one code per byte); the query tile is packed whole, the token tile with `live6` quarters of its last
+// K-step as the shadow packs it (vk_host::fp6_put_row) -- and the query's codes at features >= 256 + 32 live6 stay in its tile:
+// out[16 j + i] = q[j] . x[i] in grid values over the features the kernel reads
+int vk_fp6_bound_tile_probe(const uint8_t *q, const uint8_t *x, int32_t live6, float *out) {
+	if (!q || !x || !out) return fail(VK_ERR_INVALID, "null argument");
+	if (live6 < 1 || live6 > 4) return fail(VK_ERR_INVALID, "live6 is 1 .. 4");
+	const size_t xoff = VK_DEV_FP6_QTILE_BYTES, ooff = xoff + 5120;
+	vk_devbuf<uint8_t> buf;
+	if (int rc = buf.reserve(ooff + 1024, nullptr)) return rc;
+	uint8_t *d = buf;
+	std::vector<uint8_t> pk(ooff, 0);
+	for (int i = 0; i < 16; i++) {
+		vk_host::fp6_put_row(pk.data(), 4, i, q + (size_t)i * 384, 384);
+		vk_host::fp6_put_row(pk.data() + xoff, live6, i, x + (size_t)i * 384, 256 + 32 * live6);
+	}
+	static_assert(VK_DEV_FP6_QTILE_BYTES % 128 == 0 && VK_DEV_FP6_TILE_BYTES(4) <= 5120, "the probe's buffer");
+	VK_HIP(hipMemcpy(d, pk.data(), ooff, hipMemcpyHostToDevice));
+	VK_HIP(vk_launch_fp6_bound_probe(d, d + xoff, live6, (float *)(d + ooff), nullptr));
+	VK_HIP(hipDeviceSynchronize());
+	VK_HIP(hipMemcpy(out, d + ooff, 1024, hipMemcpyDeviceToHost));
 	return VK_OK;
 }
 

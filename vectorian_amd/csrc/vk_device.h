@@ -20,6 +20,13 @@
 #define VK_DEV_MAX_WIDE_QUERY_LEN 64   // vk_wide_kernel: lane = query column
 #define VK_DEV_BOUND_CONST_BYTES 256   // MODE 7: LDS behind the 8-bit query tile for the cells' constants (3 x 16 floats, padded);
                                        // the kernel steps over it and the host sizes the launch by it
+// MODE 8, the 6-bit (E2M3) shadow: K-steps of 128 features, 24 bytes per lane -- a 1 KiB part (each lane's first 16
+// bytes) and a 512-byte part (each lane's last 8); the last K-step of a corpus tile keeps `live6` of its four 16-lane quarters
+#define VK_DEV_FP6_STEPS 3             // K-steps of a tile: features 0 .. 383
+#define VK_DEV_FP6_STEP_BYTES 1536
+#define VK_DEV_FP6_QTILE_BYTES (VK_DEV_FP6_STEPS * VK_DEV_FP6_STEP_BYTES)   // the query tile: every K-step whole
+// bytes of a corpus tile with live6 quarters in its last K-step: the K-steps, then 16 x (s_x, e_x)
+#define VK_DEV_FP6_TILE_BYTES(live6) ((VK_DEV_FP6_STEPS - 1) * VK_DEV_FP6_STEP_BYTES + 384 * (live6) + 128)
 
 struct VkScoreParams {
 	// corpus
@@ -33,9 +40,11 @@ struct VkScoreParams {
 	int32_t nk32, tail, tile_bytes;
 	int32_t prec;              // 0: bf16 tiles (nk32 K-steps of 32); 1: fp32 tiles (nk32 blocks of 16 features)
 	int32_t q_lds;             // MODE 1: bytes of the query tile staged at the start of the dynamic LDS (0: read through L1 / L2)
-	int32_t bound_i8;          // 1: `tiles` is the 8-bit shadow (nk32 K-steps of 64 int8, tile_bytes = nk32 KiB + 128) and `qtile` its query tile
-	                           // with the cells' constants behind it: scores are upper bounds (MODE 7)
+	int32_t bound_bits;        // 0: `tiles` are the corpus's own.  8: `tiles` is the 8-bit shadow (nk32 K-steps of 64 int8, tile_bytes = nk32 KiB + 128)
+	                           // and `qtile` its query tile with the cells' constants behind it: scores are upper bounds (MODE 7);
+	                           // 6: the 6-bit shadow (MODE 8: tile_bytes = VK_DEV_FP6_TILE_BYTES(bound_live))
 	int32_t bound_live;        // MODE 7: the 16-lane quarters of a shadow tile's last block that hold features (1 .. 4); the rest is not fetched
+	                           // MODE 8: the quarters the last K-step of 128 features keeps (the tile stores no others)
 	int32_t q_mode3;           // 300-d bf16 rows: 1 = query tile in LDS (MODE 3, 136 VGPRs with general gaps), 0 = in registers (MODE 0, 160);
 	                           // 300-d fp32 rows: 1 = the specialised form (MODE 4), 0 = the generic loop (MODE 1)
 	const int32_t *group_list; // null: all groups of 4 slices; else the groups holding one long slice each (64-thread blocks)
@@ -351,6 +360,11 @@ hipError_t vk_launch_shadow(const uint8_t *tiles, int64_t n_tiles, int64_t rows_
 // one shadow tile through dot_tile_i8<nk64> (5 or 12) with `live` quarters of the last block fetched: out[16 j + i] (vk_pack.hip; tests)
 hipError_t vk_launch_i8_bound_probe(const uint8_t *qtile8, const uint8_t *tile8, int32_t nk64, int32_t live, int32_t *out, hipStream_t stream);
 hipError_t vk_launch_i8_probe(const int8_t *q, const int8_t *x, int32_t *out, hipStream_t stream);
+// the 6-bit shadow (MODE 8): tiles of VK_DEV_FP6_TILE_BYTES(live6); stats as vk_launch_shadow's
+hipError_t vk_launch_shadow6(const uint8_t *tiles, int64_t n_tiles, int64_t rows_total, int32_t d, int32_t tile_bytes, int32_t live6,
+	uint8_t *shadow, uint32_t *stats, hipStream_t stream);
+// one 6-bit query tile (VK_DEV_FP6_QTILE_BYTES) against one shadow tile through dot_tile_fp6: out[16 j + i] (vk_pack.hip; tests)
+hipError_t vk_launch_fp6_bound_probe(const uint8_t *qtile6, const uint8_t *tile6, int32_t live6, float *out, hipStream_t stream);
 // rows of the keys (up to the first empty slot of `n`) as groups of four rows of the slice table (vk_score_kernel's group_list)
 // theta on the device: the score of *theta_key (floor_excl when that slot is empty)
 hipError_t vk_launch_select_ge_key(const float *scores, int64_t n, const uint64_t *theta_key, float floor_excl, uint64_t *keys_out,

@@ -69,6 +69,16 @@ inline int bound_pass_mode() {
 	const char *e = getenv("VK_BOUND_PASS");
 	return !e ? 0 : !strcmp(e, "off") ? -1 : !strcmp(e, "force") ? 1 : 0;
 }
+// VK_BOUND_BITS, read at finalize: which shadow a corpus of 289 .. 304 features gets -- "8" the int8 one, "6" the E2M3 one.
+// Unset: 8 under VK_BOUND_PASS=force (the sizes below a million slices have been measured with 8 only, and the tests of the 8-bit
+// pass run under force), 6 where the pass is switched on by size (profiles/bound_fp6_ab.json: - 8.9 % per query at 1 M slices).
+// 753 .. 768 features: always 8.  A corpus carries one shadow.
+inline int bound_bits_wanted(int mode) {
+	const char *e = getenv("VK_BOUND_BITS");
+	if (e && !strcmp(e, "6")) return 6;
+	if (e && !strcmp(e, "8")) return 8;
+	return mode > 0 ? 8 : 6;
+}
 
 } // namespace
 
@@ -133,6 +143,7 @@ struct vk_corpus_shape {
 	// shadow_tile_bytes, and the corpus-wide constants of the bound -- shadow_n >= every |s_x xq|, shadow_x >= every |x|
 	const uint8_t *shadow = nullptr;
 	int shadow_nk64 = 0, shadow_tile_bytes = 0;
+	int shadow_bits = 0;   // 0: no shadow; 8: int8 (MODE 7); 6: E2M3 (MODE 8: three K-steps of 128, shadow_nk64 = 3, shadow_live = live6)
 	int shadow_live = 4;   // quarters of a tile's last block that hold features: ceil((d - 64 (shadow_nk64 - 1)) / 16); the bound kernel fetches only those
 	float shadow_n = 0.0f, shadow_x = 0.0f;
 };

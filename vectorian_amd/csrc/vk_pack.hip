@@ -1,5 +1,6 @@
 // vk_pack.hip -- corpus upload (normalise, round, tile order) and the per-query table of the static layout.
 #include "vk_common.hip.h"
+#include "vk_result_host.h"   // the integer helpers of the 6-bit shadow (host and device)
 
 // ---------------------------------------------------------------------------
 // corpus upload: L2-normalise rows (Vectors.normalized, vectorian/embedding/vectors.py:71-86),
@@ -179,6 +180,95 @@ extern "C" hipError_t vk_launch_i8_bound_probe(const uint8_t *qtile8, const uint
 	if (nk64 == 5) vk_i8_bound_probe_kernel<5><<<1, 64, 0, stream>>>(qtile8, tile8, live, out);
 	else if (nk64 == 12) vk_i8_bound_probe_kernel<12><<<1, 64, 0, stream>>>(qtile8, tile8, live, out);
 	else return hipErrorInvalidValue;
+	return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// The 6-bit shadow: tiles of VK_DEV_FP6_TILE_BYTES(live6) -- two whole K-steps of 128 features, the live6 quarters of
+// the third (features >= d are zero codes), then 16 x (s_x, e_x).  One thread per row; the arithmetic is
+// vk_host::quantize_row_e2m3 statement for statement, the codes and their packing come from the host's own integer helpers
+// (vk_host::e2m3_mag_of_eighths, fp6_pack32: compiled for both sides), laid out as vk_host::fp6_put_row lays them out.  stats as vk_shadow_kernel's.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void vk_shadow6_kernel(const uint8_t *__restrict__ tiles, int64_t n_tiles, int64_t rows_total, int32_t d,
+	int32_t tile_bytes, int32_t live6, uint8_t *__restrict__ shadow, uint32_t *__restrict__ stats) {
+	const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (row >= n_tiles * 16) return;
+	const int i = (int)(row & 15);
+	const uint8_t *src = tiles + (row >> 4) * (int64_t)tile_bytes;
+	uint8_t *dst = shadow + (row >> 4) * (int64_t)VK_DEV_FP6_TILE_BYTES(live6);
+	const int dk = row < rows_total ? d : 0;   // rows past the corpus (the tile's padding, the zero tile): zeros
+	float m = 0.0f;
+	bool bad = false;
+	for (int k = 0; k < dk; k++) {
+		const float x = tile_elem(src, i, k, 0);
+		bad = bad || !(fabsf(x) <= 3.4028234e38f);
+		m = fmaxf(m, fabsf(x));
+	}
+	const float s = m / 7.5f;
+	double e2 = 0.0, n2 = 0.0, a2 = 0.0;
+	for (int t = 0; t < VK_DEV_FP6_STEPS; t++) {
+		const int quarters = t == VK_DEV_FP6_STEPS - 1 ? live6 : 4;
+		for (int g = 0; g < quarters; g++) {   // a lane's operand: the codes of 32 features, packed by the host's packer
+			uint8_t codes[32];
+			for (int j = 0; j < 32; j++) {
+				const int k = 128 * t + 32 * g + j;
+				int code = 0;
+				if (k < dk) {
+					const float x = tile_elem(src, i, k, 0);
+					float v = 0.0f;
+					if (s > 0.0f) {
+						const float tt = fminf(7.5f, fabsf(x / s));
+						const float step = tt < 2.0f ? 0.125f : tt < 4.0f ? 0.25f : 0.5f;
+						const float a = fminf(7.5f, nearbyintf(tt / step) * step);
+						const int mag = vk_host::e2m3_mag_of_eighths((int)(a * 8.0f));
+						code = mag | ((x < 0.0f && mag != 0) ? 32 : 0);
+						v = x < 0.0f ? -a : a;
+					}
+					const double xs = (double)s * (double)v, dd = (double)x - xs;
+					e2 += dd * dd; n2 += xs * xs; a2 += (double)x * (double)x;
+				}
+				codes[j] = (uint8_t)code;
+			}
+			uint32_t w[6];
+			vk_host::fp6_pack32(codes, w);
+			uint8_t *step = dst + t * VK_DEV_FP6_STEP_BYTES;   // fp6_store_lane's places, as vector stores
+			const int lane = 16 * g + i;
+			*reinterpret_cast<uint4 *>(step + lane * 16) = uint4{w[0], w[1], w[2], w[3]};
+			*reinterpret_cast<uint2 *>(step + quarters * 256 + lane * 8) = uint2{w[4], w[5]};
+		}
+	}
+	const float e = quant_up_dev(sqrt(e2)), nn = quant_up_dev(sqrt(n2)), a = quant_up_dev(sqrt(a2));
+	*reinterpret_cast<float2 *>(dst + (VK_DEV_FP6_TILE_BYTES(live6) - 128) + i * 8) = float2{s, e};
+	if (bad) atomicOr(stats + 2, 1u);
+	else {
+		atomicMax(stats + 0, __builtin_bit_cast(uint32_t, nn));
+		atomicMax(stats + 1, __builtin_bit_cast(uint32_t, a));
+	}
+}
+
+extern "C" hipError_t vk_launch_shadow6(const uint8_t *tiles, int64_t n_tiles, int64_t rows_total, int32_t d, int32_t tile_bytes, int32_t live6,
+	uint8_t *shadow, uint32_t *stats, hipStream_t stream) {
+	if (live6 < 1 || live6 > 4 || d > 128 * (VK_DEV_FP6_STEPS - 1) + 32 * live6) return hipErrorInvalidValue;
+	hipError_t e = hipMemsetAsync(stats, 0, 16, stream);
+	if (e != hipSuccess) return e;
+	vk_shadow6_kernel<<<(unsigned)((n_tiles * 16 + 255) / 256), 256, 0, stream>>>(tiles, n_tiles, rows_total, d, tile_bytes, live6, shadow, stats);
+	return hipGetLastError();
+}
+
+// One 6-bit shadow tile against one 6-bit query tile, both packed already, through the bound kernel's own product: the query tile
+// staged in LDS as MODE 8 stages it, dot_tile_fp6 with `live6` quarters in the tile's last K-step (tests/test_gpu_bound6_product.py)
+__global__ __launch_bounds__(64) void vk_fp6_bound_probe_kernel(const uint8_t *__restrict__ qtile6, const uint8_t *__restrict__ tile6, int32_t live6,
+	float *__restrict__ out) {
+	__shared__ float4 qlds4[VK_DEV_FP6_QTILE_BYTES / 16];
+	const int lane = threadIdx.x;
+	for (int i = lane; i < VK_DEV_FP6_QTILE_BYTES / 16; i += 64) qlds4[i] = *reinterpret_cast<const float4 *>(qtile6 + i * 16);
+	__syncthreads();
+	const f32x4 acc = dot_tile_fp6(reinterpret_cast<const uint8_t *>(qlds4), tile6, lane, live6);
+	for (int r = 0; r < 4; r++) out[(4 * (lane >> 4) + r) * 16 + (lane & 15)] = acc[r];
+}
+extern "C" hipError_t vk_launch_fp6_bound_probe(const uint8_t *qtile6, const uint8_t *tile6, int32_t live6, float *out, hipStream_t stream) {
+	if (live6 < 1 || live6 > 4) return hipErrorInvalidValue;
+	vk_fp6_bound_probe_kernel<<<1, 64, 0, stream>>>(qtile6, tile6, live6, out);
 	return hipGetLastError();
 }
 

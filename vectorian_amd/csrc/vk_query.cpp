@@ -183,6 +183,26 @@ void vk_pack_query(const vk_corpus *c, const vk_query_desc *q, std::vector<uint8
 	// k / 64, lane 16 ((k % 64) / 16) + row, byte k % 16), then cs[16], ca[16], cb[16] -- zeros for the rows past the query, so that
 	// their cells are the exact kernel's zeros.
 	if (!tile8 || !c->shadow || c->prec || q->len_t > VK_FAST_QUERY_LEN) return;
+	if (c->shadow_bits == 6) {
+		// the 6-bit form: E2M3 codes by the shadow's quantizer and packer, all three K-steps whole (zeros past d), the same
+		// constants behind them -- gamma with the exact kernel's d_pad (320), which the shadow's format does not change
+		std::vector<uint8_t> t6((size_t)VK_DEV_FP6_QTILE_BYTES + 3 * 16 * 4, 0);
+		std::vector<uint8_t> codes((size_t)d);
+		float *cst6 = reinterpret_cast<float *>(t6.data() + (size_t)VK_DEV_FP6_QTILE_BYTES);
+		for (int i = 0; i < q->len_t; i++) {
+			for (int k = 0; k < d; k++) {
+				uint16_t b;
+				memcpy(&b, &tile[(size_t)(k >> 5) * 1024 + (size_t)(((k & 31) >> 3) * 16 + i) * 16 + (size_t)(k & 7) * 2], 2);
+				row[(size_t)k] = bf16_to_f32(b);
+				if (!(std::fabs(row[(size_t)k]) <= 3.4028234e38f)) return;   // not finite: no bound for this query
+			}
+			const vk_host::quant_meta m = vk_host::quantize_row_e2m3(row.data(), d, codes.data());
+			vk_host::fp6_put_row(t6.data(), 4, i, codes.data(), d);
+			vk_host::bound_cell_constants(m, c->shadow_n, c->shadow_x, 320, &cst6[i], &cst6[16 + i], &cst6[32 + i]);
+		}
+		tile8->swap(t6);
+		return;
+	}
 	const int nk64 = c->shadow_nk64;
 	std::vector<uint8_t> t8((size_t)nk64 * 1024 + 3 * 16 * 4, 0);
 	std::vector<int8_t> xq((size_t)d);
@@ -222,7 +242,7 @@ static int score_bounded(vk_corpus *c, const VkScoreParams &p, int grid, size_t 
 	if ((rc = c->d_bound_keys.reserve((size_t)2 * kTopkChunk, &c->device_bytes))) return rc;
 	if ((rc = c->d_counter.reserve(4, &c->device_bytes))) return rc;
 	VkScoreParams pb = p;
-	pb.tiles = c->shadow; pb.nk32 = c->shadow_nk64; pb.tail = 0; pb.tile_bytes = c->shadow_tile_bytes; pb.bound_i8 = 1; pb.bound_live = c->shadow_live;
+	pb.tiles = c->shadow; pb.nk32 = c->shadow_nk64; pb.tail = 0; pb.tile_bytes = c->shadow_tile_bytes; pb.bound_bits = c->shadow_bits; pb.bound_live = c->shadow_live;
 	pb.q_mode3 = 0; pb.q_lds = 0; pb.qtile = c->d_qtile8; pb.scores = c->d_ub; pb.raw = nullptr;
 	VK_HIP(vk_launch_score(&pb, grid, smem_bound, st));
 	VK_HIP(hipEventRecord(c->ev[2], st));
@@ -736,7 +756,8 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		// the bound kernel: the four waves' strips as above, and in place of the exact kernel's query tile the 8-bit one with the
 		// cells' constants behind it -- the region MODE 7 of vk_score_kernel steps over (NK32 KiB + VK_DEV_BOUND_CONST_BYTES)
 		const size_t smem_strips = smem - qlds - (size_t)p.q_lds;
-		const size_t smem_bound = smem_strips + (size_t)c->shadow_nk64 * 1024 + VK_DEV_BOUND_CONST_BYTES;
+		// (MODE 8: the 6-bit query tile, VK_DEV_FP6_QTILE_BYTES)
+		const size_t smem_bound = smem_strips + (c->shadow_bits == 6 ? (size_t)VK_DEV_FP6_QTILE_BYTES : (size_t)c->shadow_nk64 * 1024) + VK_DEV_BOUND_CONST_BYTES;
 		// the exact kernel over a group_list: one wave per workgroup, its strip and the exact query tile
 		const size_t smem_list = (size_t)lds_floats * 4 + qlds + (size_t)p.q_lds;
 		if ((rc = score_bounded(c, p, grid, smem, smem_bound, smem_list, kk, sel_floor, keep, st, &d_sel_bounded))) return rc;

@@ -16,6 +16,7 @@
 //   MODE 6: MODE 1 for fp32 rows (any d but the 300 of MODE 4)
 //   MODE 7: the 8-bit shadow of a contextual bf16 corpus, NK32 K-steps of 64 int8 (here NK32 counts those): every cell an upper bound of
 //           the cosine MODE 0 / 3 compute, so the score is an upper bound of theirs (the bound pass)
+//   MODE 8: the 6-bit (E2M3) shadow, three K-steps of 128 features (NK32 = 3): as MODE 7, the product on the scaled fp6 MFMA
 // GAP: 0 linear, 1 affine, 2 general (LDS history, serial in-row chain),
 //      3 general, sentences <= 32 tokens, strictly subadditive w_t (register history),
 //      4 relaxed word mover's distance (no DP: row / column minima of 1 - S),
@@ -25,7 +26,7 @@
 // LT: padded query length (4, 8, 12, 16).
 // ---------------------------------------------------------------------------
 
-// VK_SCORE_VGPRS (vk_score_m7.hip): a register budget for every kernel of the unit
+// VK_SCORE_VGPRS (vk_score_m7.hip, vk_score_m8.hip): a register budget for every kernel of the unit
 #ifdef VK_SCORE_VGPRS
 #define VK_SCORE_KERNEL_ATTR __attribute__((amdgpu_num_vgpr(VK_SCORE_VGPRS)))
 #else
@@ -53,6 +54,13 @@ __global__ __launch_bounds__(256) VK_SCORE_KERNEL_ATTR void vk_score_kernel(VkSc
 			vk_smem4[i] = *reinterpret_cast<const float4 *>(p.qtile + i * 16);
 		__syncthreads();
 		smem += NK32 * 256 + VK_DEV_BOUND_CONST_BYTES / 4;
+	}
+	// MODE 8: the 6-bit query tile (every K-step whole) and the same constants behind it
+	if constexpr (MODE == 8) {
+		for (int i = threadIdx.x; i < VK_DEV_FP6_QTILE_BYTES / 16 + 12; i += blockDim.x)
+			vk_smem4[i] = *reinterpret_cast<const float4 *>(p.qtile + i * 16);
+		__syncthreads();
+		smem += (VK_DEV_FP6_QTILE_BYTES + VK_DEV_BOUND_CONST_BYTES) / 4;
 	}
 	// MODE 1 (any d, fp32 tiles): the same staging with a runtime size; the K loop then reads the query with ds_read instead of
 	// going through L1 for every token tile
@@ -181,6 +189,7 @@ __global__ __launch_bounds__(256) VK_SCORE_KERNEL_ATTR void vk_score_kernel(VkSc
 				else if constexpr (MODE == 3) acc = sim_tile_qlds<NK32, TAIL>(qlds, tp, lane);
 				else if constexpr (MODE == 4) acc = sim_tile_f32_qlds<NK32>(qlds, tp, lane);
 				else if constexpr (MODE == 7) acc = sim_tile_i8<NK32>(qlds, tp, lane, p.bound_live);
+				else if constexpr (MODE == 8) acc = sim_tile_fp6(qlds, tp, lane, p.bound_live);
 				else {
 					// two calls, not one with a selected pointer: an LDS-or-global pointer is a flat pointer, and flat loads count
 					// on both wait counters -- every batch of tile loads would be waited for in full
@@ -313,11 +322,13 @@ static hipError_t launch_sized(K kernel, const VkScoreParams &p, int want_blocks
 	// narrow rows (d <= 96) are not a stream either: a slice is 6 KB or less and the DP dominates -- 64-d, 32 tokens: 3.4 TB/s at
 	// 3 per CU, 4.8 TB/s at 5; 96-d: 3.7 against 5.4 TB/s.  129..224-d: 4 per CU stream 4-8 % faster than 3 (6.4 against
 	// 6.0 TB/s); 128-d and 256..1536-d: 3 per CU within 2 % of the best setting (tools/sweep_dims.py, profiles/r02_sweep_dims*.jsonl)
-	const bool dp_bound = p.layout == VK_DEV_LAYOUT_STATIC || (p.nk32 <= 3 && !p.bound_i8);
+	const bool dp_bound = p.layout == VK_DEV_LAYOUT_STATIC || (p.nk32 <= 3 && p.bound_bits == 0);
 	// the 8-bit shadow (MODE 7, 328-byte rows; 1 M x 32 tokens, general gaps): 1.58 - 1.61 ms at 3 per CU, 1.60 - 1.65 at 4, 1.70 at 5, 1.80 at 2 --
 	// and three waves per SIMD of its 120 VGPRs leave room for the rounds' exact kernel beside it (vk_score_m7.hip)
+	// the 6-bit shadow (MODE 8, 3,968-byte tiles, the same shape): ms_per_step 1.44 at 3 per CU, 1.51 at 4, 1.52 at 5, 1.72 at 2 -- at 4 and 5 the
+	// kernel alone is faster (1.34 / 1.30 ms against 1.42) but the rounds lose their place beside the peer's pass
 	// the 12-step shadow (768-d rows, 1 M slices of 8 .. 64 tokens, 64-row history): LDS and registers admit two per CU -- 4.40 ms; one: 5.98 ms
-	const int stream_cap = (!p.bound_i8 && p.nk32 >= 5 && p.nk32 <= 7) ? 4 : 3;
+	const int stream_cap = (p.bound_bits == 0 && p.nk32 >= 5 && p.nk32 <= 7) ? 4 : 3;
 	if (occ > stream_cap && !dp_bound && !bound_pass) occ = stream_cap;   // the static layout is DP-bound, not a stream: keep full residency
 	// 768-d rows: a wave already keeps 24 KiB of loads in flight per tile; one workgroup per CU measured fastest
 	// (ragged 8..64 tokens, 400 k sentences: 3.37 ms at 1, 3.45 ms at 2 per CU)

@@ -1,0 +1,21 @@
+// vk_score_m8.hip -- vk_score_kernel, MODE 8: the bound pass over the 6-bit (E2M3) shadow (see vk_score.hip.h); the 64-row
+// register history of general gaps is in vk_score_m8w.hip.
+// The budget of vk_score_m7.hip, for its reason: up to 12 query columns the forms allocate at most 120 VGPRs without scratch, three
+// waves per SIMD leave room for a wave of the exact kernel (136) beside the bound pass.  The tile's registers are 18 (three K-steps of
+// 4 + 2) where the 8-bit form holds 20; the figures by gap mode and query width are in DESIGN 11.8 (tools/kernel_regs.py).
+#define VK_SCORE_VGPRS 120
+#include "vk_score.hip.h"
+
+// 289 .. 304 features (three K-steps of 128 E2M3 codes, the last with bound_live of its four quarters); alignments over slices of at
+// most 64 tokens only: the gap modes of the main launch
+extern "C" hipError_t vk_launch_score_m8w(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
+extern "C" hipError_t vk_launch_score_m8(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream) {
+	if (p->bound_live < 1 || p->bound_live > 4 || p->tile_bytes != VK_DEV_FP6_TILE_BYTES(p->bound_live)) return hipErrorInvalidValue;
+	switch (p->gap_mode) {
+	case 0: return launch_score_lt<8, VK_DEV_FP6_STEPS, false, 0>(*p, grid, smem_bytes, stream);
+	case 1: return launch_score_lt<8, VK_DEV_FP6_STEPS, false, 1>(*p, grid, smem_bytes, stream);
+	case 3: return launch_score_lt<8, VK_DEV_FP6_STEPS, false, 3>(*p, grid, smem_bytes, stream);
+	case 6: return vk_launch_score_m8w(p, grid, smem_bytes, stream);
+	default: return hipErrorInvalidValue;
+	}
+}
