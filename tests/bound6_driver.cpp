@@ -1,16 +1,7 @@
-// Driver of tests/test_bound6_host.py: the host side of the 6-bit bound pass (vk_result_host.h: the E2M3 quantizer and the packer of a
+// Driver of tests/test_bound6_host.py: the host side of the 6-bit bound pass (vk_bound_host.h: the E2M3 quantizer and the packer of a
 // lane's operand, which vk_pack_query calls for the query's rows) and nothing else.  stdin: whitespace-separated numbers, floats as the
 // hexadecimal of their bits; stdout the same.  The expected values are computed in the test, never here.
-#include "vk_result_host.h"
-
-#include <cinttypes>
-#include <cstdio>
-#include <string>
-
-static uint32_t read_u32() { uint32_t u = 0; if (scanf("%" SCNx32, &u) != 1) exit(2); return u; }
-static int64_t read_i64() { int64_t v = 0; if (scanf("%" SCNd64, &v) != 1) exit(2); return v; }
-static float read_f32() { const uint32_t u = read_u32(); float f; memcpy(&f, &u, 4); return f; }
-static uint32_t bits_of(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+#include "bound_driver.h"
 
 int main(int argc, char **argv) {
 	const std::string what = argc > 1 ? argv[1] : "";
@@ -38,7 +29,8 @@ int main(int argc, char **argv) {
 		for (const uint8_t b : tile) printf("%d ", (int)b);
 		printf("\n");
 	} else {
-		return 1;
+		const int rc = format_commands(what);   // "format", "query_tile" (bound_driver.h)
+		return rc < 0 ? 1 : rc;
 	}
 	return 0;
 }

@@ -1,40 +1,29 @@
-"""CPU tier: the host side of the 6-bit bound pass -- vk_host::quantize_row_e2m3, e2m3_eighths and the packer of a
-tile in vk_result_host.h, which vk_pack_query calls for the query's rows and vk_shadow6_kernel restates for the corpus -- run through
-a g++ driver under AddressSanitizer and UBSan (the stand-alone program tests/bound6_driver.cpp) and held against their statement
-in numpy (tests/bound6_cases.py):
+"""CPU tier: the host side of the 6-bit bound pass -- vk_host::quantize_row_e2m3, e2m3_eighths, the packer of a tile,
+the format of the shadow and the query's bound tile in vk_bound_host.h, the functions both the query's tile and the shadow's kernel
+are made of -- run through a g++ driver under AddressSanitizer and UBSan (the stand-alone program tests/bound6_driver.cpp) and held
+against their statement in numpy (tests/bound6_cases.py):
   * every code decodes to a value of the grid, and the quantizer emits the nearest one, ties to the even multiple of the step;
   * the largest component of a row maps to +-7.5; e is at least the true norm of the residual in float64;
   * rows of zeros, one-hot rows, rows of 1e-30 and of 1e30;
   * the bytes of a packed tile are the layout the kernel reads;
+  * the format of the 6-bit shadow is the table written out here at every width of the form, and the query's tile
+    (vk_host::pack_bound_query) is pack_tile's bytes with constants()'s numbers behind them;
   * a cell of the bound is >= the float64 cosine of the stored rows for 10,000 random pairs at 289, 300 and 304 features -- and is
     not once e is taken for 0, so the test can tell."""
-
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bound6_cases as b6
-from test_devbuf import CSRC, ROOT
+import bound_cases as bc
+from bound_cases import hexbits
 
 F = np.float32
 
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-	exe = str(tmp_path_factory.mktemp("bound6") / "bound6_driver")
-	subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-		"-fno-omit-frame-pointer", "-I", CSRC, os.path.join(ROOT, "tests", "bound6_driver.cpp"), "-o", exe], check=True)
-
-	def run(what, *numbers):
-		out = subprocess.run([exe, what], input=" ".join(str(x) for x in numbers), check=True, capture_output=True, text=True)
-		return out.stdout.split("\n")[:-1]
-	return run
-
-
-def hexbits(x):
-	return "%08x" % int(np.asarray(x, dtype=F).view(np.uint32))
+	return bc.build_driver(tmp_path_factory, "bound6_driver")
 
 
 def quantize_by_driver(driver, rows):
@@ -126,3 +115,39 @@ def test_every_cell_of_the_bound_is_above_the_cosine(d, driver):
 	# without the residual norms the same cells are no bound: the test can tell a bound from an estimate
 	zero = np.zeros_like(e_x)
 	assert (cells(zero, np.zeros_like(e_q)) < exact).any()
+
+
+def test_format_of_the_6bit_shadow(driver):
+	"""three K-steps of 128 features, 2 x 1536 + 384 live6 + 128 bytes per tile with live6 the quarters of 32 that hold features, a
+	query tile of 4,608 bytes, gamma over the exact kernel's 320; none beside the widths"""
+	widths = (289, 300, 303, 304)
+	asked = [bc.factory_args(d, 6) for d in widths]
+	out = driver("format", len(asked), *sum(asked, []))
+	for d, line in zip(widths, out):
+		live6 = -(-(d - 256) // 32)
+		tile = 2 * 1536 + 384 * live6 + 128
+		assert live6 == 2 and [int(v) for v in line.split()] == [6, 3, 128, live6, tile, tile - 128, 4608, 320], (d, line)
+	none = [bc.factory_args(d, 6) for d in (288, 305, 752, 769)] + [bc.factory_args(300, 6, prec=1), bc.factory_args(300, 6, layout=1)]
+	assert driver("format", len(none), *sum(none, [])) == ["none"] * len(none)
+
+
+def test_query_tile_of_the_6bit_pass(driver):
+	"""pack_bound_query at 300-d for queries of 1, 10 and 16 rows: every K-step whole, zeros past the query and past d, cs / ca / cb
+	behind them; a query with an infinite element has no bound"""
+	d = 300
+	rng = np.random.default_rng(11)
+	Q = b6.stored(rng.standard_normal((16, d)).astype(F))
+	Q[2] = 0.0
+	N, X = F(1.0078125), F(1.015625)
+	for len_t in (1, 10, 16):
+		out = driver("query_tile", *bc.factory_args(d, 6), len_t, hexbits(N), hexbits(X), *[hexbits(v) for v in Q[:len_t].reshape(-1)])
+		got = np.array([int(v) for v in out[0].split()], dtype=np.uint8)
+		codes = np.zeros((16, 384), dtype=np.uint8)
+		cst = np.zeros((3, 16), dtype=F)
+		qc, s, e, n, a = b6.quantize6(Q[:len_t])
+		codes[:len_t, :d] = qc
+		cst[:, :len_t] = b6.constants(s, e, a, N, X)
+		assert len(got) == 4608 and (got == b6.pack_tile(codes, 4)).all()
+		assert out[1].split() == [hexbits(v) for v in cst.reshape(-1)]
+	Q[9, 299] = -np.inf
+	assert driver("query_tile", *bc.factory_args(d, 6), 10, hexbits(N), hexbits(X), *[hexbits(v) for v in Q[:10].reshape(-1)]) == ["none"]

@@ -2,18 +2,19 @@
 column, the cell of the bound kernel -- on random unit rows rounded to bf16 in 50, 300 and 768 dimensions, rows with one dominant
 component and rows of zeros among them:
   * every cell of the bound is >= the float32 dot product of the bf16-rounded rows (what the exact kernel's cell approximates);
-  * the host quantizer (vk_host::quantize_row_i8 and bound_cell_constants in vk_result_host.h, which vk_pack_query calls for the query's
-    rows), run through a g++ driver with AddressSanitizer and UBSan, gives the restatement's numbers bit for bit;
-  * the rule by which a handle stops trying the bound pass (vk_host::bound_backoff) keeps its worst case.
-(The packing of the query's 8-bit tile in vk_pack_query is covered on the GPU only: bound >= exact score, tests/test_gpu_bound_pass.py.)"""
-
-import os
-import subprocess
+  * the host quantizer (vk_host::quantize_row_i8 and bound_cell_constants in vk_bound_host.h, the function both the query's tile
+    and the shadow's kernel are made of), run through a g++ driver with AddressSanitizer and UBSan (the stand-alone program
+    tests/bound_pass_driver.cpp), gives the restatement's numbers bit for bit;
+  * the format of a shadow (vk_host::shadow_format_of) is the table written out here, at every width where it changes;
+  * the query's 8-bit bound tile (vk_host::pack_bound_query) is the numpy packer's bytes, its constants constants()'s, and a query
+    with an infinite element has none;
+  * the rule by which a handle stops trying the bound pass (vk_host::bound_backoff) keeps its worst case."""
 
 import numpy as np
 import pytest
 
-from test_devbuf import CSRC, ROOT
+import bound_cases as bc
+from bound_cases import constants8 as constants, hexbits, quantize8 as quantize
 from vectorian_amd import synth
 
 F = np.float32
@@ -21,44 +22,7 @@ F = np.float32
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-	exe = str(tmp_path_factory.mktemp("bound_pass") / "bound_pass_driver")
-	subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-		"-fno-omit-frame-pointer", "-I", CSRC, os.path.join(ROOT, "tests", "bound_pass_driver.cpp"), "-o", exe], check=True)
-
-	def run(what, *numbers):
-		out = subprocess.run([exe, what], input=" ".join(str(x) for x in numbers), check=True, capture_output=True, text=True)
-		return out.stdout.split("\n")[:-1]
-	return run
-
-
-def hexbits(x):
-	return "%08x" % int(np.asarray(x, dtype=F).view(np.uint32))
-
-
-def up(v):
-	"""a non-negative double rounded UP to float32 (quant_up)"""
-	if not v > 0:
-		return F(0)
-	return np.nextafter(F(v * (1.0 + 1e-6)), F(np.inf))
-
-
-def quantize(x):
-	"""x: a float32 row.  Returns xq (int8), s, e >= |x - s xq|, n >= |s xq|, a >= |x| -- sums in double, in k order"""
-	m = F(np.max(np.abs(x))) if len(x) else F(0)
-	s = F(m / F(127))
-	if s > 0:
-		xq = np.clip(np.rint(x / s), -127, 127).astype(np.int8)
-	else:
-		xq = np.zeros(len(x), dtype=np.int8)
-	xs = np.float64(s) * xq.astype(np.float64)
-	dd = x.astype(np.float64) - xs
-	seq = lambda t: float(np.cumsum(t)[-1]) if len(t) else 0.0   # sequential, as the C loop
-	return xq, s, up(np.sqrt(seq(dd * dd))), up(np.sqrt(seq(xs * xs))), up(np.sqrt(seq(x.astype(np.float64) ** 2)))
-
-
-def constants(s, e, n, a, N, X, d_pad):
-	gamma = 2.0 * d_pad * 2.0 ** -24 * float(a) * float(X) + 2e-6
-	return s, a, up(float(e) * float(N) + gamma)
+	return bc.build_driver(tmp_path_factory, "bound_pass_driver")
 
 
 def rows_of(d, seed):
@@ -104,6 +68,46 @@ def test_every_cell_of_the_bound_is_above_the_dot_product(d, driver):
 	out = driver("constants", len(qq), *args)
 	for line, (_, s, e, n, a) in zip(out, qq):
 		assert line.split() == [hexbits(v) for v in constants(s, e, n, a, N, Xmax, d_pad)]
+
+
+# d -> live quarters of the last K-step; the 8-bit forms: (K-steps, bytes per tile, bytes of the query's tile, gamma's width)
+LIVE8 = {289: 3, 300: 3, 303: 3, 304: 3, 753: 4, 768: 4}
+FORM8 = {5: (5, 5248, 5120, 320), 12: (12, 12416, 12288, 768)}
+
+
+def test_format_of_the_8bit_shadow(driver):
+	"""the table of DESIGN 11.1; none beside the widths, for fp32 rows and for the static layout; six bits asked of 768-d rows: eight"""
+	asked = [bc.factory_args(d, 8) for d in sorted(LIVE8)] + [bc.factory_args(d, 6) for d in (753, 768)]
+	out = driver("format", len(asked), *sum(asked, []))
+	for args, line in zip(asked, out):
+		steps, tile, qtile, gamma = FORM8[5 if args[0] < 400 else 12]
+		assert [int(v) for v in line.split()] == [8, steps, 64, LIVE8[args[0]], tile, tile - 128, qtile, gamma], (args, line)
+	none = [bc.factory_args(d, b) for d in (288, 305, 752, 769, 50) for b in (8, 6)]
+	none += [bc.factory_args(d, 8, prec=1) for d in (300, 768)] + [bc.factory_args(d, 8, layout=1) for d in (300, 768)]
+	assert driver("format", len(none), *sum(none, [])) == ["none"] * len(none)
+
+
+@pytest.mark.parametrize("d", (300, 768))
+def test_query_tile_of_the_8bit_pass(d, driver):
+	"""pack_bound_query for queries of 1, 10 and 16 rows: the codes in the block order, zeros past the query and past d, the constants
+	with the exact kernel's padded K in gamma"""
+	steps, _, qtile, gamma = FORM8[5 if d == 300 else 12]
+	Q = rows_of(d, 5)[:16]
+	N, X = F(1.0078125), F(1.015625)
+	for len_t in (1, 10, 16):
+		out = driver("query_tile", *bc.factory_args(d, 8), len_t, hexbits(N), hexbits(X), *[hexbits(v) for v in Q[:len_t].reshape(-1)])
+		got = np.array([int(v) for v in out[0].split()], dtype=np.uint8)
+		codes = np.zeros((16, 64 * steps), dtype=np.int8)
+		want = [[hexbits(0)] * 16 for _ in range(3)]
+		for i in range(len_t):
+			xq, s, e, n, a = quantize(Q[i])
+			codes[i, :d] = xq
+			for j, v in enumerate(constants(s, e, n, a, N, X, gamma)):
+				want[j][i] = hexbits(v)
+		assert len(got) == qtile and (got == bc.pack_tile8(codes)).all()
+		assert out[1].split() == sum(want, [])
+	Q[3, 7] = np.inf
+	assert driver("query_tile", *bc.factory_args(d, 8), 10, hexbits(N), hexbits(X), *[hexbits(v) for v in Q[:10].reshape(-1)]) == ["none"]
 
 
 def test_back_off_after_repeated_fallbacks(driver):

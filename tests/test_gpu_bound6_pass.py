@@ -20,13 +20,14 @@ Shapes: 4,000 x 32 tokens; 3,000 slices of 1 .. 64 tokens with empty ones (both 
 Widths 289, 303 and 304 build a 6-bit shadow, 288 and 305 none.  Without VK_BOUND_BITS, force keeps the 8-bit shadow."""
 
 import ctypes as C
-import os
 import threading
 
 import numpy as np
 import pytest
 
 import bound6_cases as b6
+import bound_cases as bc
+from bound_cases import case_queries, corpus_of as _corpus, ragged_with_empties, same_results, state
 from vectorian_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -37,35 +38,9 @@ GAPS = {"linear": (0.1, 0.1), "affine": (("affine", 0.2, 0.05), ("affine", 0.2, 
 TILE6, TILE8 = 3968, 5248
 
 
-class _Env:
+def _Env(mode, bits="6"):
 	"""VK_BOUND_PASS and VK_BOUND_BITS for the duration of a block (the library reads them at finalize and per query)"""
-
-	def __init__(self, mode, bits="6"):
-		self.values = {"VK_BOUND_PASS": mode, "VK_BOUND_BITS": bits}
-
-	def __enter__(self):
-		self.old = {k: os.environ.get(k) for k in self.values}
-		for k, v in self.values.items():
-			if v is None:
-				os.environ.pop(k, None)
-			else:
-				os.environ[k] = v
-
-	def __exit__(self, *exc):
-		for k, v in self.old.items():
-			if v is None:
-				os.environ.pop(k, None)
-			else:
-				os.environ[k] = v
-
-
-def _corpus(hip, X, off):
-	Xb = synth.to_bf16_bits(synth.normalize_rows(X))
-	c = hip.Corpus(layout=hip.VK_LAYOUT_CONTEXTUAL, d=Xb.shape[1], n_tokens=Xb.shape[0], n_sentences=len(off) - 1)
-	c.append_vectors(Xb, normalize=False)
-	c.set_sentences(off)
-	c.finalize()
-	return c
+	return bc.Env(VK_BOUND_PASS=mode, VK_BOUND_BITS=bits)
 
 
 def bits_of(hip, c):
@@ -78,50 +53,17 @@ def bits_of(hip, c):
 	return out.value
 
 
-def state(hip, c, bounds=True):
-	"""(bounds per slice or None, counters: ran, round 1, round 2, fell back, queries, fallbacks, survivors)"""
-	lib = hip.lib()
-	lib.vk_bound_pass_state.restype = C.c_int
-	lib.vk_bound_pass_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-	cnt = np.zeros(7, dtype=np.int64)
-	ub = np.empty(c.n_sentences, dtype=np.float32) if bounds else None
-	with c.lock:
-		hip._check(lib.vk_bound_pass_state(c._h, ub.ctypes.data if bounds else None, c.n_sentences, cnt.ctypes.data))
-	return ub, cnt
-
-
-class Pair:
+class Pair(bc.Pair):
 	"""the same vectors twice: `forced` has a 6-bit shadow, `exact` has none"""
 
 	def __init__(self, hip, corpus, X=None, off=None):
-		self.corpus = corpus
-		self.X = corpus["X"] if X is None else X
-		self.off = np.asarray(corpus["sent_off"] if off is None else off, dtype=np.int64)
-		self.n = len(self.off) - 1
-		with _Env("off"):
-			self.exact = _corpus(hip, self.X, self.off)
-		with _Env("force"):
-			self.forced = _corpus(hip, self.X, self.off)
+		super().__init__(hip, _Env, corpus, X, off)
 		tiles = self.X.shape[0] // 16
 		extra = self.forced.device_bytes - self.exact.device_bytes
 		# the shadow is counted: 3,968 bytes per tile of 16 tokens (a few tiles of padding; far from the 8-bit shadow's 5,248)
 		assert bits_of(hip, self.forced) == 6 and bits_of(hip, self.exact) == 0
 		assert tiles * TILE6 <= extra <= (tiles + 8) * TILE6 + 4096, (extra, tiles)
 		self.terms = b6.corpus_terms(b6.stored(self.X))
-
-	def close(self):
-		self.forced.close()
-		self.exact.close()
-
-
-def same_results(a, b):
-	assert a.n == b.n
-	n = a.n
-	assert (a.score[:n].view(np.uint32) == b.score[:n].view(np.uint32)).all(), (a.score[:n], b.score[:n])
-	assert (a.raw_score[:n].view(np.uint32) == b.raw_score[:n].view(np.uint32)).all()
-	assert (a.sentence[:n] == b.sentence[:n]).all(), (a.sentence[:n], b.sentence[:n])
-	assert (a.mapping[:n] == b.mapping[:n]).all()
-	assert (a.edge_sim[:n].view(np.uint32) == b.edge_sim[:n].view(np.uint32)).all()
 
 
 BRANCHES = {"asserted no fallback": 0, "either outcome allowed": 0, "fell back where allowed": 0}
@@ -189,23 +131,6 @@ def tiny(hip):
 	p = Pair(hip, synth.make_contextual_corpus(37, 1, 3, V, D, seed=43))
 	yield p
 	p.close()
-
-
-def ragged_with_empties(d, n, seed):
-	"""n slices of 1..64 tokens, five of them emptied in place (first, inside a group, last)"""
-	corpus = synth.make_contextual_corpus(n - 5, 1, 64, V, d, seed=seed)
-	off = corpus["sent_off"]
-	at = np.array([0, 7, (n - 5) // 2, n - 6, n - 5])
-	corpus["sent_off"] = np.insert(off, at, off[at])
-	assert len(corpus["sent_off"]) - 1 == n and (np.diff(corpus["sent_off"]) == 0).sum() == 5
-	return corpus
-
-
-def case_queries(corpus, len_t):
-	"""a noisy copy of len_t consecutive corpus tokens and len_t words drawn from the vocabulary; one token: the drawn word only (a
-	copied token is a frequent word, the tie case test_a_frequent_word_falls_back states)"""
-	qs = synth.make_queries(corpus, 2, len_t, seed=100 + len_t)
-	return [q["vectors"] for q in (qs[1:] if len_t == 1 else qs)]
 
 
 @pytest.mark.parametrize("gap", sorted(GAPS))

@@ -18,12 +18,13 @@ back, which test_a_frequent_word_falls_back states; so no one-token query of a w
 fallback, a narrower length-1 case than a query copied from the corpus would be."""
 
 import ctypes as C
-import os
 import threading
 
 import numpy as np
 import pytest
 
+import bound_cases as bc
+from bound_cases import case_queries, corpus_of as _corpus, ragged_with_empties, same_results, state
 from vectorian_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -33,112 +34,23 @@ EXP5 = ("table", (1 - 2.0 ** (-np.arange(0, 65) / 5)).astype(np.float32))
 GAPS = {"linear": (0.1, 0.1), "affine": (("affine", 0.2, 0.05), ("affine", 0.2, 0.05)), "exp5": (EXP5, EXP5)}
 
 
-class _Env:
+def _Env(value):
 	"""VK_BOUND_PASS for the duration of a block (the library reads it at finalize and per query)"""
-
-	def __init__(self, value):
-		self.value = value
-
-	def __enter__(self):
-		self.old = os.environ.get("VK_BOUND_PASS")
-		os.environ["VK_BOUND_PASS"] = self.value
-
-	def __exit__(self, *exc):
-		if self.old is None:
-			del os.environ["VK_BOUND_PASS"]
-		else:
-			os.environ["VK_BOUND_PASS"] = self.old
+	return bc.Env(VK_BOUND_PASS=value)
 
 
-def _corpus(hip, X, off):
-	Xb = synth.to_bf16_bits(synth.normalize_rows(X))
-	c = hip.Corpus(layout=hip.VK_LAYOUT_CONTEXTUAL, d=Xb.shape[1], n_tokens=Xb.shape[0], n_sentences=len(off) - 1)
-	c.append_vectors(Xb, normalize=False)
-	c.set_sentences(off)
-	c.finalize()
-	return c
-
-
-class Pair:
+class Pair(bc.Pair):
 	"""the same vectors twice: `forced` has a shadow, `exact` has none"""
 
 	def __init__(self, hip, corpus, X=None, off=None):
-		self.corpus = corpus
-		X = corpus["X"] if X is None else X
-		self.X = X
-		off = corpus["sent_off"] if off is None else off
-		self.off = np.asarray(off, dtype=np.int64)
-		self.n = len(off) - 1
-		with _Env("off"):
-			self.exact = _corpus(hip, X, off)
-		with _Env("force"):
-			self.forced = _corpus(hip, X, off)
+		super().__init__(hip, _Env, corpus, X, off)
 		# the shadow is counted: 5 KiB + 128 bytes per tile of 16 tokens beside 9.5 KiB
-		assert self.forced.device_bytes - self.exact.device_bytes >= (X.shape[0] // 16) * (5 * 1024 + 128)
-
-	def close(self):
-		self.forced.close()
-		self.exact.close()
-
-
-def state(hip, c, bounds=True):
-	"""(bounds per slice or None, counters: ran, round 1, round 2, fell back, queries, fallbacks, survivors)"""
-	lib = hip.lib()
-	lib.vk_bound_pass_state.restype = C.c_int
-	lib.vk_bound_pass_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-	cnt = np.zeros(7, dtype=np.int64)
-	ub = np.empty(c.n_sentences, dtype=np.float32) if bounds else None
-	with c.lock:
-		hip._check(lib.vk_bound_pass_state(c._h, ub.ctypes.data if bounds else None, c.n_sentences, cnt.ctypes.data))
-	return ub, cnt
-
-
-def stored(x):
-	"""unit rows as the corpus stores them: normalised, rounded to bf16"""
-	return synth.bf16_bits_to_f32(synth.to_bf16_bits(synth.normalize_rows(x)))
-
-
-def quantized(x):
-	"""the quantizer of vk_host::quantize_row_i8 over all rows at once: (e >= |x - s xq|, n >= |s xq|, a >= |x|) per row, each with a
-	relative 1e-5 on top (the library rounds its double sums up by 1e-6)"""
-	s = (np.abs(x).max(axis=1) / np.float32(127)).astype(np.float32)
-	safe = np.where(s > 0, s, np.float32(1))
-	xq = np.clip(np.rint(x / safe[:, None]), -127, 127) * (s > 0)[:, None]
-	xs = s.astype(np.float64)[:, None] * xq
-	norm = lambda t: np.sqrt((t * t).sum(axis=1)) * (1 + 1e-5)
-	return norm(x.astype(np.float64) - xs), norm(xs), norm(x.astype(np.float64))
+		assert self.forced.device_bytes - self.exact.device_bytes >= (self.X.shape[0] // 16) * (5 * 1024 + 128)
 
 
 def round2_limit(pair, qv, full, k, min_score):
-	"""(delta, the most slices round 2 can hold), from the exact scores `full` and the formats alone.  A cell of the bound exceeds the
-	exact cosine by at most delta = 2 max (e_x a_q + e_q N) + gamma + 2e-5 (the Cauchy-Schwarz terms are added where the
-	true quantization error may be as far below zero, at their largest over corpus and query; 2e-5 is the exact kernel's own rounding); a
-	score is its at most len_t matched cells over len_t, so bound - exact <= delta per slice.  Round 1 scores the M >= kk largest bounds:
-	the kk-th largest bound is >= the kk-th best exact score s_kk, so theta >= s_kk - delta (or theta is the floor, when s_kk - delta is
-	not above it or fewer than kk slices are).  A slice of round 2 has bound >= theta, hence exact >= theta - delta."""
-	if not hasattr(pair, "quant"):
-		e, n, a = quantized(stored(pair.corpus["X"] if not hasattr(pair, "X") else pair.X))
-		pair.quant = (e.max(), n.max(), a.max())
-	e_x, N, X = pair.quant
-	e_q, _, a_q = quantized(stored(qv))
-	gamma = 2 * 320 * 2.0 ** -24 * a_q * X + 2e-6
-	delta = float((2 * (e_x * a_q + e_q * N) + gamma).max()) * (1 + 1e-5) + 2e-5
-	floor = min_score - 1e-5 * max(1.0, abs(min_score))            # the selection's floor with tracebacks (vk_query.cpp sel_floor)
-	kk = min(k + 8, pair.n)
-	above = np.sort(full[full > floor])[::-1]
-	if len(above) >= kk and above[kk - 1] - delta > floor:
-		return delta, int((full >= above[kk - 1] - 2 * delta).sum())
-	return delta, int((full > floor - delta).sum())
-
-
-def same_results(a, b):
-	assert a.n == b.n
-	n = a.n
-	assert (a.score[:n].view(np.uint32) == b.score[:n].view(np.uint32)).all(), (a.score[:n], b.score[:n])
-	assert (a.raw_score[:n].view(np.uint32) == b.raw_score[:n].view(np.uint32)).all()
-	assert (a.sentence[:n] == b.sentence[:n]).all(), (a.sentence[:n], b.sentence[:n])
-	assert (a.mapping[:n] == b.mapping[:n]).all()
-	assert (a.edge_sim[:n].view(np.uint32) == b.edge_sim[:n].view(np.uint32)).all()
+	"""(delta, the most slices round 2 can hold) with the 300-d forms' d_pad = 320 in gamma (bound_cases.round2_limit8)"""
+	return bc.round2_limit8(pair, qv, full, k, min_score, 320)
 
 
 def check(hip, pair, qv, expect_fallback=False, **kw):
@@ -194,16 +106,6 @@ def tiny(hip):
 	p.close()
 
 
-def case_queries(corpus, len_t):
-	"""The queries of a case: a noisy copy of len_t consecutive corpus tokens and len_t words drawn uniformly from the vocabulary
-	(synth.make_queries' two kinds).  One token: the drawn word only -- a one-token query is a lookup of one word, the corpus draws its
-	words from a Zipf law, and a copied token is a frequent word w.h.p.: hundreds to thousands of slices then hold that very word and tie
-	within the quantization error (measured on the 4,000 x 32 shape: 3,523 .. 3,966 slices reach theta), which is the tie case that
-	test_a_frequent_word_falls_back states on its own."""
-	qs = synth.make_queries(corpus, 2, len_t, seed=100 + len_t)
-	return [q["vectors"] for q in (qs[1:] if len_t == 1 else qs)]
-
-
 @pytest.mark.parametrize("gap", sorted(GAPS))
 @pytest.mark.parametrize("len_t", (1, 4, 10, 16))
 @pytest.mark.parametrize("shape", ("uniform", "ragged", "tiny"))
@@ -219,16 +121,6 @@ def test_pruned_query_is_the_exact_query(hip, request, shape, len_t, gap):
 				cnt = check(hip, pair, qv, locality=locality, gap_s=gs, gap_t=gt, max_matches=k, min_score=0.0 if locality == 0 else -1e9)
 				if shape == "uniform" and len_t == 10 and k <= 10:
 					assert cnt[2] <= pair.n // 100, cnt
-
-
-def ragged_with_empties(d, n, seed):
-	"""n slices of 1..64 tokens, five of them emptied in place (first, inside a group, last)"""
-	corpus = synth.make_contextual_corpus(n - 5, 1, 64, V, d, seed=seed)
-	off = corpus["sent_off"]
-	at = np.array([0, 7, (n - 5) // 2, n - 6, n - 5])
-	corpus["sent_off"] = np.insert(off, at, off[at])
-	assert len(corpus["sent_off"]) - 1 == n and (np.diff(corpus["sent_off"]) == 0).sum() == 5
-	return corpus
 
 
 @pytest.mark.parametrize("d", (289, 303, 304))

@@ -19,7 +19,9 @@ import threading
 import numpy as np
 import pytest
 
-from test_gpu_bound_pass import EXP5, _Env, _corpus, case_queries, quantized, ragged_with_empties, same_results, state, stored
+import bound_cases as bc
+from bound_cases import case_queries, corpus_of as _corpus, ragged_with_empties, same_results, state
+from test_gpu_bound_pass import EXP5, _Env
 from vectorian_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -30,40 +32,18 @@ TILE8 = 12 * 1024 + 128
 GAPS = {"linear": (0.1, 0.1), "exp5": (EXP5, EXP5)}
 
 
-class Pair:
+class Pair(bc.Pair):
 	"""the same vectors twice: `forced` has a shadow, `exact` has none"""
 
 	def __init__(self, hip, corpus):
-		self.corpus = corpus
-		self.X = corpus["X"]
-		self.off = np.asarray(corpus["sent_off"], dtype=np.int64)
-		self.n = len(self.off) - 1
-		with _Env("off"):
-			self.exact = _corpus(hip, self.X, self.off)
-		with _Env("force"):
-			self.forced = _corpus(hip, self.X, self.off)
+		super().__init__(hip, _Env, corpus)
 		# the shadow is counted: 12 KiB + 128 bytes per tile of 16 tokens beside 24 KiB
 		assert self.forced.device_bytes - self.exact.device_bytes >= (self.X.shape[0] // 16) * TILE8
-		e, n, a = quantized(stored(self.X))
-		self.quant = (e.max(), n.max(), a.max())
-
-	def close(self):
-		self.forced.close()
-		self.exact.close()
 
 
 def round2_limit(pair, qv, full, k, min_score):
 	"""(delta, the most slices round 2 can hold): round2_limit of the 300-d module with d_pad = 768 in gamma"""
-	e_x, N, X = pair.quant
-	e_q, _, a_q = quantized(stored(qv))
-	gamma = 2 * D_PAD * 2.0 ** -24 * a_q * X + 2e-6
-	delta = float((2 * (e_x * a_q + e_q * N) + gamma).max()) * (1 + 1e-5) + 2e-5
-	floor = min_score - 1e-5 * max(1.0, abs(min_score))
-	kk = min(k + 8, pair.n)
-	above = np.sort(full[full > floor])[::-1]
-	if len(above) >= kk and above[kk - 1] - delta > floor:
-		return delta, int((full >= above[kk - 1] - 2 * delta).sum())
-	return delta, int((full > floor - delta).sum())
+	return bc.round2_limit8(pair, qv, full, k, min_score, D_PAD)
 
 
 def check(hip, pair, qv, expect_fallback=False, **kw):

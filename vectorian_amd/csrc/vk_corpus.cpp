@@ -429,29 +429,20 @@ int vk_corpus_set_slices(vk_corpus_t *c, const int64_t *start, const int64_t *en
 	return set_slices_impl(c, start, end, n_sentences, false);
 }
 
-// The 8-bit shadow of the token rows: contextual bf16 rows whose exact kernel is one of the two compile-time forms that
-// rescore the contenders -- 289 .. 304 features (d_pad = 304, the 300-d form: five K-steps of 64 int8, 5,248 bytes per tile) and
-// 753 .. 768 features (d_pad = 768, the 768-d form: twelve K-steps, 12,416 bytes per tile) --
-// every slice within VK_FAST_SENT_LEN tokens.  Never an error: without the memory (or with a row that is not finite) the corpus has
-// no shadow and its queries take the exact pass.
+// The shadow of the token rows in the format vk_host::shadow_format_of gives this corpus -- none for most -- with every slice
+// within VK_FAST_SENT_LEN tokens.  Never an error: without the memory (or with a row that is not finite) the corpus has no shadow and
+// its queries take the exact pass.
 static void build_shadow(vk_corpus *c) {
 	const int mode = bound_pass_mode();
 	if (mode < 0 || (mode == 0 && c->desc.n_sentences < kBoundPassMinSentences)) return;
-	if (c->desc.layout != VK_LAYOUT_CONTEXTUAL || c->prec != 0 || c->max_len > VK_FAST_SENT_LEN || c->n_entries < 1) return;
-	int nk64 = (c->nk32 == 10 && c->tail == 1) ? 5 : (c->nk32 == 24 && c->tail == 0) ? 12 : 0;
-	if (nk64 == 0) return;
-	// the 300-d form in six bits: three K-steps of 128 E2M3 codes, of the last only the quarters of 32 that hold features
-	const bool six = nk64 == 5 && bound_bits_wanted(mode) == 6;
-	const int live6 = (c->desc.d - 128 * (VK_DEV_FP6_STEPS - 1) + 31) / 32;   // 2 for 289 .. 304 features
-	if (six) nk64 = VK_DEV_FP6_STEPS;
-	const int tile_bytes = six ? VK_DEV_FP6_TILE_BYTES(live6) : nk64 * 1024 + 128;
-	const size_t bytes = (size_t)c->n_tiles * tile_bytes;
+	if (c->max_len > VK_FAST_SENT_LEN || c->n_entries < 1) return;
+	const vk_host::shadow_format f = vk_host::shadow_format_of(c->desc.d, c->nk32, c->tail, c->prec, c->desc.layout, bound_bits_wanted(mode));
+	if (f.bits == 0) return;
+	const size_t bytes = (size_t)c->n_tiles * f.tile_bytes();
 	uint8_t *sh = nullptr;
 	if (c->d_counter.reserve(4, &c->device_bytes) || alloc_shared(c, &sh, bytes)) { (void)hipGetLastError(); return; }
 	uint32_t stats[4] = {0, 0, 1, 0};
-	const hipError_t launched = six ? vk_launch_shadow6(c->d_tiles, c->n_tiles, c->rows_total, c->desc.d, c->tile_bytes, live6, sh, c->d_counter, c->stream)
-		: vk_launch_shadow(c->d_tiles, c->n_tiles, c->rows_total, c->desc.d, c->tile_bytes, nk64, sh, c->d_counter, c->stream);
-	const bool ran = launched == hipSuccess
+	const bool ran = vk_launch_shadow(c->d_tiles, c->n_tiles, c->rows_total, c->tile_bytes, &f, sh, c->d_counter, c->stream) == hipSuccess
 		&& hipMemcpyAsync(stats, c->d_counter, 16, hipMemcpyDeviceToHost, c->stream) == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;
 	if (!ran || stats[2] != 0) {
 		(void)hipGetLastError();
@@ -459,9 +450,7 @@ static void build_shadow(vk_corpus *c) {
 		c->device_bytes -= (int64_t)bytes;
 		return;
 	}
-	c->shadow = sh; c->shadow_nk64 = nk64; c->shadow_tile_bytes = tile_bytes;
-	c->shadow_bits = six ? 6 : 8;
-	c->shadow_live = six ? live6 : (c->desc.d - 64 * (nk64 - 1) + 15) / 16;   // 1 .. 4 (d_pad - 15 <= d <= d_pad for both forms)
+	c->shadow = sh; c->shadow_format = f;
 	memcpy(&c->shadow_n, &stats[0], 4);
 	memcpy(&c->shadow_x, &stats[1], 4);
 }
@@ -628,7 +617,27 @@ int vk_bound_pass_state(vk_corpus_t *c, float *bounds, int64_t n, int64_t *count
 // the format of every bound pass vk_bound_pass_state reports on
 int vk_bound_pass_bits(vk_corpus_t *c, int64_t *bits) {
 	if (!c || !bits) return fail(VK_ERR_INVALID, "null argument");
-	*bits = c->shadow ? c->shadow_bits : 0;
+	*bits = c->shadow ? c->shadow_format.bits : 0;
+	return VK_OK;
+}
+
+// Internal (tests; not part of the ABI): the handle's shadow as the device holds it.  format[5]: bits (0: no shadow, the rest zero
+// then), K-steps per tile, live quarters of the last K-step, bytes per tile, tiles (the zero tile behind the corpus included);
+// nx[2]: the corpus-wide constants N and X.  out (null: none wanted): the bytes of tiles tile0 .. tile0 + n - 1.
+int vk_bound_pass_shadow(vk_corpus_t *c, int64_t *format, float *nx, int64_t tile0, int64_t n, uint8_t *out) {
+	if (!c || !format || !nx) return fail(VK_ERR_INVALID, "null argument");
+	const vk_host::shadow_format &sf = c->shadow_format;
+	const int64_t f[5] = {sf.bits, sf.steps, sf.live, sf.tile_bytes(), c->n_tiles};
+	memset(format, 0, sizeof f);
+	nx[0] = nx[1] = 0.0f;
+	if (!c->shadow) return out ? fail(VK_ERR_STATE, "the corpus has no shadow") : VK_OK;
+	memcpy(format, f, sizeof f);
+	nx[0] = c->shadow_n; nx[1] = c->shadow_x;
+	if (!out) return VK_OK;
+	if (tile0 < 0 || n < 0 || tile0 > c->n_tiles || n > c->n_tiles - tile0) return fail(VK_ERR_INVALID, "tiles out of range");
+	VK_HIP(hipSetDevice(c->device));
+	VK_HIP(hipStreamSynchronize(c->stream));
+	if (n > 0) VK_HIP(hipMemcpy(out, c->shadow + tile0 * sf.tile_bytes(), (size_t)n * sf.tile_bytes(), hipMemcpyDeviceToHost));
 	return VK_OK;
 }
 
@@ -668,8 +677,7 @@ int vk_i8_bound_tile_probe(const int8_t *q, const int8_t *x, int32_t nk64, int32
 	std::vector<uint8_t> pk(2 * tb);
 	for (int side = 0; side < 2; side++)
 		for (int i = 0; i < 16; i++)
-			for (int k = 0; k < nk64 * 64; k++)
-				pk[side * tb + (size_t)(k >> 6) * 1024 + (size_t)(((k & 63) >> 4) * 16 + i) * 16 + (size_t)(k & 15)] = (uint8_t)(side ? x : q)[(size_t)i * nk64 * 64 + k];
+			vk_host::i8_put_row(pk.data() + side * tb, i, (const uint8_t *)(side ? x : q) + (size_t)i * nk64 * 64, nk64 * 64);
 	VK_HIP(hipMemcpy(d, pk.data(), 2 * tb, hipMemcpyHostToDevice));
 	VK_HIP(vk_launch_i8_bound_probe(d, d + tb, nk64, live, (int32_t *)(d + 2 * tb), nullptr));
 	VK_HIP(hipDeviceSynchronize());

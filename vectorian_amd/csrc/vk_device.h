@@ -328,6 +328,8 @@ struct VkLongqParams {
 };
 
 #ifdef __cplusplus
+namespace vk_host { struct shadow_format; }   // vk_bound_host.h
+
 extern "C" {
 #endif
 size_t vk_longq_scratch_bytes(int32_t len_t, int32_t gap_mode, int32_t flow, int32_t tagged);
@@ -354,15 +356,13 @@ size_t vk_wide_lds_demand(int32_t max_len, int32_t nq, int32_t gap_mode, int32_t
 size_t vk_wide_scratch_bytes(int32_t max_len, int32_t nq, int32_t gap_mode, int32_t flow, int32_t ring);
 int32_t vk_wide_gs_blocks(int32_t max_len, int32_t nq, int32_t gap_mode, int32_t flow_k, int64_t n_sent, int32_t ring);
 int32_t vk_wide_ring_rows(int32_t nq, int32_t gap_mode, int32_t ws_tail);
-// the 8-bit shadow of a bf16 contextual corpus (vk_pack.hip): stats = 4 words (largest |s xq|, largest |x| as float bits; not finite)
-hipError_t vk_launch_shadow(const uint8_t *tiles, int64_t n_tiles, int64_t rows_total, int32_t d, int32_t tile_bytes, int32_t nk64,
+// the shadow of a bf16 contextual corpus in the format *f (vk_bound_host.h; vk_pack.hip): tile_bytes of a token tile; stats = 4 words
+// (largest |s xq|, largest |x| as float bits; not finite)
+hipError_t vk_launch_shadow(const uint8_t *tiles, int64_t n_tiles, int64_t rows_total, int32_t tile_bytes, const vk_host::shadow_format *f,
 	uint8_t *shadow, uint32_t *stats, hipStream_t stream);
 // one shadow tile through dot_tile_i8<nk64> (5 or 12) with `live` quarters of the last block fetched: out[16 j + i] (vk_pack.hip; tests)
 hipError_t vk_launch_i8_bound_probe(const uint8_t *qtile8, const uint8_t *tile8, int32_t nk64, int32_t live, int32_t *out, hipStream_t stream);
 hipError_t vk_launch_i8_probe(const int8_t *q, const int8_t *x, int32_t *out, hipStream_t stream);
-// the 6-bit shadow (MODE 8): tiles of VK_DEV_FP6_TILE_BYTES(live6); stats as vk_launch_shadow's
-hipError_t vk_launch_shadow6(const uint8_t *tiles, int64_t n_tiles, int64_t rows_total, int32_t d, int32_t tile_bytes, int32_t live6,
-	uint8_t *shadow, uint32_t *stats, hipStream_t stream);
 // one 6-bit query tile (VK_DEV_FP6_QTILE_BYTES) against one shadow tile through dot_tile_fp6: out[16 j + i] (vk_pack.hip; tests)
 hipError_t vk_launch_fp6_bound_probe(const uint8_t *qtile6, const uint8_t *tile6, int32_t live6, float *out, hipStream_t stream);
 // rows of the keys (up to the first empty slot of `n`) as groups of four rows of the slice table (vk_score_kernel's group_list)

@@ -8,6 +8,7 @@
 #include "vk_devbuf.h"
 #include "vk_guard.h"
 #include "vk_result_host.h"
+#include "vk_bound_host.h"
 
 #include <algorithm>
 #include <atomic>
@@ -139,12 +140,10 @@ struct vk_corpus_shape {
 	// `shared` the block this handle allocates into (a view: its source's), `vectors_of` the block of the source of a filtered
 	// static corpus (its vocabulary tiles and magnitudes).  The raw pointers above are aliases into these blocks.
 	std::shared_ptr<vk_devblock> shared, vectors_of;
-	// the 8-bit shadow of the token rows (null: none), in `shared` like the tiles: shadow_nk64 K-steps of 64 int8 per tile of
-	// shadow_tile_bytes, and the corpus-wide constants of the bound -- shadow_n >= every |s_x xq|, shadow_x >= every |x|
+	// the shadow of the token rows (null: none), in `shared` like the tiles, its format (vk_bound_host.h), and the
+	// corpus-wide constants of the bound -- shadow_n >= every |s_x xq|, shadow_x >= every |x|
 	const uint8_t *shadow = nullptr;
-	int shadow_nk64 = 0, shadow_tile_bytes = 0;
-	int shadow_bits = 0;   // 0: no shadow; 8: int8 (MODE 7); 6: E2M3 (MODE 8: three K-steps of 128, shadow_nk64 = 3, shadow_live = live6)
-	int shadow_live = 4;   // quarters of a tile's last block that hold features: ceil((d - 64 (shadow_nk64 - 1)) / 16); the bound kernel fetches only those
+	vk_host::shadow_format shadow_format;
 	float shadow_n = 0.0f, shadow_x = 0.0f;
 };
 
@@ -204,7 +203,7 @@ struct vk_corpus : vk_corpus_shape {
 		VkScoreParams full{}; int full_grid = 0; size_t full_smem = 0;   // the exact pass of the last query (its workspaces stay until the next)
 		int64_t ran = 0, round1 = 0, round2 = 0, fell_back = 0;           // the last query: bound pass ran, candidates of the rounds, full pass after all
 		int64_t queries = 0, fallbacks = 0, survivors = 0;                // since the handle was made
-		vk_host::bound_backoff backoff;                                    // default mode: when the handle stops trying (vk_result_host.h)
+		vk_host::bound_backoff backoff;                                    // default mode: when the handle stops trying (vk_bound_host.h)
 	} bp;
 	vk_devbuf<int32_t> d_sb_id[2]; int64_t sb_n[2] = {0, 0}; bool sb_built = false; int64_t sb_empty = 0;
 	vk_devbuf<uint16_t> d_btable;
@@ -251,8 +250,8 @@ template <typename T> int alloc_shared(vk_corpus *c, T **p, size_t n) {
 int vk_wait_peer_turn(vk_corpus *c, hipStream_t st);
 int vk_validate_query(const vk_corpus *c, const vk_query_desc *q, const vk_topk_out *out);
 int vk_longq_query(vk_corpus *c, const vk_query_desc *q, vk_topk_out *out, vk_host_keep &keep);   // vk_longq_host.cpp
-// tile8: with a shadow, the query's 8-bit tile and the cells' constants behind it (left empty when a row is not finite)
-void vk_pack_query(const vk_corpus *c, const vk_query_desc *q, std::vector<uint8_t> &tile, float *mags, std::vector<uint8_t> *tile8 = nullptr);
+// bound_tile: with a shadow, the query's tile in the shadow's format and the cells' constants behind it (left empty when a row is not finite)
+void vk_pack_query(const vk_corpus *c, const vk_query_desc *q, std::vector<uint8_t> &tile, float *mags, std::vector<uint8_t> *bound_tile = nullptr);
 
 // ---- steps the query paths share (vk_query.cpp, vk_longq_host.cpp, vk_batch.cpp); the rules without a device are in vk_result_host.h
 namespace {

@@ -1,6 +1,6 @@
 // vk_pack.hip -- corpus upload (normalise, round, tile order) and the per-query table of the static layout.
 #include "vk_common.hip.h"
-#include "vk_result_host.h"   // the integer helpers of the 6-bit shadow (host and device)
+#include "vk_bound_host.h"   // the format of a shadow and the quantizer of a row (host and device)
 
 // ---------------------------------------------------------------------------
 // corpus upload: L2-normalise rows (Vectors.normalized, vectorian/embedding/vectors.py:71-86),
@@ -85,65 +85,85 @@ __global__ __launch_bounds__(256) void vk_pack_rows_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// The 8-bit shadow of a bf16 contextual corpus, built once at vk_corpus_finalize.  A shadow tile is 16 rows like a token
-// tile: nk64 blocks of 1 KiB in the operand order of v_mfma_i32_16x16x64_i8 (block t, lane 16 g + i: row i, features 64 t + 16 g .. + 15;
-// features >= d are zero), then 16 x (s_x, e_x) as floats.  One thread per row; the arithmetic is vk_host::quantize_row_i8
-// (vk_result_host.h) statement for statement.  stats[0] / [1]: the largest |s_x xq| / |x| of the corpus as float bits (non-negative
-// floats order as their bits), stats[2]: some element is not finite (no shadow then).
+// The shadow of a bf16 contextual corpus, built once at vk_corpus_finalize in the format vk_bound_host.h
+// describes.  One thread per row: vk_host::quantize_row on the format's grid -- the function the query's side runs on the host --
+// reading the row out of its token tile and collecting each lane's operand, which one vector store (the E2M3 grid: two) puts where
+// i8_offset / fp6_store_lane put it; features >= d are zero codes, rows past the corpus zeros throughout.  stats[0] / [1]: the
+// largest |s_x xq| / |x| of the corpus as float bits (non-negative floats order as their bits), stats[2]: some element is not
+// finite (no shadow then).
 // ---------------------------------------------------------------------------
 
-__device__ __forceinline__ float quant_up_dev(double x) {
-	if (!(x > 0.0)) return 0.0f;
-	const float f = (float)(x * (1.0 + 1e-6));
-	return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, f) + 1u);   // nextafterf(f, +inf) of a positive finite float
-}
+// the operand a lane collects, code by code (its place in the operand is a constant once quantize_row's loop is unrolled), and stores
+// when it is whole.  int8: sixteen codes, one uint4
+template <typename Grid> struct lane_operand;
+template <> struct lane_operand<vk_host::grid_i8> {
+	uint32_t w[4];
+	__device__ __forceinline__ void put(const vk_host::shadow_format &, uint8_t *dst, int i, int k, int code) {
+		const int j = k & 15;
+		if ((j & 3) == 0) w[j >> 2] = 0u;
+		w[j >> 2] |= ((uint32_t)code & 255u) << ((j & 3) * 8);
+		if (j == 15) *reinterpret_cast<uint4 *>(dst + vk_host::i8_offset(i, k - 15)) = uint4{w[0], w[1], w[2], w[3]};
+	}
+};
+// E2M3: thirty-two codes through the host's packer, a uint4 and a uint2
+template <> struct lane_operand<vk_host::grid_e2m3> {
+	uint8_t codes[32];
+	__device__ __forceinline__ void put(const vk_host::shadow_format &f, uint8_t *dst, int i, int k, int code) {
+		const int j = k & 31;
+		codes[j] = (uint8_t)code;
+		if (j != 31) return;
+		uint32_t w[6];
+		vk_host::fp6_pack32(codes, w);
+		const int t = k >> 7, quarters = t == f.steps - 1 ? f.kept : 4, lane = 16 * ((k & 127) >> 5) + i;
+		uint8_t *step = dst + t * f.step_bytes();
+		*reinterpret_cast<uint4 *>(step + lane * 16) = uint4{w[0], w[1], w[2], w[3]};
+		*reinterpret_cast<uint2 *>(step + quarters * 256 + lane * 8) = uint2{w[4], w[5]};
+	}
+};
 
-__global__ __launch_bounds__(256) void vk_shadow_kernel(const uint8_t *__restrict__ tiles, int64_t n_tiles, int64_t rows_total, int32_t d,
-	int32_t tile_bytes, int32_t nk64, uint8_t *__restrict__ shadow, uint32_t *__restrict__ stats) {
+template <typename Grid>
+__global__ __launch_bounds__(256) void vk_shadow_kernel(const uint8_t *__restrict__ tiles, int64_t n_tiles, int64_t rows_total, int32_t tile_bytes,
+	const vk_host::shadow_format f, uint8_t *__restrict__ shadow, uint32_t *__restrict__ stats) {
 	const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (row >= n_tiles * 16) return;
 	const int i = (int)(row & 15);
 	const uint8_t *src = tiles + (row >> 4) * (int64_t)tile_bytes;
-	const int64_t sh_bytes = (int64_t)nk64 * 1024 + 128;
-	uint8_t *dst = shadow + (row >> 4) * sh_bytes;
-	const int dk = row < rows_total ? d : 0;   // rows past the corpus (the tile's padding, the zero tile): zeros
-	float m = 0.0f;
+	uint8_t *dst = shadow + (row >> 4) * (int64_t)f.tile_bytes();
+	const int dk = row < rows_total ? f.d : 0;   // rows past the corpus (the tile's padding, the zero tile): zeros
 	bool bad = false;
-	for (int k = 0; k < dk; k++) {
-		const float x = tile_elem(src, i, k, 0);
-		bad = bad || !(fabsf(x) <= 3.4028234e38f);
-		m = fmaxf(m, fabsf(x));
-	}
-	const float s = m / 127.0f;
-	double e2 = 0.0, n2 = 0.0, a2 = 0.0;
-	for (int c = 0; c < nk64 * 4; c++) {   // chunks of 16 features: block c >> 2, lane group c & 3
-		uint32_t w[4] = {0u, 0u, 0u, 0u};
-		for (int j = 0; j < 16; j++) {
-			const int k = c * 16 + j;
-			if (k >= dk) break;
+	lane_operand<Grid> op;
+	const vk_host::quant_meta m = vk_host::quantize_row<Grid>(dk, f.width(),
+		[&](int k) {
 			const float x = tile_elem(src, i, k, 0);
-			int v = 0;
-			if (s > 0.0f) v = (int)fminf(127.0f, fmaxf(-127.0f, nearbyintf(x / s)));
-			const double xs = (double)s * (double)v, dd = (double)x - xs;
-			e2 += dd * dd; n2 += xs * xs; a2 += (double)x * (double)x;
-			w[j >> 2] |= ((uint32_t)v & 255u) << ((j & 3) * 8);
-		}
-		*reinterpret_cast<uint4 *>(dst + (c >> 2) * 1024 + ((c & 3) * 16 + i) * 16) = uint4{w[0], w[1], w[2], w[3]};
-	}
-	const float e = quant_up_dev(sqrt(e2)), nn = quant_up_dev(sqrt(n2)), a = quant_up_dev(sqrt(a2));
-	*reinterpret_cast<float2 *>(dst + (int64_t)nk64 * 1024 + i * 8) = float2{s, e};
+			bad = bad || !(fabsf(x) <= 3.4028234e38f);
+			return x;
+		},
+		[&](int k, int code) { op.put(f, dst, i, k, code); });
+	*reinterpret_cast<float2 *>(dst + f.meta_offset() + i * 8) = float2{m.s, m.e};
 	if (bad) atomicOr(stats + 2, 1u);
 	else {
-		atomicMax(stats + 0, __builtin_bit_cast(uint32_t, nn));
-		atomicMax(stats + 1, __builtin_bit_cast(uint32_t, a));
+		atomicMax(stats + 0, __builtin_bit_cast(uint32_t, m.n));
+		atomicMax(stats + 1, __builtin_bit_cast(uint32_t, m.a));
 	}
 }
 
-extern "C" hipError_t vk_launch_shadow(const uint8_t *tiles, int64_t n_tiles, int64_t rows_total, int32_t d, int32_t tile_bytes, int32_t nk64,
+// the host's description of the 6-bit form is the one the bound kernel is compiled with (vk_device.h), at every number of live quarters
+constexpr vk_host::shadow_format fmt6_of(int d) { return vk_host::shadow_format_of(d, 10, 1, 0, VK_LAYOUT_CONTEXTUAL, 6); }
+constexpr bool fmt6_is_the_devices(int d, int live) {
+	return fmt6_of(d).live == live && fmt6_of(d).steps == VK_DEV_FP6_STEPS && fmt6_of(d).step_bytes() == VK_DEV_FP6_STEP_BYTES
+		&& fmt6_of(d).tile_bytes() == VK_DEV_FP6_TILE_BYTES(live) && fmt6_of(d).qtile_bytes() == VK_DEV_FP6_QTILE_BYTES;
+}
+static_assert(fmt6_is_the_devices(257, 1) && fmt6_is_the_devices(289, 2) && fmt6_is_the_devices(304, 2) && fmt6_is_the_devices(321, 3) && fmt6_is_the_devices(384, 4),
+	"vk_host::shadow_format and VK_DEV_FP6_*");
+
+extern "C" hipError_t vk_launch_shadow(const uint8_t *tiles, int64_t n_tiles, int64_t rows_total, int32_t tile_bytes, const vk_host::shadow_format *f,
 	uint8_t *shadow, uint32_t *stats, hipStream_t stream) {
+	if (f->bits == 0 || f->live < 1 || f->live > 4 || f->kept < f->live || f->kept > 4 || f->d > f->width()) return hipErrorInvalidValue;
 	hipError_t e = hipMemsetAsync(stats, 0, 16, stream);
 	if (e != hipSuccess) return e;
-	vk_shadow_kernel<<<(unsigned)((n_tiles * 16 + 255) / 256), 256, 0, stream>>>(tiles, n_tiles, rows_total, d, tile_bytes, nk64, shadow, stats);
+	const unsigned grid = (unsigned)((n_tiles * 16 + 255) / 256);
+	if (f->bits == 8) vk_shadow_kernel<vk_host::grid_i8><<<grid, 256, 0, stream>>>(tiles, n_tiles, rows_total, tile_bytes, *f, shadow, stats);
+	else vk_shadow_kernel<vk_host::grid_e2m3><<<grid, 256, 0, stream>>>(tiles, n_tiles, rows_total, tile_bytes, *f, shadow, stats);
 	return hipGetLastError();
 }
 
@@ -180,78 +200,6 @@ extern "C" hipError_t vk_launch_i8_bound_probe(const uint8_t *qtile8, const uint
 	if (nk64 == 5) vk_i8_bound_probe_kernel<5><<<1, 64, 0, stream>>>(qtile8, tile8, live, out);
 	else if (nk64 == 12) vk_i8_bound_probe_kernel<12><<<1, 64, 0, stream>>>(qtile8, tile8, live, out);
 	else return hipErrorInvalidValue;
-	return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// The 6-bit shadow: tiles of VK_DEV_FP6_TILE_BYTES(live6) -- two whole K-steps of 128 features, the live6 quarters of
-// the third (features >= d are zero codes), then 16 x (s_x, e_x).  One thread per row; the arithmetic is
-// vk_host::quantize_row_e2m3 statement for statement, the codes and their packing come from the host's own integer helpers
-// (vk_host::e2m3_mag_of_eighths, fp6_pack32: compiled for both sides), laid out as vk_host::fp6_put_row lays them out.  stats as vk_shadow_kernel's.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void vk_shadow6_kernel(const uint8_t *__restrict__ tiles, int64_t n_tiles, int64_t rows_total, int32_t d,
-	int32_t tile_bytes, int32_t live6, uint8_t *__restrict__ shadow, uint32_t *__restrict__ stats) {
-	const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (row >= n_tiles * 16) return;
-	const int i = (int)(row & 15);
-	const uint8_t *src = tiles + (row >> 4) * (int64_t)tile_bytes;
-	uint8_t *dst = shadow + (row >> 4) * (int64_t)VK_DEV_FP6_TILE_BYTES(live6);
-	const int dk = row < rows_total ? d : 0;   // rows past the corpus (the tile's padding, the zero tile): zeros
-	float m = 0.0f;
-	bool bad = false;
-	for (int k = 0; k < dk; k++) {
-		const float x = tile_elem(src, i, k, 0);
-		bad = bad || !(fabsf(x) <= 3.4028234e38f);
-		m = fmaxf(m, fabsf(x));
-	}
-	const float s = m / 7.5f;
-	double e2 = 0.0, n2 = 0.0, a2 = 0.0;
-	for (int t = 0; t < VK_DEV_FP6_STEPS; t++) {
-		const int quarters = t == VK_DEV_FP6_STEPS - 1 ? live6 : 4;
-		for (int g = 0; g < quarters; g++) {   // a lane's operand: the codes of 32 features, packed by the host's packer
-			uint8_t codes[32];
-			for (int j = 0; j < 32; j++) {
-				const int k = 128 * t + 32 * g + j;
-				int code = 0;
-				if (k < dk) {
-					const float x = tile_elem(src, i, k, 0);
-					float v = 0.0f;
-					if (s > 0.0f) {
-						const float tt = fminf(7.5f, fabsf(x / s));
-						const float step = tt < 2.0f ? 0.125f : tt < 4.0f ? 0.25f : 0.5f;
-						const float a = fminf(7.5f, nearbyintf(tt / step) * step);
-						const int mag = vk_host::e2m3_mag_of_eighths((int)(a * 8.0f));
-						code = mag | ((x < 0.0f && mag != 0) ? 32 : 0);
-						v = x < 0.0f ? -a : a;
-					}
-					const double xs = (double)s * (double)v, dd = (double)x - xs;
-					e2 += dd * dd; n2 += xs * xs; a2 += (double)x * (double)x;
-				}
-				codes[j] = (uint8_t)code;
-			}
-			uint32_t w[6];
-			vk_host::fp6_pack32(codes, w);
-			uint8_t *step = dst + t * VK_DEV_FP6_STEP_BYTES;   // fp6_store_lane's places, as vector stores
-			const int lane = 16 * g + i;
-			*reinterpret_cast<uint4 *>(step + lane * 16) = uint4{w[0], w[1], w[2], w[3]};
-			*reinterpret_cast<uint2 *>(step + quarters * 256 + lane * 8) = uint2{w[4], w[5]};
-		}
-	}
-	const float e = quant_up_dev(sqrt(e2)), nn = quant_up_dev(sqrt(n2)), a = quant_up_dev(sqrt(a2));
-	*reinterpret_cast<float2 *>(dst + (VK_DEV_FP6_TILE_BYTES(live6) - 128) + i * 8) = float2{s, e};
-	if (bad) atomicOr(stats + 2, 1u);
-	else {
-		atomicMax(stats + 0, __builtin_bit_cast(uint32_t, nn));
-		atomicMax(stats + 1, __builtin_bit_cast(uint32_t, a));
-	}
-}
-
-extern "C" hipError_t vk_launch_shadow6(const uint8_t *tiles, int64_t n_tiles, int64_t rows_total, int32_t d, int32_t tile_bytes, int32_t live6,
-	uint8_t *shadow, uint32_t *stats, hipStream_t stream) {
-	if (live6 < 1 || live6 > 4 || d > 128 * (VK_DEV_FP6_STEPS - 1) + 32 * live6) return hipErrorInvalidValue;
-	hipError_t e = hipMemsetAsync(stats, 0, 16, stream);
-	if (e != hipSuccess) return e;
-	vk_shadow6_kernel<<<(unsigned)((n_tiles * 16 + 255) / 256), 256, 0, stream>>>(tiles, n_tiles, rows_total, d, tile_bytes, live6, shadow, stats);
 	return hipGetLastError();
 }
 

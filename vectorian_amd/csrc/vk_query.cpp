@@ -147,7 +147,7 @@ int vk_validate_query(const vk_corpus *c, const vk_query_desc *q, const vk_topk_
 
 // Vectors.normalized for the query rows, then bf16 (RNE), then tile order (16 rows,
 // rows >= len_t zero).  Same arithmetic as oracle/vk_oracle.c vko_normalize_rows_bf16.
-void vk_pack_query(const vk_corpus *c, const vk_query_desc *q, std::vector<uint8_t> &tile, float *mags, std::vector<uint8_t> *tile8) {
+void vk_pack_query(const vk_corpus *c, const vk_query_desc *q, std::vector<uint8_t> &tile, float *mags, std::vector<uint8_t> *bound_tile) {
 	const int d = c->desc.d;
 	tile.assign((size_t)c->tile_bytes * (size_t)((q->len_t + 15) / 16), 0);   // tile i / 16 holds row i % 16
 	std::vector<float> row((size_t)d);
@@ -179,46 +179,17 @@ void vk_pack_query(const vk_corpus *c, const vk_query_desc *q, std::vector<uint8
 			memcpy(&tile[off], &b, 2);
 		}
 	}
-	// The bound pass: the rows as stored (bf16) quantized like the shadow's, in the operand order of the 8-bit MFMA (block
-	// k / 64, lane 16 ((k % 64) / 16) + row, byte k % 16), then cs[16], ca[16], cb[16] -- zeros for the rows past the query, so that
-	// their cells are the exact kernel's zeros.
-	if (!tile8 || !c->shadow || c->prec || q->len_t > VK_FAST_QUERY_LEN) return;
-	if (c->shadow_bits == 6) {
-		// the 6-bit form: E2M3 codes by the shadow's quantizer and packer, all three K-steps whole (zeros past d), the same
-		// constants behind them -- gamma with the exact kernel's d_pad (320), which the shadow's format does not change
-		std::vector<uint8_t> t6((size_t)VK_DEV_FP6_QTILE_BYTES + 3 * 16 * 4, 0);
-		std::vector<uint8_t> codes((size_t)d);
-		float *cst6 = reinterpret_cast<float *>(t6.data() + (size_t)VK_DEV_FP6_QTILE_BYTES);
-		for (int i = 0; i < q->len_t; i++) {
-			for (int k = 0; k < d; k++) {
-				uint16_t b;
-				memcpy(&b, &tile[(size_t)(k >> 5) * 1024 + (size_t)(((k & 31) >> 3) * 16 + i) * 16 + (size_t)(k & 7) * 2], 2);
-				row[(size_t)k] = bf16_to_f32(b);
-				if (!(std::fabs(row[(size_t)k]) <= 3.4028234e38f)) return;   // not finite: no bound for this query
-			}
-			const vk_host::quant_meta m = vk_host::quantize_row_e2m3(row.data(), d, codes.data());
-			vk_host::fp6_put_row(t6.data(), 4, i, codes.data(), d);
-			vk_host::bound_cell_constants(m, c->shadow_n, c->shadow_x, 320, &cst6[i], &cst6[16 + i], &cst6[32 + i]);
-		}
-		tile8->swap(t6);
-		return;
-	}
-	const int nk64 = c->shadow_nk64;
-	std::vector<uint8_t> t8((size_t)nk64 * 1024 + 3 * 16 * 4, 0);
-	std::vector<int8_t> xq((size_t)d);
-	float *cst = reinterpret_cast<float *>(t8.data() + (size_t)nk64 * 1024);
-	for (int i = 0; i < q->len_t; i++) {
+	// The bound pass: the rows as stored (bf16), read back from the tile, in the format of the corpus's shadow with the
+	// cells' constants behind them (vk_host::pack_bound_query)
+	if (!bound_tile || !c->shadow || c->prec || q->len_t > VK_FAST_QUERY_LEN) return;
+	std::vector<float> stored((size_t)q->len_t * d);
+	for (int i = 0; i < q->len_t; i++)
 		for (int k = 0; k < d; k++) {
 			uint16_t b;
 			memcpy(&b, &tile[(size_t)(k >> 5) * 1024 + (size_t)(((k & 31) >> 3) * 16 + i) * 16 + (size_t)(k & 7) * 2], 2);
-			row[(size_t)k] = bf16_to_f32(b);
-			if (!(std::fabs(row[(size_t)k]) <= 3.4028234e38f)) return;   // not finite: no bound for this query
+			stored[(size_t)i * d + k] = bf16_to_f32(b);
 		}
-		const vk_host::quant_meta m = vk_host::quantize_row_i8(row.data(), d, xq.data());
-		for (int k = 0; k < d; k++) t8[(size_t)(k >> 6) * 1024 + (size_t)(((k & 63) >> 4) * 16 + i) * 16 + (size_t)(k & 15)] = (uint8_t)xq[(size_t)k];
-		vk_host::bound_cell_constants(m, c->shadow_n, c->shadow_x, nk64 * 64, &cst[i], &cst[16 + i], &cst[32 + i]);
-	}
-	tile8->swap(t8);
+	vk_host::pack_bound_query(c->shadow_format, stored.data(), q->len_t, c->shadow_n, c->shadow_x, *bound_tile);
 }
 
 // The bound pass and its two rounds in place of the exact pass `p` over every slice: afterwards d_scores (and d_raw when
@@ -242,7 +213,8 @@ static int score_bounded(vk_corpus *c, const VkScoreParams &p, int grid, size_t 
 	if ((rc = c->d_bound_keys.reserve((size_t)2 * kTopkChunk, &c->device_bytes))) return rc;
 	if ((rc = c->d_counter.reserve(4, &c->device_bytes))) return rc;
 	VkScoreParams pb = p;
-	pb.tiles = c->shadow; pb.nk32 = c->shadow_nk64; pb.tail = 0; pb.tile_bytes = c->shadow_tile_bytes; pb.bound_bits = c->shadow_bits; pb.bound_live = c->shadow_live;
+	const vk_host::shadow_format &sf = c->shadow_format;
+	pb.tiles = c->shadow; pb.nk32 = sf.steps; pb.tail = 0; pb.tile_bytes = sf.tile_bytes(); pb.bound_bits = sf.bits; pb.bound_live = sf.live;
 	pb.q_mode3 = 0; pb.q_lds = 0; pb.qtile = c->d_qtile8; pb.scores = c->d_ub; pb.raw = nullptr;
 	VK_HIP(vk_launch_score(&pb, grid, smem_bound, st));
 	VK_HIP(hipEventRecord(c->ev[2], st));
@@ -757,7 +729,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		// cells' constants behind it -- the region MODE 7 of vk_score_kernel steps over (NK32 KiB + VK_DEV_BOUND_CONST_BYTES)
 		const size_t smem_strips = smem - qlds - (size_t)p.q_lds;
 		// (MODE 8: the 6-bit query tile, VK_DEV_FP6_QTILE_BYTES)
-		const size_t smem_bound = smem_strips + (c->shadow_bits == 6 ? (size_t)VK_DEV_FP6_QTILE_BYTES : (size_t)c->shadow_nk64 * 1024) + VK_DEV_BOUND_CONST_BYTES;
+		const size_t smem_bound = smem_strips + (size_t)c->shadow_format.qtile_bytes() + VK_DEV_BOUND_CONST_BYTES;
 		// the exact kernel over a group_list: one wave per workgroup, its strip and the exact query tile
 		const size_t smem_list = (size_t)lds_floats * 4 + qlds + (size_t)p.q_lds;
 		if ((rc = score_bounded(c, p, grid, smem, smem_bound, smem_list, kk, sel_floor, keep, st, &d_sel_bounded))) return rc;

@@ -6,19 +6,13 @@
 #define VK_RESULT_HOST_H
 
 #include "../../include/vectorian_hip.h"
+#include "vk_bound_host.h"   // the bound pass's host rules, for the programs that include this header to reach them
 
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <vector>
-
-// the integer helpers of the 6-bit shadow are compiled for the device too (vk_shadow6_kernel calls them)
-#ifdef __HIPCC__
-#define VK_HOST_DEVICE __host__ __device__
-#else
-#define VK_HOST_DEVICE
-#endif
 
 namespace vk_host {
 
@@ -119,124 +113,6 @@ inline void wt_with_closure(float *wt, const vk_gap &gap_t, int len_t, bool is_a
 	for (int k = 2; k <= len_t && k < 80; k++)
 		for (int a = 1; a < k; a++) wt[80 + k] = std::min(wt[80 + k], wt[80 + a] + wt[80 + k - a]);
 }
-
-// ---- the 8-bit bound pass: the quantizer of one row x (the bf16 values as stored, handed over as floats).
-// s = max|x| / 127, xq[k] = round(x[k] / s) (to nearest even, within -127 .. 127); e >= |x - s xq|, n >= |s xq|, a >= |x| (Euclidean
-// norms, summed in double in k order, then rounded UP to float: quant_up).  A row of zeros gives zeros throughout.  The shadow's builder
-// (vk_shadow_kernel, vk_pack.hip) is this function statement for statement.
-struct quant_meta { float s = 0.0f, e = 0.0f, n = 0.0f, a = 0.0f; };
-inline float quant_up(double x) {
-	if (!(x > 0.0)) return 0.0f;
-	return std::nextafterf((float)(x * (1.0 + 1e-6)), INFINITY);
-}
-inline quant_meta quantize_row_i8(const float *x, int d, int8_t *xq) {
-	float m = 0.0f;
-	for (int k = 0; k < d; k++) m = std::max(m, std::fabs(x[k]));
-	quant_meta r;
-	r.s = m / 127.0f;
-	double e2 = 0.0, n2 = 0.0, a2 = 0.0;
-	for (int k = 0; k < d; k++) {
-		int v = 0;
-		if (r.s > 0.0f) v = (int)std::min(127.0f, std::max(-127.0f, std::nearbyintf(x[k] / r.s)));
-		xq[k] = (int8_t)v;
-		const double xs = (double)r.s * (double)v, dd = (double)x[k] - xs;
-		e2 += dd * dd; n2 += xs * xs; a2 += (double)x[k] * (double)x[k];
-	}
-	r.e = quant_up(std::sqrt(e2)); r.n = quant_up(std::sqrt(n2)); r.a = quant_up(std::sqrt(a2));
-	return r;
-}
-// The constants of query column j in a cell of the bound pass, ub = clip01((s_x cs) I + e_x ca + cb) (I the exact integer product):
-// cs = s_q, ca = a_q, cb = e_q N + gamma, with N >= every |s_x xq| of the corpus and X >= every |x| of it.  gamma:
-// twice d_pad 2^-24 a_q X for the fp32 accumulation of the exact kernel's MFMA cosine and the five roundings of the bound's own
-// evaluation, plus 2e-6 absolute for the same roundings near zero.  Rounded up.
-inline void bound_cell_constants(const quant_meta &q, float N, float X, int d_pad, float *cs, float *ca, float *cb) {
-	const double gamma = 2.0 * (double)d_pad * std::ldexp(1.0, -24) * (double)q.a * (double)X + 2e-6;
-	*cs = q.s; *ca = q.a;
-	*cb = quant_up((double)q.e * (double)N + gamma);
-}
-
-// ---- the 6-bit bound pass: E2M3 codes, bit 5 the sign, bits 4 .. 0 the magnitude: 0 .. 1.875 in steps of 0.125 (codes
-// 0 .. 15), 2 .. 3.75 in steps of 0.25 (16 .. 23), 4 .. 7.5 in steps of 0.5 (24 .. 31) -- the operand format of
-// v_mfma_scale_f32_16x16x128_f8f6f4 with cbsz = blgp = 2.  No code is an infinity or a NaN.
-VK_HOST_DEVICE inline int e2m3_eighths(int code) {   // 8 x the value: an integer, |.| <= 60
-	const int mag = code & 31, e = mag >> 3, f = mag & 7;
-	const int n = e == 0 ? f : (8 + f) << (e - 1);
-	return (code & 32) ? -n : n;
-}
-// the magnitude bits of the grid value n8 / 8 (n8 = 0 .. 15, an even number up to 30, a multiple of 4 up to 60)
-VK_HOST_DEVICE inline int e2m3_mag_of_eighths(int n8) {
-	return n8 < 16 ? n8 : n8 < 32 ? 16 + ((n8 - 16) >> 1) : 24 + ((n8 - 32) >> 2);
-}
-// The quantizer of one row (the bf16 values as stored): s = max|x| / 7.5, xq[k] the code of the grid value nearest to x[k] / s -- a
-// tie at the midpoint of a step goes to the even multiple of that step (nearbyintf), magnitudes clip to 7.5; e, n, a as quantize_row_i8
-// gives them, with s x^ the value of the code.  A row of zeros gives zeros throughout.  The builder of the 6-bit shadow
-// (vk_shadow6_kernel, vk_pack.hip) is this function statement for statement in its floating-point part and calls the same integer
-// helpers (e2m3_mag_of_eighths, fp6_pack32).
-inline quant_meta quantize_row_e2m3(const float *x, int d, uint8_t *xq) {
-	float m = 0.0f;
-	for (int k = 0; k < d; k++) m = std::max(m, std::fabs(x[k]));
-	quant_meta r;
-	r.s = m / 7.5f;
-	double e2 = 0.0, n2 = 0.0, a2 = 0.0;
-	for (int k = 0; k < d; k++) {
-		int code = 0;
-		float v = 0.0f;
-		if (r.s > 0.0f) {
-			const float t = std::min(7.5f, std::fabs(x[k] / r.s));
-			const float step = t < 2.0f ? 0.125f : t < 4.0f ? 0.25f : 0.5f;
-			const float a = std::min(7.5f, std::nearbyintf(t / step) * step);
-			const int mag = e2m3_mag_of_eighths((int)(a * 8.0f));
-			code = mag | ((x[k] < 0.0f && mag != 0) ? 32 : 0);
-			v = x[k] < 0.0f ? -a : a;
-		}
-		xq[k] = (uint8_t)code;
-		const double xs = (double)r.s * (double)v, dd = (double)x[k] - xs;
-		e2 += dd * dd; n2 += xs * xs; a2 += (double)x[k] * (double)x[k];
-	}
-	r.e = quant_up(std::sqrt(e2)); r.n = quant_up(std::sqrt(n2)); r.a = quant_up(std::sqrt(a2));
-	return r;
-}
-// A lane's operand of one K-step: 32 codes, code j at bits 6 j .. 6 j + 5 of 192 (six words).  Stored as the tile keeps a K-step of
-// `quarters` 16-lane quarters: the first four words of lane l at 16 l, the last two behind all of those at 256 quarters + 8 l.
-VK_HOST_DEVICE inline void fp6_pack32(const uint8_t *codes, uint32_t *w) {
-	for (int i = 0; i < 6; i++) w[i] = 0u;
-	for (int j = 0; j < 32; j++) {
-		const int bit = 6 * j;
-		w[bit >> 5] |= (uint32_t)(codes[j] & 63) << (bit & 31);
-		if ((bit & 31) > 26) w[(bit >> 5) + 1] |= (uint32_t)(codes[j] & 63) >> (32 - (bit & 31));
-	}
-}
-inline void fp6_store_lane(uint8_t *step, int quarters, int lane, const uint32_t *w) {
-	memcpy(step + (size_t)lane * 16, w, 16);
-	memcpy(step + (size_t)quarters * 256 + (size_t)lane * 8, w + 4, 8);
-}
-// one row's codes (d of them, zeros beyond) into row i of a tile whose last K-step keeps `live6` quarters (4: a query tile)
-inline void fp6_put_row(uint8_t *tile, int live6, int i, const uint8_t *codes, int d) {
-	uint8_t c32[32];
-	uint32_t w[6];
-	for (int t = 0; t < 3; t++)
-		for (int g = 0; g < (t == 2 ? live6 : 4); g++) {
-			for (int j = 0; j < 32; j++) { const int k = 128 * t + 32 * g + j; c32[j] = k < d ? codes[k] : 0; }
-			fp6_pack32(c32, w);
-			fp6_store_lane(tile + (size_t)t * 1536, t == 2 ? live6 : 4, 16 * g + i, w);
-		}
-}
-
-// When a handle stops trying the bound pass: after 5 fallbacks to the full pass among its last 8 bound passes the next 64
-// queries go without one.  A stream of queries whose bounds never separate thus pays at most 8 wasted bound passes per 72 queries.
-// take(): does this query try the bound pass; record(): how the bound pass of a query that took it ended.
-struct bound_backoff {
-	uint32_t recent = 0;   // fallbacks among the last 8 bound passes, one bit each
-	int skip = 0;          // queries still to go without a bound pass
-	bool take() {
-		if (skip > 0) { skip--; return false; }
-		return true;
-	}
-	void record(bool fell_back) {
-		recent = ((recent << 1) | (fell_back ? 1u : 0u)) & 0xffu;
-		if (fell_back && __builtin_popcount(recent) >= 5) { skip = 64; recent = 0; }
-	}
-};
 
 } // namespace vk_host
 
