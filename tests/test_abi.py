@@ -78,6 +78,19 @@ def test_document_pass_sizing():
 		assert b % 256 == 0 and (n + 1) * 32 * 4 <= b <= (n + 2) * 32 * 4 + 255
 
 
+def test_internal_state_exports_are_bound():
+	"""vk_batch_state and vk_query_route (internal: the route and form of the last batch / the route of the last query, for the GPU
+	tests) are exported and refuse a null handle without touching a device"""
+	import ctypes as C
+	from vectorian_amd import core
+	lib = core.lib()
+	for name in ("vk_batch_state", "vk_query_route"):
+		fn = getattr(lib, name)
+		fn.restype = C.c_int
+		fn.argtypes = [C.c_void_p, C.c_void_p]
+		assert fn(None, None) == core.VK_ERR_INVALID
+
+
 def test_no_gpu_means_loud_failure():
 	import torch
 	if torch.cuda.is_available():

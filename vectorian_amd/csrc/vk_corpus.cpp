@@ -649,6 +649,14 @@ int vk_batch_state(vk_corpus_t *c, int64_t *state) {
 	return VK_OK;
 }
 
+// Internal (tests; not part of the ABI): the route of the last vk_query on this handle -- state[VK_QR_COUNT] in the order of
+// vk_query_route_index (all zero: no query yet)
+int vk_query_route(vk_corpus_t *c, int64_t *state) {
+	if (!c || !state) return fail(VK_ERR_INVALID, "null argument");
+	memcpy(state, c->query_route, sizeof c->query_route);
+	return VK_OK;
+}
+
 // Internal (tests): one v_mfma_i32_16x16x64_i8 on 16 x 64 int8 query rows and 16 x 64 int8 token rows (host, row-major), packed as
 // the shadow packs its blocks: out[16 j + i] = q[j] . x[i]
 int vk_i8_tile_probe(const int8_t *q, const int8_t *x, int32_t *out) {

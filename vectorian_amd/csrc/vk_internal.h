@@ -9,6 +9,7 @@
 #include "vk_guard.h"
 #include "vk_result_host.h"
 #include "vk_bound_host.h"
+#include "vk_route_host.h"
 
 #include <algorithm>
 #include <atomic>
@@ -157,6 +158,16 @@ enum vk_batch_state_index {
 	VK_BS_COUNT
 };
 
+// vk_corpus::query_route by index (the internal export vk_query_route hands the array out in this order; the tests name the entries
+// in the same order): the route of the last vk_query on the handle as vk_host::route_query decided it (the enums of vk_route_host.h;
+// all -1: a query of more than VK_MAX_QUERY_LEN tokens, which vk_longq_host.cpp serves).  VK_QR_PLAN is what ran: PLAN_FUSED where a
+// query row that is not finite or a negative boost kept a query off the bound pass it was routed to.
+enum vk_query_route_index {
+	VK_QR_PLAN, VK_QR_GAP_MODE, VK_QR_WIDE_GAP_MODE, VK_QR_SCORE32_GAP_MODE, VK_QR_WAVE_TILES,
+	VK_QR_PASS_SHORT, VK_QR_PASS_MID, VK_QR_PASS_XLONG, VK_QR_LIST, VK_QR_RING_ROWS, VK_QR_FLOW, VK_QR_OSTRIDE, VK_QR_RAW, VK_QR_SPAN_SKIP_RAW,
+	VK_QR_COUNT
+};
+
 // The handle: the shape above and what is this handle's alone.  Every workspace is a vk_devbuf (vk_devbuf.h): sized by reserve() where
 // it is needed, counted in device_bytes while it lives, freed with the handle.
 struct vk_corpus : vk_corpus_shape {
@@ -213,6 +224,7 @@ struct vk_corpus : vk_corpus_shape {
 	// route and form of the last vk_query_batch on this handle (vk_batch_state in vk_corpus.cpp, for the tests; host integers only),
 	// addressed by VK_BS_*: the route, then the shared pass's three, then the GEMM pass's twelve
 	int64_t batch_state[VK_BS_COUNT] = {};
+	int64_t query_route[VK_QR_COUNT] = {};   // ... of the last vk_query (vk_query_route), addressed by VK_QR_*
 	hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // 0 start, 5 before / 1 after the wait for the peer's kernel, 2 scored (the peer's turn), 3 selected, 4 done; 6: the batched GEMM has ended (its turn ends after the selection)
 	vk_timings last{};
 	bool have_scores = false;
@@ -270,6 +282,26 @@ template <typename P> void corpus_fields_ids(P &p, const vk_corpus *c) {
 // the recurrence's constants (vk_host::gap_form, or another parameter struct) into a parameter struct; gap_mode stays with the caller
 template <typename P, typename G> void gap_fields(P &p, const G &g) {
 	p.gs = g.gs; p.gt = g.gt; p.a_s = g.a_s; p.a_t = g.a_t; p.open_s = g.open_s; p.open_t = g.open_t;
+}
+
+// The tag-weighted modifier's fields of a kernel parameter struct whose tw / tpos arrays hold `cols` query columns, and the reference
+// score's total either way: the sum of the query's tag weights (reference_score with max_similarity_for_t = t_pos_weights,
+// slice/static.h:280-286), its length without them
+inline float ref_total_of(const vk_query_desc *q) {
+	if (!q->tag_weights) return (float)q->len_t;
+	float total = 0.0f;
+	for (int j = 0; j < q->len_t; j++) total += q->tag_weights[j];
+	return total;
+}
+template <typename P> void tag_weight_fields(P &p, const vk_corpus *c, const vk_query_desc *q, int cols) {
+	const bool tagged = q->tag_weights != nullptr;
+	for (int j = 0; j < cols; j++) {
+		p.tw[j] = (tagged && j < q->len_t) ? q->tag_weights[j] : 0.0f;
+		p.tpos[j] = (tagged && j < q->len_t) ? (int32_t)q->q_pos[j] : -1;
+	}
+	p.ref_total = ref_total_of(q);
+	if (!tagged) return;
+	p.pos_s = c->d_pos; p.tw_keep = 1.0f - q->pos_mismatch_penalty; p.tw_threshold = q->similarity_threshold;
 }
 
 // c->last from the events of a query: 0 start, 5 before / 1 after the wait for the peer, `scored` the scoring pass has ended (2; the

@@ -7,38 +7,35 @@
 #include "vk_guard.h"
 #include "vk_transport_host.h"
 
-// The multi-block kernel (vk_score32_kernel) for a query of 17..64 tokens: the gap mode it is launched with, the token tiles a
-// wave's strip spans, and whether the query tiles and at least one wave's strip fit the LDS of a CU (vk_score32_waves).  One
-// place for vk_validate_query and vk_query: exact transport and the 1:n RWMD have no other kernel for such queries, so a shape that
-// does not fit is refused before anything is enqueued -- with the gap mode of the launch, not a stand-in (round 2 tested mode 6 and
-// launched 5 or 7, whose strips are up to 1,280 bytes larger: a borderline shape failed in hipFuncSetAttribute instead).
-struct Score32Plan { int gap_mode, wave_tiles; bool fits, only_kernel; };
-// Exact transport (WRD, the non-relaxed WMD): a bound pass over all slices, then the exact solver on the candidates.
-static bool exact_transport(const vk_query_desc *q) { return q->algorithm == VK_ALG_WRD || (q->algorithm == VK_ALG_RWMD && q->wmd_full); }
-// ... and with the 1:n RWMD the algorithms that keep a slice's bag of words in LDS: a query of more than 16 tokens has the multi-block
-// kernel and the long slices' own kernels, no wide kernel
-static bool transport_in_lds(const vk_query_desc *q) { return exact_transport(q) || (q->algorithm == VK_ALG_RWMD && !q->rwmd_injective); }
-static Score32Plan score32_plan(const vk_corpus *c, const vk_query_desc *q) {
-	const bool is_static = c->desc.layout == VK_LAYOUT_STATIC;
-	const bool bound_pass = exact_transport(q);
-	const bool fill = q->algorithm == VK_ALG_RWMD && !q->wmd_full && !q->rwmd_injective;
-	const int ks = q->gap_s.kind, kt = q->gap_t.kind;
-	int gm;
-	if (bound_pass) gm = 5;
-	else if (fill) gm = 7;
-	else if (q->algorithm == VK_ALG_RWMD) gm = 4;
-	else if (ks == VK_GAP_LINEAR && kt == VK_GAP_LINEAR) gm = 0;
-	else if (ks != VK_GAP_TABLE && kt != VK_GAP_TABLE) gm = 1;
-	else gm = -1;   // general gaps: by the longest slice the kernel sees (below)
-	// alignments and the relaxed 1:1 WMD over a corpus that holds slices of more than 64 tokens (round 4): the multi-block kernel takes the
-	// others, the slices apart a pass of their own (vk_docw_kernel under linear / affine gaps, else vk_wide_kernel over their list)
-	const bool apart = (q->algorithm == VK_ALG_ALIGN || gm == 4) && c->h_apart && !c->h_apart->empty() && !getenv("VK_NO_APART");
-	if (gm < 0) gm = (apart ? c->max_short_len : c->max_len) <= 32 ? 3 : 6;
-	const bool long_apart = ((bound_pass || fill) && c->n_long_groups > 0) || apart;   // the long slices have kernels of their own
-	const int wave_tiles = long_apart ? (q->len_t <= 32 ? c->max_short_pair_tiles : (c->max_short_len + 15) / 16 + 1)
-		: (q->len_t <= 32 ? c->max_pair_tiles : (c->max_len + 15) / 16 + 1);
-	const bool fits = vk_score32_waves(is_static ? 0 : c->nk32, c->tail, wave_tiles, q->len_t, gm) >= 1;
-	return {gm, wave_tiles, fits, bound_pass || fill};
+// The route of a query (vk_route_host.h): the facts it is decided from, copied from the corpus and the query -- one place for
+// vk_validate_query, which refuses a shape before anything is enqueued, and for query_body.  (bound_pass stays false here: the
+// handle's back-off is asked by the query that runs.)
+static constexpr int kCanonMargin = 8;   // runners-up selected with the winners where the host restates the winners' scores
+static const vk_host::route_fits kRouteFits{vk_score32_waves, vk_wide_ring_rows, vk_wide_lds_demand};
+static bool exact_transport(const vk_query_desc *q) { return vk_host::exact_transport(q->algorithm, q->wmd_full != 0); }
+static vk_host::route_facts route_facts_of(const vk_corpus *c, const vk_query_desc *q, const vk_topk_out *out) {
+	vk_host::route_facts f;
+	f.layout = c->desc.layout; f.prec = c->prec; f.nk32 = c->nk32; f.tail = c->tail;
+	f.max_len = c->max_len; f.max_short_len = c->max_short_len; f.n_long_groups = c->n_long_groups;
+	f.has_apart = c->h_apart && !c->h_apart->empty(); f.has_xlong = c->h_xlong && !c->h_xlong->empty();
+	f.max_pair_tiles = c->max_pair_tiles; f.max_short_pair_tiles = c->max_short_pair_tiles; f.uniform_len = c->uniform_len;
+	f.has_pos = c->d_pos != nullptr; f.has_tags = c->d_tag != nullptr; f.n_sentences = c->desc.n_sentences;
+	f.algorithm = q->algorithm; f.wmd_full = q->wmd_full != 0; f.rwmd_injective = q->rwmd_injective != 0; f.len_t = q->len_t;
+	if (q->algorithm == VK_ALG_ALIGN) {
+		f.gaps = vk_host::classify_gaps(q->gap_s, q->gap_t);
+		// (vk_validate_query asks before it has looked at the gap kinds: no table is read under a kind that is none)
+		if (f.gaps.gap_mode == 2 && q->gap_s.kind >= VK_GAP_LINEAR && q->gap_s.kind <= VK_GAP_TABLE) f.ws_tail = vk_host::ws_tail_of(q->gap_s, c->max_len);
+	}
+	f.submatch = q->submatch_weight > 0.0f; f.tagged = q->tag_weights != nullptr; f.has_q_tags = q->q_tags != nullptr; f.has_q_ids = q->q_token_ids != nullptr;
+	f.only = q->only_slices != nullptr; f.want_flow = q->want_flow != 0; f.locality = q->locality;
+	f.sim_rows = out->sim_rows != nullptr; f.raw_score = out->raw_score != nullptr; f.boost = q->boost != nullptr;
+	// the size of the selection.  Winners restated on the host (tracebacks; the relaxed WMD's rows): a few runners-up are selected with
+	// them (57 .. 64 matches: the margin takes the selection to the k > 64 path; beyond VK_MAX_MATCHES: every score is sorted, never
+	// more winners than rows)
+	const int k = q->max_matches;
+	const bool restated = (q->want_flow && q->algorithm == VK_ALG_ALIGN) || (q->algorithm == VK_ALG_RWMD && !q->wmd_full && q->want_flow && out->sim_rows);
+	f.kk = f.only ? q->n_only : (int)std::min<int64_t>(!restated ? k : (k <= VK_MAX_MATCHES ? std::min(k + kCanonMargin, VK_MAX_MATCHES) : k + kCanonMargin), std::max<int64_t>(c->n_entries, 1));
+	return f;
 }
 
 int vk_validate_query(const vk_corpus *c, const vk_query_desc *q, const vk_topk_out *out) {
@@ -54,8 +51,10 @@ int vk_validate_query(const vk_corpus *c, const vk_query_desc *q, const vk_topk_
 		if (out->sim_rows) return fail(VK_ERR_UNSUPPORTED, "queries of more than 64 tokens: similarity rows of the winners are not returned");
 		if (q->max_matches > VK_MAX_MATCHES) return fail(VK_ERR_UNSUPPORTED, "queries of more than 64 tokens: max_matches <= VK_MAX_MATCHES");
 	}
-	if (q->len_t > VK_FAST_QUERY_LEN && transport_in_lds(q) && !score32_plan(c, q).fits)
-		return fail(VK_ERR_UNSUPPORTED, "exact transport / 1:n RWMD with a query of more than 16 tokens: the query tiles of rows this wide and one wave's similarity strip exceed the LDS of a workgroup (160 KiB)");
+	if (q->len_t <= VK_MAX_QUERY_LEN) {   // (the switches a refusal reads: none)
+		const vk_host::query_route r = vk_host::route_query(route_facts_of(c, q, out), vk_host::route_switches{}, kRouteFits);
+		if (r.status != VK_OK && !r.fits32) return fail(r.status, r.message);
+	}
 	// Slices of more than VK_MAX_SENT_LEN tokens (whole documents as slices, up to VK_MAX_DOC_LEN): alignments -- the
 	// one-wave-per-slice kernel with the slice's state in global memory (vk_wide_kernel, global-state form; the same form takes a
 	// query of more than 16 tokens whose state over the corpus's longest slice exceeds the LDS: VK_ERR_UNSUPPORTED in round 2) --
@@ -93,6 +92,18 @@ int vk_validate_query(const vk_corpus *c, const vk_query_desc *q, const vk_topk_
 			if (q->only_slices[i] < 0 || q->only_slices[i] >= c->desc.n_sentences) return fail(VK_ERR_INVALID, "only_slices: slice index out of range");
 	}
 	if (q->bidirectional) return fail(VK_ERR_UNSUPPORTED, "bidirectional is not implemented (unused upstream, query.cpp:81-83)");
+	// the two checks every algorithm makes, each at its own place among the others (which error a doubly wrong query gets)
+	int rc = VK_OK;
+	const auto tag_weights = [&]() -> int {   // TagWeightedSlice wraps any slice, whatever the matcher (match/instantiate.cpp:173-189)
+		if (!q->tag_weights) return VK_OK;
+		if (!q->q_pos) return fail(VK_ERR_INVALID, "tag-weighted query without q_pos");
+		if (!c->d_pos) return fail(VK_ERR_STATE, "tag-weighted query needs vk_corpus_set_token_pos");
+		if (q->similarity_threshold < 0.0f) return fail(VK_ERR_INVALID, "similarity_threshold must be >= 0 (slice/static.h:209)");
+		return VK_OK;
+	};
+	const auto flow_arrays = [&]() -> int {
+		return (q->want_flow && (!out->mapping || !out->edge_sim)) ? fail(VK_ERR_INVALID, "want_flow needs mapping and edge_sim arrays") : VK_OK;
+	};
 	if (q->algorithm == VK_ALG_ALIGN) {
 		if (q->locality < VK_LOCAL || q->locality > VK_SEMIGLOBAL) return fail(VK_ERR_INVALID, "bad locality");
 		for (const vk_gap *g : {&q->gap_s, &q->gap_t}) {
@@ -101,17 +112,11 @@ int vk_validate_query(const vk_corpus *c, const vk_query_desc *q, const vk_topk_
 		}
 		if (q->gap_s.kind == VK_GAP_TABLE && q->gap_s.n_table <= c->max_len) return fail(VK_ERR_INVALID, "gap_s table shorter than the longest sentence");
 		if (q->gap_t.kind == VK_GAP_TABLE && q->gap_t.n_table <= q->len_t) return fail(VK_ERR_INVALID, "gap_t table shorter than the query");
-		if (q->want_flow && (!out->mapping || !out->edge_sim)) return fail(VK_ERR_INVALID, "want_flow needs mapping and edge_sim arrays");
-		if (q->tag_weights) {
-			if (!q->q_pos) return fail(VK_ERR_INVALID, "tag-weighted query without q_pos");
-			if (!c->d_pos) return fail(VK_ERR_STATE, "tag-weighted query needs vk_corpus_set_token_pos");
-			if (q->similarity_threshold < 0.0f) return fail(VK_ERR_INVALID, "similarity_threshold must be >= 0 (slice/static.h:209)");
-		}
+		if ((rc = flow_arrays())) return rc;
+		if ((rc = tag_weights())) return rc;
 	} else if (q->algorithm == VK_ALG_RWMD) {
-		if (q->tag_weights) {   // TagWeightedSlice wraps any slice, whatever the matcher (match/instantiate.cpp:173-189)
-			if (!q->q_pos) return fail(VK_ERR_INVALID, "tag-weighted query without q_pos");
-			if (!c->d_pos) return fail(VK_ERR_STATE, "tag-weighted query needs vk_corpus_set_token_pos");
-			if (q->similarity_threshold < 0.0f) return fail(VK_ERR_INVALID, "similarity_threshold must be >= 0 (slice/static.h:209)");
+		if ((rc = tag_weights())) return rc;
+		if (q->tag_weights) {
 			if (q->q_tags && c->desc.layout == VK_LAYOUT_STATIC) {
 				// vocabulary keys (token id, tag) as id * 256 + tag in 32 bits, ordered as upstream's signed pairs: ids below 2^23, tags 0 .. 127
 				if (c->desc.vocab_size > (1 << 23)) return fail(VK_ERR_UNSUPPORTED, "tag-weighted transport with q_tags over the static layout: vocabularies of more than 2^23 entries overflow the (id, tag) keys");
@@ -130,15 +135,11 @@ int vk_validate_query(const vk_corpus *c, const vk_query_desc *q, const vk_topk_
 			if (q->rwmd_injective) return fail(VK_ERR_INVALID, "non-relaxed WMD with injective mapping is not supported");      // wmd.h:201-204
 			if (q->rwmd_symmetric) return fail(VK_ERR_INVALID, "non-relaxed WMD with symmetric computation is not supported");  // wmd.h:206-209
 		}
-		if (q->want_flow && (!out->mapping || !out->edge_sim)) return fail(VK_ERR_INVALID, "want_flow needs mapping and edge_sim arrays");
+		if ((rc = flow_arrays())) return rc;
 	} else if (q->algorithm == VK_ALG_WRD) {
-		if (q->tag_weights) {
-			if (!q->q_pos) return fail(VK_ERR_INVALID, "tag-weighted query without q_pos");
-			if (!c->d_pos) return fail(VK_ERR_STATE, "tag-weighted query needs vk_corpus_set_token_pos");
-			if (q->similarity_threshold < 0.0f) return fail(VK_ERR_INVALID, "similarity_threshold must be >= 0 (slice/static.h:209)");
-		}
+		if ((rc = tag_weights())) return rc;
 		if (!c->d_mag) return fail(VK_ERR_STATE, "VK_ALG_WRD needs a corpus created with keep_magnitudes = 1");
-		if (q->want_flow && (!out->mapping || !out->edge_sim)) return fail(VK_ERR_INVALID, "want_flow needs mapping and edge_sim arrays");
+		if ((rc = flow_arrays())) return rc;
 	} else {
 		return fail(VK_ERR_INVALID, "bad algorithm");
 	}
@@ -274,6 +275,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	int rc = VK_OK;
 	VK_HIP(hipSetDevice(c->device));
 	c->bp.pruned = false; c->bp.ran = c->bp.round1 = c->bp.round2 = c->bp.fell_back = 0;
+	for (int64_t &x : c->query_route) x = -1;
 	if (q->len_t > VK_MAX_QUERY_LEN) return vk_longq_query(c, q, out, keep);   // 65 .. 512 tokens (vk_longq_host.cpp)
 	hipStream_t st = c->stream;
 	const int64_t n = c->n_entries;           // rows of the slice table (== n_sentences unless long slices were padded)
@@ -282,6 +284,21 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	out->n_out = 0;
 	c->have_scores = false;
 	if (n == 0) return VK_OK;
+	// ---- the route: which kernels this query runs on, decided here and read below (vk_route_host.h).  The bound pass may
+	// take the query where the corpus has a shadow, VK_BOUND_PASS and the corpus's size allow it and the handle's back-off agrees
+	const vk_host::route_switches sw = vk_host::read_route_switches();
+	vk_host::route_facts facts = route_facts_of(c, q, out);
+	const int bound_mode = bound_pass_mode();
+	facts.bound_pass = c->shadow && bound_mode >= 0 && (bound_mode > 0 || c->desc.n_sentences >= kBoundPassMinSentences) && vk_host::bound_pass_takes(facts) &&
+		(bound_mode != 0 || c->bp.backoff.take());
+	const vk_host::query_route r = vk_host::route_query(facts, sw, kRouteFits);
+	if (r.status != VK_OK) return fail(r.status, r.message);
+	const int64_t route_state[VK_QR_COUNT] = {r.plan, r.gap_mode, r.wide_gap_mode, r.score32_gap_mode, r.wave_tiles, r.pass[vk_host::CLASS_SHORT],
+		r.pass[vk_host::CLASS_MID], r.pass[vk_host::CLASS_XLONG], r.list, r.ring_rows, r.flow, r.ostride, r.raw, r.span_skip_raw};
+	memcpy(c->query_route, route_state, sizeof route_state);
+	const bool wide_query = q->len_t > VK_FAST_QUERY_LEN;   // 17 .. 64 tokens
+	const bool xlong = c->max_len > VK_MAX_SENT_LEN;       // whole documents as slices: the one-wave-per-slice family, state in global memory
+	const bool wide_family = r.flow != vk_host::FLOW_NARROW;   // the winners' tracebacks (and some scoring pass) on that family: VkWideParams
 	auto sentence_of = [c](int64_t row) { return c->entry_sent.empty() ? row : (int64_t)c->entry_sent[(size_t)row]; };
 	const bool is_static_l = c->desc.layout == VK_LAYOUT_STATIC;
 	// transport algorithms: similarity rows (and, for exact transport, the optimal plan) of the winners, from which
@@ -292,16 +309,8 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		w.table = c->d_table; w.table_stride = (int64_t)c->n_tiles * 16 * 16;
 		w.qtile = c->d_qtile; w.nq = (q->len_t + 15) / 16; w.len_t = q->len_t; w.mag = c->d_mag;
 		w.d = c->desc.d; w.q_ids = is_static_l ? (int32_t *)c->d_qids : nullptr;   // canonical similarity rows (sim_canon)
-		w.ref_total = (float)q->len_t;
+		tag_weight_fields(w, c, q, VK_MAX_QUERY_LEN);
 		if (q->tag_weights) {
-			float total = 0.0f;
-			for (int j = 0; j < q->len_t; j++) total += q->tag_weights[j];
-			for (int j = 0; j < VK_MAX_QUERY_LEN; j++) {
-				w.tw[j] = j < q->len_t ? q->tag_weights[j] : 0.0f;
-				w.tpos[j] = j < q->len_t ? (int32_t)q->q_pos[j] : -1;
-			}
-			w.pos_s = c->d_pos; w.tw_keep = 1.0f - q->pos_mismatch_penalty; w.tw_threshold = q->similarity_threshold;
-			w.ref_total = total;   // reference_score with max_sum_of_similarities = sum of t_pos_weights (slice/static.h:280-286)
 			if (is_static_l && q->algorithm == VK_ALG_RWMD && q->q_tags && q->q_token_ids && c->d_tag && c->d_qbits) {
 				// the cells upstream writes twice (static_vocab_fixup); d_qbits holds this query's bitmap (set before the scoring launch)
 				w.tag_s = c->d_tag; w.qid_bits = c->d_qbits;
@@ -352,32 +361,8 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	VK_HIP(hipEventRecord(c->ev[0], st));
 	std::vector<uint8_t> &qtile = keep.vec<uint8_t>();
 	float qmags[VK_MAX_QUERY_LEN] = {0};
-	// whole documents as slices (beyond VK_MAX_SENT_LEN tokens): scored by the one-wave-per-slice kernel, every winner retraced by it;
-	// the other slices of such a corpus keep their fused kernels when the query has at most 16 tokens (wide_score false)
-	const bool xlong = c->max_len > VK_MAX_SENT_LEN;
-	const bool wide_score = q->len_t > VK_FAST_QUERY_LEN;
-	// General gaps over slices of 65 .. 512 tokens: the one-wave-per-slice kernel (candidate scan dealt out over the idle lanes, eight
-	// loads deep, a saturated table as a running maximum) is several times faster than the fused kernel's pass over long slices with
-	// its serial LDS-history scan (8,000 slices of 300 .. 512 tokens at 300-d: 101 ms) -- they take the documents' pass as well,
-	// and every winner is retraced by the same kernel
-	// (round 4: linear / affine gaps too -- the skewed sweep of vk_doc_kernel is faster than the fused kernel's long pass; VK_LONG_LINEAR=1: that pass)
-	const bool long_via_wide = q->algorithm == VK_ALG_ALIGN && !wide_score && c->n_long_groups > 0 &&
-		(q->gap_s.kind == VK_GAP_TABLE || q->gap_t.kind == VK_GAP_TABLE || !getenv("VK_LONG_LINEAR")) && !getenv("VK_LONG_PASS");
-	const bool wide = wide_score || xlong || long_via_wide;
-	// the relaxed 1:1 WMD over slices of 65 .. 512 tokens: scored by vk_doc_kernel's streaming arm instead of the fused kernel's long pass
-	// (the winners keep their path: rows from vk_rows_kernel, scores restated on the host)
-	const bool rwmd_long_doc = q->algorithm == VK_ALG_RWMD && q->rwmd_injective && !q->wmd_full && !wide_score && !xlong && c->n_long_groups > 0 && !getenv("VK_LONG_PASS");
-	// whole documents under linear / affine gaps with a query of at most 16 tokens: vk_doc_kernel scores them and retraces the winners
-	// (general gaps: under a table that saturates within 126 tokens -- wp.ws_tail, set below; doc_ok() asks once wp is filled)
-	// (... and the slices of 65 .. 512 tokens that general gaps send through the one-wave-per-slice pass)
-	const bool doc_fast = (xlong || rwmd_long_doc || (long_via_wide && !getenv("VK_NO_DOC_MID"))) && !wide_score && (q->algorithm == VK_ALG_ALIGN || q->algorithm == VK_ALG_RWMD) && !getenv("VK_NO_DOC_KERNEL");
 	const int nq = (q->len_t + 15) / 16;
-	// the bound pass can take this query: alignment of at most 16 tokens over a corpus with a shadow, nothing that changes a
-	// cell or the reference score per slice (tag weights, submatch weight), every slice scored; the boost is checked where it is uploaded
-	const int bound_mode = bound_pass_mode();
-	bool bound_ok = c->shadow && bound_mode >= 0 && (bound_mode > 0 || c->desc.n_sentences >= kBoundPassMinSentences) && q->algorithm == VK_ALG_ALIGN &&
-		q->len_t <= VK_FAST_QUERY_LEN && q->submatch_weight == 0.0f && !q->tag_weights && !only && c->n_long_groups == 0 && c->max_len <= VK_FAST_SENT_LEN;
-	if (bound_ok && bound_mode == 0 && !c->bp.backoff.take()) bound_ok = false;
+	bool bound_ok = r.plan == vk_host::PLAN_BOUNDED;   // ... unless a query row is not finite or a boost is negative (below)
 	std::vector<uint8_t> &qtile8 = keep.vec<uint8_t>();
 	vk_pack_query(c, q, qtile, qmags, bound_ok ? &qtile8 : nullptr);
 	VK_HIP(hipMemcpyAsync(c->d_qtile, qtile.data(), qtile.size(), hipMemcpyHostToDevice, st));
@@ -388,14 +373,12 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	}
 
 	VkScoreParams p{};
-	bool span_skip_raw = false;   // span-embedding path without its second output array
 	float qmass_all[VK_MAX_QUERY_LEN] = {0};   // masses of the query tokens (transport algorithms), all 64 columns
 	const size_t n_ws = std::max<size_t>((size_t)kGapTable, (size_t)c->max_len + 2);   // w_s up to the longest slice
 	std::vector<float> &ws = keep.vec<float>(n_ws);
 	float *wt = keep.array<float>(160);   // wt[0..79]: w_t as given; wt[80..159]: its subadditive closure (vk_result_host.h)
 	const bool is_align = q->algorithm == VK_ALG_ALIGN;
 	if (q->algorithm == VK_ALG_WRD) {
-		p.gap_mode = 5;
 		float sum_t = 0.0f;
 		for (int j = 0; j < q->len_t; j++) sum_t += qmags[j];           // wrd.h:99-102, float sum in order
 		const bool rawm = !q->wrd_normalize_magnitudes;   // wrd.h:99-102: masses stay the magnitudes
@@ -404,7 +387,6 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		p.wrd_raw_total = rawm ? sum_t : 0.0f;
 		p.mag = c->d_mag;
 	} else if (q->algorithm == VK_ALG_RWMD) {
-		p.gap_mode = 4;
 		p.rwmd_symmetric = q->rwmd_symmetric;
 		p.rwmd_normalize_bow = q->rwmd_normalize_bow;
 		if (q->wmd_full) {
@@ -413,7 +395,6 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		}
 		else if (!q->rwmd_injective) {
 			// 1:n form: masses of the query's vocabulary entries (count / len at the first occurrence of a token id)
-			p.gap_mode = 7;
 			const bool ids = c->desc.layout == VK_LAYOUT_STATIC && q->q_token_ids;
 			for (int j = 0; j < VK_MAX_QUERY_LEN; j++) {
 				float mass = 0.0f;
@@ -432,19 +413,11 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 			memcpy(p.qmass, qmass_all, sizeof p.qmass);
 			if (ids && q->tag_weights && q->q_tags) p.tag_s = c->d_tag;
 		}
-	} else {
-		const vk_host::gap_form g = vk_host::classify_gaps(q->gap_s, q->gap_t);
-		p.gap_mode = g.gap_mode;
-		gap_fields(p, g);
-	}
+	} else gap_fields(p, facts.gaps);
+	p.gap_mode = r.gap_mode;
 	for (size_t i = 0; i < n_ws; i++) ws[i] = (is_align && (int64_t)i <= c->max_len) ? gap_cost(q->gap_s, (int)i) : 0.0f;
 	if ((rc = c->d_ws.reserve(n_ws, &c->device_bytes))) return rc;
 	vk_host::wt_with_closure(wt, q->gap_t, q->len_t, is_align);
-	bool wide_sub = false;   // a long query with general gaps: the multi-block kernel takes it
-	if (p.gap_mode == 2) {
-		if (!wide_score) p.gap_mode = c->max_short_len <= 32 ? 3 : 6;
-		wide_sub = wide;
-	}
 	VK_HIP(hipMemcpyAsync(c->d_ws, ws.data(), n_ws * sizeof(float), hipMemcpyHostToDevice, st));
 	VK_HIP(hipMemcpyAsync(c->d_wt, wt, 160 * sizeof(float), hipMemcpyHostToDevice, st));
 
@@ -469,9 +442,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	// the host restates each winner's score from them in the reference's order of operations (vk_transport_host.h): the scores of the
 	// result set are the oracle's floats, whichever kernel ranked the slices (per query, batched GEMM, a shard of the corpus).
 	const bool canon_tr = q->algorithm == VK_ALG_RWMD && !q->wmd_full && q->want_flow && out->sim_rows != nullptr;
-	constexpr int kCanonMargin = 8;
-	// (57 .. 64 matches: the margin takes the selection to the k > 64 path; beyond VK_MAX_MATCHES: every score is sorted, never more winners than rows)
-	const int kk = only ? q->n_only : (int)std::min<int64_t>(!(do_flow || canon_tr) ? k : (k <= VK_MAX_MATCHES ? std::min(k + kCanonMargin, VK_MAX_MATCHES) : k + kCanonMargin), std::max<int64_t>(n, 1));
+	const int kk = facts.kk;
 	const float sel_floor = (do_flow || canon_tr) ? q->min_score - 1e-5f * std::max(1.0f, std::fabs(q->min_score)) : q->min_score;
 
 	// ---- the fused scoring kernel ------------------------------------------
@@ -486,19 +457,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	p.ws = c->d_ws; p.wt = c->d_wt + 80; p.wt0 = c->d_wt;
 	p.boost = q->boost ? (float *)c->d_boost : nullptr;
 	p.scores = c->d_scores; p.raw = c->d_raw;
-	p.ref_total = (float)q->len_t;
-	if (q->tag_weights) {
-		float total = 0.0f;
-		for (int j = 0; j < q->len_t; j++) total += q->tag_weights[j];
-		for (int j = 0; j < VK_FAST_QUERY_LEN; j++) {
-			p.tw[j] = j < q->len_t ? q->tag_weights[j] : 0.0f;
-			p.tpos[j] = j < q->len_t ? (int32_t)q->q_pos[j] : -1;
-		}
-		p.pos_s = c->d_pos;
-		p.tw_keep = 1.0f - q->pos_mismatch_penalty;
-		p.tw_threshold = q->similarity_threshold;
-		p.ref_total = total;   // reference_score with max_similarity_for_t = t_pos_weights (slice/static.h:280-286)
-	}
+	tag_weight_fields(p, c, q, VK_FAST_QUERY_LEN);
 	// vocabulary transports with tag weights over the static layout: the cells upstream writes twice (static_vocab_fixup,
 	// vk_common.hip.h) -- needs the (id, tag) keys of both sides: q_tags and vk_corpus_set_token_tags
 	int32_t qkey_all[VK_MAX_QUERY_LEN];
@@ -522,29 +481,17 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	bool bounded = false;   // the scoring pass was the bound pass and its rounds (score_bounded)
 	const uint64_t *d_sel_bounded = nullptr;   // ... which selected the kk best among their candidates already
 	VkWideParams wp{};
-	// Winners of 65 .. 512 tokens under linear / affine gaps (scored by the fused kernel's long pass): their tracebacks on vk_doc_kernel's
-	// sweep as well -- vk_flow_kernel fills such a matrix row by row in LDS (8,000 slices of 300 .. 512 tokens: 1.6 ms of a 2.8 ms query)
-	const bool flow_doc = is_align && !wide && c->max_len > VK_FAST_SENT_LEN && q->len_t <= 16 && (p.gap_mode == 0 || p.gap_mode == 1) && !getenv("VK_NO_DOC_FLOW");
-	// a query of 17 .. 64 tokens under linear / affine gaps: the long slices (65 tokens .. whole documents) and every winner's traceback on
-	// the wave-wide skewed sweep (vk_docw_kernel); the slices of at most 64 tokens keep the multi-block kernel
-	const bool docw = is_align && wide_score && q->len_t <= VK_MAX_QUERY_LEN && (p.gap_mode == 0 || p.gap_mode == 1) && !getenv("VK_NO_DOCW");
-	// ... of 17 .. 32 tokens under general gaps whose table saturates within 126 tokens (wp.ws_tail): vk_docg_kernel
-	auto docg_ok = [&]() { return is_align && wide_score && q->len_t <= 32 && c->max_len > VK_FAST_SENT_LEN && p.gap_mode == 2 && wp.ws_tail >= 1 && wp.ws_tail <= 126 && !getenv("VK_NO_DOCG"); };
-	auto doc_ok = [&]() { return (doc_fast || flow_doc) && (q->algorithm == VK_ALG_RWMD ? wp.gap_mode == 4 && !getenv("VK_NO_DOC_RWMD")   // (the relaxed 1:1 form)
-		: (wp.gap_mode == 0 || wp.gap_mode == 1 || (wp.gap_mode == 2 && wp.ws_tail >= 1 && wp.ws_tail <= 126 && !getenv("VK_NO_DOC_GENERAL")))); };
-	// vk_wide_kernel: the state of a slice in LDS where that fits, else in global memory (one region per workgroup)
-	// The scoring pass of vk_wide_kernel takes one wave per slice: its work list, longest first (wp.order).  A query of more than 16
-	// tokens: every non-empty row of the slice table (the others carry no score: preset); at most 16 tokens: only the slices the fused
-	// kernels leave to it -- those beyond VK_MAX_SENT_LEN, or, under general gaps, every slice of more than 64 tokens.
-	auto wide_order = [&](int force = -1) -> int {
-		const int which = force >= 0 ? force : wide_score ? 0 : (long_via_wide || rwmd_long_doc) ? 1 : 2;
-		vk_devbuf<int32_t> &d_ord = which == 0 ? c->d_wide_order : which == 1 ? c->d_apart_order : c->d_xlong_order;
-		int32_t &n_ord = which == 0 ? c->n_wide_order : which == 1 ? c->n_apart_order : c->n_xlong_order;
+	// The work list of a pass of the one-wave-per-slice family, longest first (wp.order): every non-empty row of the slice table (the
+	// others carry no score: preset), the slices of more than 64 tokens, or those beyond VK_MAX_SENT_LEN -- built when first needed
+	auto wide_order = [&](vk_host::route_list list) -> int {
+		const bool all = list == vk_host::LIST_ALL, apart = list == vk_host::LIST_APART;
+		vk_devbuf<int32_t> &d_ord = all ? c->d_wide_order : apart ? c->d_apart_order : c->d_xlong_order;
+		int32_t &n_ord = all ? c->n_wide_order : apart ? c->n_apart_order : c->n_xlong_order;
 		if (n_ord < 0) {
 			std::vector<int32_t> ord;
-			if (which == 0) { for (int64_t e = 0; e < n; e++) if ((*c->h_end)[(size_t)e] > (*c->h_start)[(size_t)e]) ord.push_back((int32_t)e); }
-			else if (which == 1 && c->h_apart) ord = *c->h_apart;
-			else if (which == 2 && c->h_xlong) ord = *c->h_xlong;
+			if (all) { for (int64_t e = 0; e < n; e++) if ((*c->h_end)[(size_t)e] > (*c->h_start)[(size_t)e]) ord.push_back((int32_t)e); }
+			else if (apart && c->h_apart) ord = *c->h_apart;
+			else if (!apart && c->h_xlong) ord = *c->h_xlong;
 			std::stable_sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) {
 				return (*c->h_end)[(size_t)a] - (*c->h_start)[(size_t)a] > (*c->h_end)[(size_t)b] - (*c->h_start)[(size_t)b]; });
 			int rcw;
@@ -553,147 +500,100 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 			n_ord = (int32_t)ord.size();
 		}
 		wp.order = d_ord; wp.n_order = n_ord;
-		if (which == 0) {
+		if (all) {
 			VK_HIP(hipMemsetD32Async(static_cast<hipDeviceptr_t>(c->d_scores), (int)0xff800000u, (size_t)n, st));
 			if (wp.raw) VK_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(wp.raw), (int)0xff800000u, (size_t)n, st));
 		}
 		return VK_OK;
 	};
-	auto wide_state = [&](int flow_k, int force = -1) -> int {   // force: the work list (wide_order), whatever the query's own choice
+	// vk_wide_kernel's state for a scoring pass over the route's list (flow_k 0) or for flow_k tracebacks: in LDS where the route says
+	// so, else one region of scratch per workgroup, sized here (with room for the records of the route's traceback kernel)
+	auto wide_state = [&](int flow_k) -> int {
 		const bool flow = flow_k > 0;
+		const vk_host::route_list list = flow ? vk_host::LIST_NONE : r.list;
 		wp.scratch = nullptr; wp.scratch_stride = 0; wp.h_ring = 0; wp.order = nullptr; wp.n_order = 0;
-		// (the pass over the long slices of a corpus: the ring form where the gap table saturates -- 9 KB of LDS per wave, not 35)
-		const bool part = !flow && ((!wide_score && (xlong || long_via_wide || rwmd_long_doc)) || force >= 0);
-		const bool want_ring = part && vk_wide_ring_rows(nq, wp.gap_mode, wp.ws_tail) > 0;
-		if (!xlong && !want_ring && !(flow && (doc_ok() || docw || docg_ok())) && vk_wide_lds_demand(c->max_len, nq, wp.gap_mode, q->tag_weights != nullptr, flow) <= 160 * 1024) {
-			if (part) {   // state in LDS, but still only the long slices
-				int rcw = VK_OK;
-				if ((rcw = wide_order(force))) return rcw;
-			}
-			return VK_OK;
-		}
-		wp.h_ring = vk_wide_ring_rows(nq, wp.gap_mode, wp.ws_tail);   // a saturated gap table: the column history is a ring in LDS
+		if (flow ? r.wide_lds_flow : r.wide_lds_score)
+			return list == vk_host::LIST_APART || list == vk_host::LIST_XLONG ? wide_order(list) : VK_OK;   // (state in LDS, but still only the long slices)
+		wp.h_ring = r.ring_rows;   // a saturated gap table: the column history is a ring in LDS
 		size_t per = vk_wide_scratch_bytes(c->max_len, nq, wp.gap_mode, flow, wp.h_ring);
-		if (flow && doc_ok()) per = std::max(per, vk_doc_scratch_bytes(c->max_len, wp.gap_mode));   // (vk_doc_kernel's records of a winner)
-		if (flow && docw) per = std::max(per, vk_docw_scratch_bytes(c->max_len, nq));
-		if (flow && docg_ok()) per = std::max(per, vk_docg_scratch_bytes(c->max_len));
+		if (flow && r.flow == vk_host::FLOW_DOC) per = std::max(per, vk_doc_scratch_bytes(c->max_len, wp.gap_mode));   // (vk_doc_kernel's records of a winner)
+		if (flow && r.flow == vk_host::FLOW_DOCW) per = std::max(per, vk_docw_scratch_bytes(c->max_len, nq));
+		if (flow && r.flow == vk_host::FLOW_DOCG) per = std::max(per, vk_docg_scratch_bytes(c->max_len));
 		const size_t blocks = (size_t)vk_wide_gs_blocks(c->max_len, nq, wp.gap_mode, flow_k, n, wp.h_ring);
 		const size_t need = per * blocks;
 		if (need > ((size_t)16 << 30)) return fail(VK_ERR_UNSUPPORTED, "traceback state of this many slices this long exceeds 16 GiB of scratch");
 		if (int rcw = c->d_wide_scratch.reserve(need, &c->device_bytes)) return rcw;
 		wp.scratch = c->d_wide_scratch; wp.scratch_stride = (int64_t)per;
-		if (!flow && (xlong || part)) {
-			int rcw = VK_OK;
-			if ((rcw = wide_order(force))) return rcw;
-		}
+		return list != vk_host::LIST_NONE ? wide_order(list) : VK_OK;
+	};
+	// the doc / docw / docg / wide pass over the route's list
+	auto list_pass = [&]() -> int {
+		const vk_host::route_pass pass = r.wide_pass;
+		if (int rcw = (pass == vk_host::PASS_WIDE || pass == vk_host::PASS_DOC) ? wide_state(0) : wide_order(r.list)) return rcw;
+		if (wp.order && wp.n_order == 0) return VK_OK;
+		if (pass == vk_host::PASS_DOCW) VK_HIP(vk_launch_docw(&wp, 0, st));
+		else if (pass == vk_host::PASS_DOCG) VK_HIP(vk_launch_docg(&wp, 0, st));
+		else if (pass == vk_host::PASS_DOC) VK_HIP(vk_launch_doc(&wp, 0, st));
+		else VK_HIP(vk_launch_wide(&wp, 0, st));
 		return VK_OK;
 	};
-	if (wide || flow_doc || rwmd_long_doc) {
+	if (wide_family || r.list != vk_host::LIST_NONE) {
 		corpus_fields_ids(wp, c);
 		wp.table = c->d_table; wp.table_stride = table_stride; wp.n_sent = (int32_t)n;
 		wp.qtile = c->d_qtile; wp.nq = nq; wp.len_t = q->len_t; wp.locality = q->locality; wp.max_len = c->max_len;
-		wp.gap_mode = (p.gap_mode == 3 || p.gap_mode == 6) ? 2 : p.gap_mode;   // (the fused kernels' register-history forms of general gaps)
+		wp.gap_mode = r.wide_gap_mode;
 		wp.rwmd_symmetric = p.rwmd_symmetric; wp.rwmd_normalize_bow = p.rwmd_normalize_bow;
 		gap_fields(wp, p);
 		wp.ws = c->d_ws; wp.wt = c->d_wt; wp.wt0 = c->d_wt;
-		if (wp.gap_mode == 2 && c->max_len >= 2) {   // the constant tail of w_s (a saturated table): from which k on
-			int kt = c->max_len;
-			while (kt > 1 && ws[(size_t)kt - 1] == ws[(size_t)c->max_len]) kt--;
-			if (kt < c->max_len) wp.ws_tail = kt;
-		}
-		wp.pos_s = p.pos_s; wp.tag_s = p.tag_s; wp.qid_bits = p.qid_bits; wp.slices_overlap = p.slices_overlap; memcpy(wp.qkey, qkey_all, sizeof wp.qkey);
-		wp.tw_keep = p.tw_keep; wp.tw_threshold = p.tw_threshold; wp.ref_total = p.ref_total;
-		for (int j = 0; j < VK_MAX_QUERY_LEN; j++) {
-			wp.tw[j] = (p.pos_s && j < q->len_t) ? q->tag_weights[j] : 0.0f;
-			wp.tpos[j] = (p.pos_s && j < q->len_t) ? (int32_t)q->q_pos[j] : -1;
-		}
-		wp.boost = p.boost; wp.scores = c->d_scores; wp.raw = c->d_raw;
+		wp.ws_tail = facts.ws_tail;   // the constant tail of w_s (a saturated table): from which k on
+		tag_weight_fields(wp, c, q, VK_MAX_QUERY_LEN);
+		wp.tag_s = p.tag_s; wp.qid_bits = p.qid_bits; wp.slices_overlap = p.slices_overlap; memcpy(wp.qkey, qkey_all, sizeof wp.qkey);
+		wp.boost = p.boost; wp.scores = c->d_scores; wp.raw = r.raw ? (float *)c->d_raw : nullptr;
 		wp.d = c->desc.d; wp.q_ids = is_static ? (int32_t *)c->d_qids : nullptr;   // FLOW: canonical similarity rows (sim_canon)
-		// as for the 16-column kernel: the aligner scores of all slices only if something reads them
-		if (((is_align && q->want_flow) || exact_transport(q)) && !(q->submatch_weight > 0.0f) && !getenv("VK_KEEP_RAW")) wp.raw = nullptr;
-		if (wide_score) {
-		// 17..32 tokens with linear / affine gaps over a bf16 contextual corpus of short slices: the fused two-block kernel
-		// (affine: the prefix-scan form of F needs open_t >= extend_t, as dp_affine)
-		// (33..64 tokens: one slice per wave and four column blocks)
-		const bool rwmd_inj = q->algorithm == VK_ALG_RWMD && (p.gap_mode == 4 || p.gap_mode == 7) && !q->wmd_full;
-		const bool bound_pass = exact_transport(q);   // stage 1
-		// exact transport over a corpus with long slices: the multi-block kernel skips them (their groups are padded, vk_corpus.cpp),
-		// vk_long_bound_kernel bounds them
-		const bool long_apart = (bound_pass || p.gap_mode == 7) && c->n_long_groups > 0;
-		const Score32Plan plan32 = score32_plan(c, q);
-		const int wave_tiles = plan32.wave_tiles;
-		// the multi-block kernel skips the slices of more than 64 tokens; a pass of their own scores them (vk_docw_kernel, else vk_wide_kernel)
-		const bool docw_rwmd = rwmd_inj && p.gap_mode == 4 && c->max_len > VK_FAST_SENT_LEN && !getenv("VK_NO_DOCW");   // the relaxed 1:1 WMD: vk_docw_kernel's streaming arm
-		const bool apart_route = (is_align || (rwmd_inj && p.gap_mode == 4)) && c->h_apart && !c->h_apart->empty() && !getenv("VK_NO_APART");
-		const bool two_blocks = (is_align || rwmd_inj || bound_pass) && (long_apart || apart_route || (c->n_long_groups == 0 &&
-			c->max_len <= VK_FAST_SENT_LEN)) && (apart_route || c->max_len <= VK_MAX_SENT_LEN) && (rwmd_inj || bound_pass || p.gap_mode == 0 || (p.gap_mode == 1 && p.a_t >= 0.0f) || (p.gap_mode == 2 && wide_sub)) &&
-			plan32.fits && (bound_pass || p.gap_mode == 7 || !getenv("VK_NO_SCORE32"));
-		if ((bound_pass || p.gap_mode == 7) && !two_blocks)
-			return fail(VK_ERR_UNSUPPORTED, "exact transport / 1:n RWMD with a query of more than 16 tokens: the multi-block kernel does not fit this corpus (LDS)");
-		if (p.gap_mode == 7) memcpy(wp.qmass, qmass_all, sizeof wp.qmass);
-		if (only) {
-		} else if (two_blocks) {
-			if (bound_pass) {
-				wp.gap_mode = 5;
-				wp.mag = q->algorithm == VK_ALG_WRD ? c->d_mag : nullptr;
-				memcpy(wp.qmass, qmass_all, sizeof wp.qmass);
-				wp.wrd_raw_total = p.wrd_raw_total; wp.wmd_bound = q->algorithm == VK_ALG_WRD ? 0 : p.wmd_bound;
-			}
-			if (p.gap_mode == 2) { wp.gap_mode = (apart_route ? c->max_short_len : c->max_len) <= 32 ? 3 : 6; wp.wt = c->d_wt + 80; }   // register history of 32 / 64 rows, closure of w_t
-			VK_HIP(vk_launch_score32(&wp, wave_tiles, st));
-			if (long_apart && p.gap_mode == 7) VK_HIP(vk_launch_long_rwmd_fill(&wp, c->d_long_groups, c->n_long_groups, (int32_t)n, st));
-			else if (long_apart) {
-				VkWrdParams lw{};
-				fill_transport(lw);
-				lw.mag = q->algorithm == VK_ALG_WRD ? c->d_mag : nullptr;
-				memcpy(lw.qmass, qmass_all, sizeof lw.qmass);
-				lw.wrd_raw_total = p.wrd_raw_total; lw.wmd_bound = wp.wmd_bound;
-				lw.group_list = c->d_long_groups; lw.n_list = c->n_long_groups; lw.n_entries = (int32_t)n;
-				lw.scores = c->d_scores; lw.raw = c->d_raw; lw.boost = p.boost;
-				VK_HIP(vk_launch_long_bound(&lw, st));
-			}
-			wp.gap_mode = p.gap_mode;                                        // the traceback kernel knows 0 / 1 / 2
-			wp.wt = c->d_wt;                                                 // ... and walks the caller's table
-			if (apart_route && (docw || docw_rwmd)) {
-				if ((rc = wide_order(1))) return rc;
-				if (wp.n_order > 0) VK_HIP(vk_launch_docw(&wp, 0, st));
-			} else if (apart_route && docg_ok()) {
-				if ((rc = wide_order(1))) return rc;
-				if (wp.n_order > 0) VK_HIP(vk_launch_docg(&wp, 0, st));
-			} else if (apart_route) {   // general gaps, relaxed 1:1 WMD: row by row, but only the slices apart
-				if ((rc = wide_state(0, 1))) return rc;
-				if (wp.n_order > 0) VK_HIP(vk_launch_wide(&wp, 0, st));
-			}
-		}
-		else if (docw || docw_rwmd) {   // (the multi-block kernel does not fit this corpus: every slice on the sweep)
-			if ((rc = wide_order(0))) return rc;
-			if (wp.n_order > 0) VK_HIP(vk_launch_docw(&wp, 0, st));
-		}
-		else if (docg_ok()) {
-			if ((rc = wide_order(0))) return rc;
-			if (wp.n_order > 0) VK_HIP(vk_launch_docg(&wp, 0, st));
-		}
-		else {
-			if ((rc = wide_state(0))) return rc;
-			VK_HIP(vk_launch_wide(&wp, 0, st));
-		}
-		}
 	}
-	if (wide_score) {
-	} else if (is_align && !is_static && q->len_t == 1 && c->uniform_len == 1 && q->locality == VK_LOCAL && !p.pos_s) {
+	if (r.plan == vk_host::PLAN_MULTI_BLOCK) {
+		// a query of 17 .. 64 tokens: the multi-block kernel over the slices of at most 64 tokens (17 .. 32 tokens: two column blocks;
+		// 33 .. 64: one slice per wave and four), then a pass of their own over the slices it skips
+		const bool exact = exact_transport(q);   // stage 1: the bound over all slices
+		if (exact || r.score32_gap_mode == 7) memcpy(wp.qmass, qmass_all, sizeof wp.qmass);
+		if (exact) {
+			wp.mag = q->algorithm == VK_ALG_WRD ? c->d_mag : nullptr;
+			wp.wrd_raw_total = p.wrd_raw_total; wp.wmd_bound = q->algorithm == VK_ALG_WRD ? 0 : p.wmd_bound;
+		}
+		wp.gap_mode = r.score32_gap_mode;
+		if (r.wide_gap_mode == 2) wp.wt = c->d_wt + 80;   // register history of 32 / 64 rows, closure of w_t
+		VK_HIP(vk_launch_score32(&wp, r.wave_tiles, st));
+		if (r.pass[vk_host::CLASS_MID] == vk_host::PASS_LONG_RWMD_FILL) VK_HIP(vk_launch_long_rwmd_fill(&wp, c->d_long_groups, c->n_long_groups, (int32_t)n, st));
+		else if (r.pass[vk_host::CLASS_MID] == vk_host::PASS_LONG_BOUND) {
+			// exact transport over a corpus with long slices: the multi-block kernel skips them (their groups are padded, vk_corpus.cpp)
+			VkWrdParams lw{};
+			fill_transport(lw);
+			lw.mag = q->algorithm == VK_ALG_WRD ? c->d_mag : nullptr;
+			memcpy(lw.qmass, qmass_all, sizeof lw.qmass);
+			lw.wrd_raw_total = p.wrd_raw_total; lw.wmd_bound = wp.wmd_bound;
+			lw.group_list = c->d_long_groups; lw.n_list = c->n_long_groups; lw.n_entries = (int32_t)n;
+			lw.scores = c->d_scores; lw.raw = c->d_raw; lw.boost = p.boost;
+			VK_HIP(vk_launch_long_bound(&lw, st));
+		}
+		wp.gap_mode = r.wide_gap_mode;   // the kernels of the one-wave-per-slice family know 0 / 1 / 2 / 4
+		wp.wt = c->d_wt;                 // ... and walk the caller's table
+		if (r.wide_pass != vk_host::PASS_NONE && (rc = list_pass())) return rc;
+	} else if (r.plan == vk_host::PLAN_DOCW_ALL || r.plan == vk_host::PLAN_DOCG_ALL || r.plan == vk_host::PLAN_WIDE_ALL) {
+		// (the multi-block kernel does not take this query or this corpus: every slice on the one-wave-per-slice family)
+		if ((rc = list_pass())) return rc;
+	} else if (r.plan == vk_host::PLAN_SPAN) {
 		// span-embedding index: one vector per slice, one query vector -> the clipped cosine is the local alignment score.
 		// The aligner scores are written only if something reads them: the traceback kernel restates those of the winners, and
 		// without a booster the score IS the aligner score ((raw / 1) * 1)
-		span_skip_raw = !(q->submatch_weight > 0.0f) && ((q->want_flow && is_align) || !p.boost || !out->raw_score);
 		VkScoreParams ps = p;
-		if (span_skip_raw) ps.raw = nullptr;
-		if (!only) VK_HIP(vk_launch_span(&ps, st));
-	} else {
+		if (r.span_skip_raw) ps.raw = nullptr;
+		VK_HIP(vk_launch_span(&ps, st));
+	} else if (!wide_query) {
 	p.max_short_len = VK_FAST_SENT_LEN;
 	// the aligner scores of all slices: read by the submatch bound and, without traceback, for the winners; with traceback the
 	// flow kernel restates those of the winners
 	// (exact transport: the solver states them); a second output array costs the stream 1 % (2.90 -> 2.87 ms per 1 M x 32 x 300-d)
-	if (((is_align && q->want_flow) || exact_transport(q)) && !(q->submatch_weight > 0.0f) && !getenv("VK_KEEP_RAW")) p.raw = nullptr;
+	if (!r.raw) p.raw = nullptr;
 	p.s_rows_per_wave = is_static ? (c->max_group_tokens + 15) / 16 * 16 : c->max_group_tiles * 16;
 	p.h_rows = c->max_short_len + 1;
 	const int lt = q->len_t <= 4 ? 4 : q->len_t <= 8 ? 8 : q->len_t <= 12 ? 12 : 16;   // strip rows hold the padded query columns (launch_score_lt)
@@ -709,21 +609,22 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	// Linear / affine gaps take 112 registers in the register form.  VK_QREG=1 / VK_QLDS=1 force one or the other.
 	const bool reg_history = p.gap_mode == 3 || p.gap_mode == 6;
 	if (!is_static && c->prec == 0 && c->nk32 == 10 && c->tail == 1)
-		p.q_mode3 = getenv("VK_QLDS") ? 1 : getenv("VK_QREG") ? 0 : (reg_history ? 1 : 0);
-	if (!is_static && c->prec == 1 && c->nk32 == 19 && !getenv("VK_NO_F32_SPECIAL")) p.q_mode3 = 1;   // fp32 rows at 300-d: MODE 4 (all 19 blocks of a tile in flight)
+		p.q_mode3 = sw.qlds ? 1 : sw.qreg ? 0 : (reg_history ? 1 : 0);
+	if (!is_static && c->prec == 1 && c->nk32 == 19 && !sw.no_f32_special) p.q_mode3 = 1;   // fp32 rows at 300-d: MODE 4 (all 19 blocks of a tile in flight)
 	const size_t qlds = (!is_static && ((c->prec == 0 && c->nk32 == 24 && c->tail == 0) || p.q_mode3)) ? (size_t)c->nk32 * 1024 : 0;   // MODE 3 / 4: query tile in LDS
 	smem += qlds;
 	// the generic contextual kernel (MODE 1: fp32 tiles, or a d without a specialised form) stages the query tile in LDS when it fits
 	// beside the strips of at least two workgroups per CU
 	if (!is_static && qlds == 0 && !(c->prec == 0 && c->nk32 == 10 && c->tail == 1)) {
 		const size_t qb = ((size_t)c->tile_bytes + 1023) / 1024 * 1024;
-		if (2 * (smem + qb) <= 160 * 1024 && !getenv("VK_NO_QLDS1")) { p.q_lds = (int32_t)qb; smem += qb; }
+		if (2 * (smem + qb) <= 160 * 1024 && !sw.no_qlds1) { p.q_lds = (int32_t)qb; smem += qb; }
 	}
 	if (smem > 160 * 1024) return fail(VK_ERR_UNSUPPORTED, "LDS demand exceeds 160 KiB per workgroup");
 	const int64_t n_groups = (n + 3) / 4;
 	const int grid = (int)std::min<int64_t>((n_groups + 3) / 4, (int64_t)1 << 20);   // capped to residency by the launcher
 	// the 8-bit bound pass and exact scores of the contenders only, or the exact pass over every slice
-	bounded = bound_ok && kk <= VK_MAX_MATCHES && (p.gap_mode == 0 || p.gap_mode == 1 || p.gap_mode == 3 || p.gap_mode == 6);
+	bounded = bound_ok;
+	if (!bounded && r.plan == vk_host::PLAN_BOUNDED) c->query_route[VK_QR_PLAN] = vk_host::PLAN_FUSED;
 	if (bounded) {
 		// the bound kernel: the four waves' strips as above, and in place of the exact kernel's query tile the 8-bit one with the
 		// cells' constants behind it -- the region MODE 7 of vk_score_kernel steps over (NK32 KiB + VK_DEV_BOUND_CONST_BYTES)
@@ -733,8 +634,8 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		// the exact kernel over a group_list: one wave per workgroup, its strip and the exact query tile
 		const size_t smem_list = (size_t)lds_floats * 4 + qlds + (size_t)p.q_lds;
 		if ((rc = score_bounded(c, p, grid, smem, smem_bound, smem_list, kk, sel_floor, keep, st, &d_sel_bounded))) return rc;
-	} else if (!only) VK_HIP(vk_launch_score(&p, grid, smem, st));
-	if (c->n_long_groups > 0 && !only && !long_via_wide && !rwmd_long_doc) {
+	} else if (r.plan != vk_host::PLAN_LISTED) VK_HIP(vk_launch_score(&p, grid, smem, st));
+	if (r.pass[vk_host::CLASS_MID] == vk_host::PASS_FUSED_LONG) {
 		// slices longer than VK_FAST_SENT_LEN: one per wave, one wave per workgroup, LDS strip for the longest;
 		// general gaps take the LDS-history form (the four DPP rows share one history: only row 0 is active)
 		VkScoreParams pl = p;
@@ -751,12 +652,9 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		if (smem_l > 160 * 1024) return fail(VK_ERR_UNSUPPORTED, "LDS demand of the long-slice pass exceeds 160 KiB");
 		VK_HIP(vk_launch_score(&pl, c->n_long_groups, smem_l, st));
 	}
-	if ((xlong || long_via_wide || rwmd_long_doc) && !only) {
-		// slices beyond VK_MAX_SENT_LEN (whole documents; general gaps: beyond 64 tokens): one wave per slice, longest first
-		if ((rc = wide_state(0))) return rc;
-		// (linear / affine gaps: the skewed sweep of vk_doc_kernel -- no in-row dependency, a fifth of the time per row; round 4)
-		if (wp.n_order > 0) VK_HIP(doc_ok() ? vk_launch_doc(&wp, 0, st) : vk_launch_wide(&wp, 0, st));
-	}
+	// slices beyond VK_MAX_SENT_LEN (whole documents), or every slice of more than 64 tokens: one wave per slice, longest first
+	// (linear / affine gaps: the skewed sweep of vk_doc_kernel -- no in-row dependency, a fifth of the time per row; round 4)
+	if (r.wide_pass != vk_host::PASS_NONE && (rc = list_pass())) return rc;
 	}
 
 	if (exact_transport(q) && only) {
@@ -799,7 +697,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		// ---- stage 2: exact EMD on the candidates with the largest bounds, until the k-th best
 		// exact score is above every remaining bound (then no unsolved sentence can enter)
 		VK_HIP(hipEventRecord(c->ev[2], st));
-		if (getenv("VK_WRD_TURNS")) c->ev2_recorded = true;   // experiment: bound passes take turns like the alignment kernels
+		if (sw.wrd_turns) c->ev2_recorded = true;   // experiment: bound passes take turns like the alignment kernels
 		// (no turn-taking between handles here: ev2_recorded stays unset.  Two bound passes sharing the chip, each with its
 		// long epilogue, fill each other's gaps: 336 M pairs/s with three handles against 302 M/s when they queue)
 		// Round 1: the M largest bounds.  Its k-th best exact score theta prunes: every row whose bound is below
@@ -859,7 +757,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 				VK_HIP(hipMemcpyAsync(&count, c->d_counter, 4, hipMemcpyDeviceToHost, st));
 				VK_HIP(hipStreamSynchronize(st));
 				if (count == 0) break;
-				if (getenv("VK_DEBUG_CANDIDATES")) fprintf(stderr, "[vk] exact transport: round 2 solves %u candidates (theta %.6f, n %lld)\n", count, theta, (long long)n);
+				if (sw.debug_candidates) fprintf(stderr, "[vk] exact transport: round 2 solves %u candidates (theta %.6f, n %lld)\n", count, theta, (long long)n);
 				const int take = (int)std::min<size_t>(count, cap);
 				if ((rc = solve(c->d_keys[0], take, &ub_last, &n_cand))) return rc;
 				done = (size_t)count <= cap;   // every row that could still enter has been solved
@@ -885,14 +783,14 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	}
 
 	// ---- flow (traceback) of `count` slices named by device keys: narrow or wide kernel
-	const int ostride = (wide || flow_doc) ? 64 : 16;   // row stride of the mapping / edge_sim device arrays
+	const int ostride = r.ostride;   // row stride of the mapping / edge_sim device arrays
 	auto launch_flow = [&](const uint64_t *d_keys, int count) -> int {
-		if (wide || flow_doc) {
+		if (wide_family) {
 			wp.keys = d_keys; wp.raw_out = c->d_out_raw; wp.mapping = c->d_out_map; wp.edge_sim = c->d_out_sim;
 			int rcw = wide_state(count);
 			if (rcw) return rcw;
 			wp.dp_rows = nullptr; wp.dp_rows_len = 0;
-			if (xlong || doc_ok() || docw || docg_ok()) {
+			if (xlong || r.flow != vk_host::FLOW_WIDE) {
 				// Long winners: their similarities (canonical arithmetic, tag weights applied) restated beforehand by one wave per 16
 				// tokens, so that the serial sweep of a winner is its recurrence alone (5,000 tokens: 8.4 ms of a 12 ms query were the
 				// sweep restating 313 tiles one after the other; 3.6 ms since).  Within 2 GiB; else the sweep restates them itself.
@@ -909,9 +807,10 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 					wp.dp_rows = c->d_rows_out; wp.dp_rows_len = R;
 				}
 			}
-			if (docw && wp.dp_rows && wp.scratch && wp.scratch_stride >= (int64_t)vk_docw_scratch_bytes(c->max_len, nq)) VK_HIP(vk_launch_docw(&wp, count, st));
-			else if (docg_ok() && wp.dp_rows && wp.scratch && wp.scratch_stride >= (int64_t)vk_docg_scratch_bytes(c->max_len)) VK_HIP(vk_launch_docg(&wp, count, st));
-			else if (doc_ok() && wp.dp_rows && wp.scratch && wp.scratch_stride >= (int64_t)vk_doc_scratch_bytes(c->max_len, wp.gap_mode)) VK_HIP(vk_launch_doc(&wp, count, st));
+			// (the route's kernel where its rows and scratch came about, else vk_wide_kernel)
+			if (r.flow == vk_host::FLOW_DOCW && wp.dp_rows && wp.scratch && wp.scratch_stride >= (int64_t)vk_docw_scratch_bytes(c->max_len, nq)) VK_HIP(vk_launch_docw(&wp, count, st));
+			else if (r.flow == vk_host::FLOW_DOCG && wp.dp_rows && wp.scratch && wp.scratch_stride >= (int64_t)vk_docg_scratch_bytes(c->max_len)) VK_HIP(vk_launch_docg(&wp, count, st));
+			else if (r.flow == vk_host::FLOW_DOC && wp.dp_rows && wp.scratch && wp.scratch_stride >= (int64_t)vk_doc_scratch_bytes(c->max_len, wp.gap_mode)) VK_HIP(vk_launch_doc(&wp, count, st));
 			else VK_HIP(vk_launch_wide(&wp, count, st));
 			return VK_OK;
 		}
@@ -1086,11 +985,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		const bool tagged = vocab && q->tag_weights && q->q_tags && c->h_tag;
 		std::vector<int32_t> key_t((size_t)q->len_t), key_s;
 		for (int j = 0; vocab && j < q->len_t; j++) key_t[(size_t)j] = tagged ? q->q_token_ids[j] * 256 + (int32_t)(uint8_t)q->q_tags[j] : q->q_token_ids[j];
-		float total = (float)q->len_t;
-		if (q->tag_weights) {
-			total = 0.0f;
-			for (int j = 0; j < q->len_t; j++) total += q->tag_weights[j];
-		}
+		const float total = ref_total_of(q);
 		for (int i = 0; i < n_sel; i++) {
 			const int64_t row = rows_idx[(size_t)i];
 			const int32_t t_a = (*c->h_start)[(size_t)row], len_s = (*c->h_end)[(size_t)row] - t_a;
@@ -1114,13 +1009,13 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	std::vector<float> &raw_sel = keep.vec<float>((size_t)std::max(n_out, 1));
 	if (!do_flow && !(canon_tr && n_sel > 0) && out->raw_score && n_out > 0) {
 		// gather the aligner scores of the winners (a large result set: the whole array in one copy, gathered here)
-		if (n_out > 256 && !span_skip_raw) {
+		if (n_out > 256 && !r.span_skip_raw) {
 			std::vector<float> &all_raw = keep.vec<float>((size_t)n);
 			VK_HIP(hipMemcpyAsync(all_raw.data(), c->d_raw, (size_t)n * 4, hipMemcpyDeviceToHost, st));
 			VK_HIP(hipStreamSynchronize(st));
 			for (int i = 0; i < n_out; i++) raw_sel[(size_t)i] = all_raw[(size_t)row_at(i)];
 		} else for (int i = 0; i < n_out; i++) {
-			if (!span_skip_raw) VK_HIP(hipMemcpyAsync(&raw_sel[(size_t)i], c->d_raw + row_at(i), 4, hipMemcpyDeviceToHost, st));
+			if (!r.span_skip_raw) VK_HIP(hipMemcpyAsync(&raw_sel[(size_t)i], c->d_raw + row_at(i), 4, hipMemcpyDeviceToHost, st));
 		}
 		VK_HIP(hipStreamSynchronize(st));
 	}
@@ -1129,7 +1024,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		const float s = val[(size_t)src];
 		out->score[i] = s;
 		out->sentence[i] = sentence_of(row_at(src));
-		if (out->raw_score) out->raw_score[i] = (do_flow || canon_tr) ? raw[(size_t)src] : span_skip_raw ? s : raw_sel[(size_t)i];
+		if (out->raw_score) out->raw_score[i] = (do_flow || canon_tr) ? raw[(size_t)src] : r.span_skip_raw ? s : raw_sel[(size_t)i];
 		if (do_flow) {
 			for (int j = 0; j < q->len_t; j++) {
 				out->mapping[(size_t)i * q->len_t + j] = map[(size_t)src * ostride + j];
