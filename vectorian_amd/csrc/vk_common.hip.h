@@ -259,34 +259,38 @@ typedef __attribute__((ext_vector_type(2))) int i32x2;
 __device__ __forceinline__ i32x8 fp6_operand(const i32x4 lo, const i32x2 hi) {
 	return i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], 0, 0};
 }
-template <bool META = false>
-__device__ __forceinline__ f32x4 dot_tile_fp6(const uint8_t *__restrict__ qlds, const uint8_t *__restrict__ tile, int lane, int live6, f32x2 *meta = nullptr) {
-	i32x4 lo[VK_DEV_FP6_STEPS];
-	i32x2 hi[VK_DEV_FP6_STEPS];
-	// The lane's offsets and the scale operand are made anew for every tile (the empty asm hides that they never change): hoisted out
-	// of the kernel's loops they stay live through the DP and the 12-column form with general gaps takes 123 registers, past the
-	// budget of 120 (vk_score_m8.hip).  Three VALU instructions per tile.
+// The lane's offsets and the scale operand are made anew wherever they are needed (the empty asm hides that they never change): hoisted
+// out of the kernel's loops they stay live through the DP (vk_score_m8.hip).  A few VALU instructions per trip of the tile loop.
+__device__ __forceinline__ uint32_t fp6_lane_offset(int lane) {
 	uint32_t o16 = (uint32_t)lane * 16u;
 	asm volatile("" : "+v"(o16));
+	return o16;
+}
+// one tile's operands as its six loads leave them: lo / hi per K-step, and the 16 x (s_x, e_x) behind them
+template <bool META>
+__device__ __forceinline__ void load_tile_fp6(i32x4 (&lo)[VK_DEV_FP6_STEPS], i32x2 (&hi)[VK_DEV_FP6_STEPS], f32x2 &meta, const uint8_t *__restrict__ tile, int lane, int live6, uint32_t o16) {
+	const uint32_t o8 = o16 >> 1;
+#pragma unroll
+	for (int t = 0; t < VK_DEV_FP6_STEPS - 1; t++) {
+		const uint8_t *step = tile + t * VK_DEV_FP6_STEP_BYTES;
+		lo[t] = __builtin_nontemporal_load(reinterpret_cast<const i32x4 *>(step + o16));
+		hi[t] = __builtin_nontemporal_load(reinterpret_cast<const i32x2 *>(step + 1024 + o8));
+	}
+	// (s_x, e_x) of the lane's token: behind the whole K-steps (in front of the tile's loads the forms take more registers) and in
+	// front of the last one's masked loads
+	if constexpr (META) meta = __builtin_nontemporal_load(reinterpret_cast<const f32x2 *>(tile + (VK_DEV_FP6_TILE_BYTES(live6) - 128) + (lane & 15) * 8));
+	constexpr int t = VK_DEV_FP6_STEPS - 1;
+	const uint8_t *step = tile + t * VK_DEV_FP6_STEP_BYTES;
+	lo[t] = i32x4{0, 0, 0, 0}; hi[t] = i32x2{0, 0};
+	if (lane < 16 * live6) {
+		lo[t] = __builtin_nontemporal_load(reinterpret_cast<const i32x4 *>(step + o16));
+		hi[t] = __builtin_nontemporal_load(reinterpret_cast<const i32x2 *>(step + live6 * 256 + o8));
+	}
+}
+__device__ __forceinline__ f32x4 mma_tile_fp6(const i32x4 (&lo)[VK_DEV_FP6_STEPS], const i32x2 (&hi)[VK_DEV_FP6_STEPS], const uint8_t *__restrict__ qlds, uint32_t o16) {
 	const uint32_t o8 = o16 >> 1;
 	int one = 0x7f7f7f7f;   // E8M0 127 in every byte: x 1
 	asm volatile("" : "+v"(one));
-#pragma unroll
-	for (int t = 0; t < VK_DEV_FP6_STEPS; t++) {
-		const uint8_t *step = tile + t * VK_DEV_FP6_STEP_BYTES;
-		if (t == VK_DEV_FP6_STEPS - 1) {
-			lo[t] = i32x4{0, 0, 0, 0}; hi[t] = i32x2{0, 0};
-			if (lane < 16 * live6) {
-				lo[t] = __builtin_nontemporal_load(reinterpret_cast<const i32x4 *>(step + o16));
-				hi[t] = __builtin_nontemporal_load(reinterpret_cast<const i32x2 *>(step + live6 * 256 + o8));
-			}
-		} else {
-			lo[t] = __builtin_nontemporal_load(reinterpret_cast<const i32x4 *>(step + o16));
-			hi[t] = __builtin_nontemporal_load(reinterpret_cast<const i32x2 *>(step + 1024 + o8));
-		}
-	}
-	// (s_x, e_x) of the lane's token, behind the tile's own loads and in front of the MFMAs that wait for them
-	if constexpr (META) *meta = __builtin_nontemporal_load(reinterpret_cast<const f32x2 *>(tile + (VK_DEV_FP6_TILE_BYTES(live6) - 128) + (lane & 15) * 8));
 	f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
 	for (int t = 0; t < VK_DEV_FP6_STEPS; t++) {
@@ -296,17 +300,49 @@ __device__ __forceinline__ f32x4 dot_tile_fp6(const uint8_t *__restrict__ qlds, 
 	}
 	return acc;
 }
+// the product alone (the probe of tests/test_gpu_bound6_product.py reads the MFMA's floats)
+__device__ __forceinline__ f32x4 dot_tile_fp6(const uint8_t *__restrict__ qlds, const uint8_t *__restrict__ tile, int lane, int live6) {
+	i32x4 lo[VK_DEV_FP6_STEPS];
+	i32x2 hi[VK_DEV_FP6_STEPS];
+	f32x2 meta;
+	const uint32_t o16 = fp6_lane_offset(lane);
+	load_tile_fp6<false>(lo, hi, meta, tile, lane, live6, o16);
+	return mma_tile_fp6(lo, hi, qlds, o16);
+}
 
 // the cell is sim_tile_i8's with the MFMA's float in place of (float) I; the 16 x (s_x, e_x) follow the tile's K-steps
-__device__ __forceinline__ f32x4 sim_tile_fp6(const uint8_t *__restrict__ qlds, const uint8_t *__restrict__ tile, int lane, int live6) {
-	f32x2 m;
-	const f32x4 acc = dot_tile_fp6<true>(qlds, tile, lane, live6, &m);
+__device__ __forceinline__ f32x4 cell_tile_fp6(const f32x4 acc, const f32x2 m, const uint8_t *__restrict__ qlds, int lane) {
 	const float *cst = reinterpret_cast<const float *>(qlds + VK_DEV_FP6_QTILE_BYTES) + (lane >> 4) * 4;
 	const f32x4 cs = *reinterpret_cast<const f32x4 *>(cst), ca = *reinterpret_cast<const f32x4 *>(cst + 16), cb = *reinterpret_cast<const f32x4 *>(cst + 32);
 	f32x4 ub;
 #pragma unroll
 	for (int r = 0; r < 4; r++) ub[r] = clip01(((m[0] * cs[r]) * acc[r] + m[1] * ca[r]) + cb[r]);
 	return ub;
+}
+
+// T consecutive tiles per trip of the kernel's tile loop (VK_FP6_TILES; what is left of a group goes one tile at a time): the
+// loads of all T, their (s_x, e_x) included, are issued before the first MFMA waits for any -- T times 3,968 bytes in flight per
+// wave where one tile per trip kept one.  No branch on the number of tiles in here: a join between the loads and the
+// MFMAs makes the compiler wait for every load of every tile before the first product.
+#ifndef VK_FP6_TILES
+#define VK_FP6_TILES 2
+#endif
+template <int T>
+__device__ __forceinline__ void sim_tiles_fp6(f32x4 (&ub)[T], const uint8_t *__restrict__ qlds, const uint8_t *__restrict__ tile, int tile_bytes, int lane, int live6) {
+	i32x4 lo[T][VK_DEV_FP6_STEPS];
+	i32x2 hi[T][VK_DEV_FP6_STEPS];
+	f32x2 meta[T];
+	const uint32_t o16 = fp6_lane_offset(lane);
+#pragma unroll
+	for (int i = 0; i < T; i++) load_tile_fp6<true>(lo[i], hi[i], meta[i], tile + (int64_t)i * tile_bytes, lane, live6, o16);
+	if constexpr (T > 1) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+	for (int i = 0; i < T; i++) {
+		ub[i] = cell_tile_fp6(mma_tile_fp6(lo[i], hi[i], qlds, o16), meta[i], qlds, lane);
+		// the cells are taken as used HERE: the caller stores them under a lane guard, and whatever only that store reads the
+		// compiler sinks into the guarded block -- the last tile's (s_x, e_x) load went there, behind the first wait
+		asm volatile("" : "+v"(ub[i]));
+	}
 }
 
 // fp32 unit rows (VK_PREC_F32, the reference's own precision), NB16 blocks of 16 features known at compile time: all the
@@ -882,12 +918,25 @@ __device__ __forceinline__ float dp_general(const float *__restrict__ S, float *
 // subadditive costs such as 1 - 2^(-k/c)); a composed gap is rounded once here and twice in the chain, a difference of an ulp,
 // far inside the 1e-4 of the scores -- the tracebacks of the winners walk the caller's table sequentially (vk_flow_kernel).
 // The border row is set directly: H[0][j] = -w_t(j), one gap, from `wt0`.
-template <int LT, int MAXLEN>
+template <int LT, int MAXLEN, bool FRESH = true>
 __device__ __forceinline__ float dp_general_reg(const float *__restrict__ S, int rowbase, int len, int maxlen, int v,
 	const DpArgs &a, const float (&wsr)[MAXLEN + 1], const float (&wtr)[LT]) {
 
-	const bool is_local = a.locality == VK_DEV_LOCAL;
-	const bool is_global = a.locality == VK_DEV_GLOBAL;
+	// The locality flag and the lane's column are made anew for every call (the empty asm hides that they never change, as in
+	// fp6_lane_offset).  The selects they feed -- a border term per row, an in-row cost per column -- are invariants of the kernel's
+	// group loop: hoisted out of it they are MAXLEN + 1 + LT - 1 registers (44 at 32 rows and 12 columns, 76 at 64 rows) that stay
+	// live through the tile loop, where nothing reads them.  Redone per call they live inside the DP only, at the price of about
+	// a hundred more VALU instructions per group of 32-token slices (5 % of the DP's).  The values and every float operation on
+	// them are what they were.  FRESH = false leaves them to the compiler: the 64-row form of the 8-bit pass, which LDS
+	// holds to two workgroups per CU whatever its registers, only paid for the redoing (vk_score_kernel).
+	int loc = a.locality, vsel = v;
+	if constexpr (FRESH) {
+		asm volatile("" : "+v"(loc));
+		asm volatile("" : "+v"(vsel));
+		loc = __builtin_amdgcn_readfirstlane(loc);
+	}
+	const bool is_local = loc == VK_DEV_LOCAL;
+	const bool is_global = loc == VK_DEV_GLOBAL;
 	const float floor0 = is_local ? 0.0f : VK_NEG_INF;
 	const bool last_col = v == a.len_t - 1;
 	const float wt_border = a.wt[v + 1];             // distance from the border column to column v + 1 (chains of gaps allowed: closure)
@@ -898,7 +947,7 @@ __device__ __forceinline__ float dp_general_reg(const float *__restrict__ S, int
 	// preset, a DPP move and a subtract.
 	float wtv[16];
 #pragma unroll
-	for (int k = 1; k < LT; k++) wtv[k] = v >= k ? wtr[k] : __builtin_inff();
+	for (int k = 1; k < LT; k++) wtv[k] = vsel >= k ? wtr[k] : __builtin_inff();
 
 	float hreg[MAXLEN + 1];
 	float h = is_global ? -wt_border0 : 0.0f;

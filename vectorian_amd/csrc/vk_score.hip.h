@@ -3,6 +3,7 @@
 #ifndef VK_SCORE_HIP_H
 #define VK_SCORE_HIP_H
 
+#include <type_traits>
 #include "vk_common.hip.h"
 
 // ---------------------------------------------------------------------------
@@ -87,9 +88,12 @@ __global__ __launch_bounds__(256) VK_SCORE_KERNEL_ATTR void vk_score_kernel(VkSc
 	a.wrd_raw_total = p.wrd_raw_total;
 	const float inv_ref = p.ref_total;
 	// tag-weighted modifier: this lane's four query columns (MFMA layout: 4*(lane>>4) + r)
+	// the bound pass is never taken with tag weights (bound_wanted in vk_route_host.h; the launchers of MODE 7 / 8 refuse pos_s):
+	// its kernels do not carry the lane's eight modifier registers through their loops
+	constexpr bool TAGS = MODE != 7 && MODE != 8;
 	float twl[4] = {1.0f, 1.0f, 1.0f, 1.0f};
 	int tposl[4] = {0, 0, 0, 0};
-	if (p.pos_s) {
+	if (TAGS && p.pos_s) {
 		const int cbase = (MODE == 2) ? (lane & 3) * 4 : (lane >> 4) * 4;
 #pragma unroll
 		for (int r = 0; r < 4; r++) { twl[r] = p.tw[cbase + r]; tposl[r] = p.tpos[cbase + r]; }
@@ -183,13 +187,33 @@ __global__ __launch_bounds__(256) VK_SCORE_KERNEL_ATTR void vk_score_kernel(VkSc
 				tp += p.tile_bytes;
 			}
 			if (ntiles > 0) { prev_tile = tile0 + ntiles - 1; prev_row = ntiles - 1; }
+			if constexpr (MODE == 8) {
+				// VK_FP6_TILES tiles per trip while the group has that many left, all their loads ahead of the first MFMA; then what
+				// is left (fewer than T; with ti0 = 1 a group may have no tile at all) one tile per trip.  Both bounds are
+				// wave-uniform: a tile past the group's last is neither loaded nor written to the strip
+				// the 64-row history (GAP 6) keeps one tile per trip: with two its forms allocate 128 registers, past the 120 that the
+				// 32-row forms keep to; no corpus of that shape has been measured either way
+				constexpr int T = GAP == 6 ? 1 : VK_FP6_TILES;
+				const auto tiles = [&](auto tc, int ti) {
+					constexpr int N = decltype(tc)::value;
+					f32x4 ub[N];
+					sim_tiles_fp6<N>(ub, qlds, tp, p.tile_bytes, lane, p.bound_live);
+#pragma unroll
+					for (int i = 0; i < N; i++)
+						if ((lane >> 4) * 4 < LT) *reinterpret_cast<f32x4 *>(S + ((ti + i) * 16 + (lane & 15)) * LT + (lane >> 4) * 4) = ub[i];
+					tp += (int64_t)N * p.tile_bytes;
+				};
+				int ti = ti0;
+				for (; ti + T <= ntiles; ti += T) tiles(std::integral_constant<int, T>{}, ti);
+				if constexpr (T > 1)
+					for (; ti < ntiles; ti++) tiles(std::integral_constant<int, 1>{}, ti);
+			} else
 			for (int ti = ti0; ti < ntiles; ti++) {
 				f32x4 acc;
 				if constexpr (MODE == 0) acc = sim_tile<NK32, TAIL>(qf, tp, lane);
 				else if constexpr (MODE == 3) acc = sim_tile_qlds<NK32, TAIL>(qlds, tp, lane);
 				else if constexpr (MODE == 4) acc = sim_tile_f32_qlds<NK32>(qlds, tp, lane);
 				else if constexpr (MODE == 7) acc = sim_tile_i8<NK32>(qlds, tp, lane, p.bound_live);
-				else if constexpr (MODE == 8) acc = sim_tile_fp6(qlds, tp, lane, p.bound_live);
 				else {
 					// two calls, not one with a selected pointer: an LDS-or-global pointer is a flat pointer, and flat loads count
 					// on both wait counters -- every batch of tile loads would be waited for in full
@@ -198,7 +222,7 @@ __global__ __launch_bounds__(256) VK_SCORE_KERNEL_ATTR void vk_score_kernel(VkSc
 					if (p.q_lds > 0) acc = sim_tile_generic<DEEP, PREC>(qlds, tp, p.nk32, p.tail, lane);
 					else acc = sim_tile_generic<DEEP, PREC>(p.qtile, tp, p.nk32, p.tail, lane);
 				}
-				if (p.pos_s) {
+				if (TAGS && p.pos_s) {
 					const int ps = p.pos_s[(tile0 + ti) * 16 + (lane & 15)];
 #pragma unroll
 					for (int r = 0; r < 4; r++) acc[r] = tag_weighted(acc[r], twl[r], ps, tposl[r], p.tw_keep, p.tw_threshold);
@@ -231,7 +255,10 @@ __global__ __launch_bounds__(256) VK_SCORE_KERNEL_ATTR void vk_score_kernel(VkSc
 		else if constexpr (GAP == 1) raw = dp_affine<LT>(S, rb, lenc, maxlen, v, a);
 		else if constexpr (GAP == 2) raw = dp_general<LT>(S, Hh, p.h_rows, rb, lenc, maxlen, lane, a);
 		else if constexpr (GAP == 3) raw = dp_general_reg<LT, 32>(S, rb, lenc, maxlen, v, a, wsr, wtr);
-		else if constexpr (GAP == 6) raw = dp_general_reg<LT, 64>(S, rb, lenc, maxlen, v, a, wsr, wtr);
+		// MODE 7 with the 64-row history (config 5 of the benchmark: 768-d rows) keeps the DP's invariants for the kernel's lifetime:
+		// 65 KB of LDS per workgroup admit two per CU, so 111 registers buy nothing there where 187 fit, and redoing 80 selects per
+		// group cost 1 % of the kernel (4.40 -> 4.44 ms)
+		else if constexpr (GAP == 6) raw = dp_general_reg<LT, 64, MODE != 7>(S, rb, lenc, maxlen, v, a, wsr, wtr);
 		else if constexpr (GAP == 4) {
 			// stage 1 of the full WMD over normalised bags of words = the WRD bound with unit magnitudes
 			if (a.wmd_bound == 1) raw = wrd_bound_rows<LT>(S, rb, lenc, maxlen, v, a, nullptr, nullptr, 1.0f / (float)a.len_t);
@@ -325,10 +352,12 @@ static hipError_t launch_sized(K kernel, const VkScoreParams &p, int want_blocks
 	const bool dp_bound = p.layout == VK_DEV_LAYOUT_STATIC || (p.nk32 <= 3 && p.bound_bits == 0);
 	// the 8-bit shadow (MODE 7, 328-byte rows; 1 M x 32 tokens, general gaps): 1.58 - 1.61 ms at 3 per CU, 1.60 - 1.65 at 4, 1.70 at 5, 1.80 at 2 --
 	// and three waves per SIMD of its 120 VGPRs leave room for the rounds' exact kernel beside it (vk_score_m7.hip)
-	// the 6-bit shadow (MODE 8, 3,968-byte tiles, the same shape): ms_per_step 1.44 at 3 per CU, 1.51 at 4, 1.52 at 5, 1.72 at 2 -- at 4 and 5 the
-	// kernel alone is faster (1.34 / 1.30 ms against 1.42) but the rounds lose their place beside the peer's pass
+	// the 6-bit shadow (MODE 8, 3,968-byte tiles, the same shape; two tiles per trip, 104 VGPRs, four waves per SIMD at the most):
+	// ms_per_step 1.59 at 2 per CU, 1.44 at 3, 1.40 at 4 on a machine where the kernel before it (118 VGPRs, one tile per trip)
+	// took 1.47 at 3, 1.53 - 1.56 at 4 and 1.53 at 5 -- at 4 that kernel alone was faster (1.35 ms) and the step slower, the
+	// rounds waiting for the peer's pass; this one keeps ms_per_step within 0.02 ms of kernel_ms at 4
 	// the 12-step shadow (768-d rows, 1 M slices of 8 .. 64 tokens, 64-row history): LDS and registers admit two per CU -- 4.40 ms; one: 5.98 ms
-	const int stream_cap = (p.bound_bits == 0 && p.nk32 >= 5 && p.nk32 <= 7) ? 4 : 3;
+	const int stream_cap = ((p.bound_bits == 0 && p.nk32 >= 5 && p.nk32 <= 7) || p.bound_bits == 6) ? 4 : 3;
 	if (occ > stream_cap && !dp_bound && !bound_pass) occ = stream_cap;   // the static layout is DP-bound, not a stream: keep full residency
 	// 768-d rows: a wave already keeps 24 KiB of loads in flight per tile; one workgroup per CU measured fastest
 	// (ragged 8..64 tokens, 400 k sentences: 3.37 ms at 1, 3.45 ms at 2 per CU)

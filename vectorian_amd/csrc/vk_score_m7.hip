@@ -1,14 +1,12 @@
 // vk_score_m7.hip -- vk_score_kernel, MODE 7: the bound pass over the 8-bit shadow (see vk_score.hip.h); the 64-row register
 // history of general gaps is in vk_score_m7w.hip.
-// A budget of 120 VGPRs (a target the compiler may exceed rather than spill to scratch).  With general gaps (GAP 3) the kernel takes 110 /
-// 114 / 118 / 122 VGPRs for queries padded to 4 / 8 / 12 / 16 columns, no AGPRs, and keeps 54 - 58 SGPRs of its gap tables in VGPR lanes
-// (counted in those figures).  Up to 12 columns that allocates 112 - 120: three waves per SIMD leave 152 of the 512, room for a wave of
-// the exact kernel (136: the rounds' rescoring of this handle and of the peer) beside the bound pass -- the headline's shape, and the only
-// one this was measured on.  Without the budget the 12-column form allocated 128 (118 + 4 AGPRs for the MFMA result), three waves left
-// 128, and the exact kernel waited for the peer's whole bound pass (1.47 ms in the trace).  13 - 16 query tokens: 122 allocates 128 with
-// the budget too, so there the rescoring waits its turn behind the peer's bound pass; results are the same, the overlap is lost.
-// The twelve-step form (768-d rows) takes 117 / 121 / 125 / 125 under the same budget: from 8 columns on it allocates 128 like the
-// 16-column form above (DESIGN 11.3 has the whole table).
+// A budget of 120 VGPRs (a target the compiler may exceed rather than spill to scratch).  It was set when the general-gap forms took 110 /
+// 114 / 118 / 122 VGPRs for queries padded to 4 / 8 / 12 / 16 columns: 44 of those were loop invariants of the DP that the compiler
+// kept for the kernel's lifetime (dp_general_reg makes them per group now), and eight were the tag modifier's, which a
+// bound pass never has.  Today the forms take 66 / 70 / 74 / 81 (five K-steps) and 69 / 70 / 74 / 79 (twelve), allocate 72 - 88 and keep
+// five waves per SIMD or more; three workgroups per CU (launch_sized) leave more than half of the registers to the rounds' exact kernel,
+// whose rescoring form allocates 96 at 300-d.  The gap tables still spill 50 - 60 SGPRs into VGPR lanes (counted in those figures).
+// DESIGN 11.9 has the whole table; nothing but the headline's shape was timed.
 #define VK_SCORE_VGPRS 120
 #include "vk_score.hip.h"
 
@@ -27,6 +25,7 @@ static hipError_t launch_m7(const VkScoreParams *p, int32_t grid, size_t smem_by
 }
 extern "C" hipError_t vk_launch_score_m7(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream) {
 	if (p->bound_live < 1 || p->bound_live > 4) return hipErrorInvalidValue;
+	if (p->pos_s) return hipErrorInvalidValue;   // no tag weights under a bound (vk_score.hip.h, TAGS)
 	if (p->nk32 == 5) return launch_m7<5>(p, grid, smem_bytes, stream);
 	if (p->nk32 == 12) return launch_m7<12>(p, grid, smem_bytes, stream);
 	return hipErrorInvalidValue;
