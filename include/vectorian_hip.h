@@ -33,17 +33,20 @@ extern "C" {
 
 #define VK_ABI_VERSION 12
 #define VK_MAX_QUERY_LEN 64   /* query tokens, every strategy */
-#define VK_MAX_LONG_QUERY_LEN 512 /* alignments (VK_ALG_ALIGN, submatch_weight = 0) over slices of at most VK_FAST_SENT_LEN tokens: queries of up to
+#define VK_MAX_LONG_QUERY_LEN 512 /* alignments (VK_ALG_ALIGN, submatch_weight = 0) over slices of at most VK_MAX_SENT_LEN tokens: queries of up to
                                  this many tokens (a whole paragraph as the query) -- one wave per slice with the roles swapped, lanes = the
-                                 slice's tokens, the query's tokens streamed (vk_longq_kernel); upstream's own bound is the int16 of a
-                                 mapping (metric/alignment.h:357-358) */
+                                 slice's tokens, the query's tokens streamed (vk_longq_kernel; slices of more than VK_FAST_SENT_LEN tokens
+                                 in column blocks of 64 tokens); a corpus that holds a slice of more than VK_MAX_SENT_LEN tokens returns
+                                 VK_ERR_UNSUPPORTED for such a query; upstream's own bound is the int16 of a mapping
+                                 (metric/alignment.h:357-358) */
 #define VK_FAST_QUERY_LEN 16  /* queries up to this length run in the fused kernels (one 16-wide MFMA column block); longer ones
                                  take the multi-block kernel (2 or 4 column blocks) or, where that does not apply, a
                                  one-wave-per-slice kernel, ~10x slower */
 #define VK_MAX_SENT_LEN 512   /* tokens per sentence (slice), every algorithm; see VK_MAX_DOC_LEN */
 #define VK_FAST_SENT_LEN 64   /* slices up to this length run 4 per wave in the fused kernel (|s| <= 64); longer
                                  ones take a second launch, one slice per wave (exact transport: a slower solver; with a query of
-                                 more than VK_FAST_QUERY_LEN tokens its state lives in global memory) */
+                                 more than VK_FAST_QUERY_LEN tokens its state lives in global memory; with one of more than
+                                 VK_MAX_QUERY_LEN tokens: the block form of vk_longq_kernel) */
 #define VK_MAX_DOC_LEN 32767  /* alignments (VK_ALG_ALIGN): tokens per slice when slices are whole documents -- what the int16 of a
                                  mapping can name, upstream's own bound (metric/alignment.h:357-358).  A corpus that holds a slice
                                  of more than VK_MAX_SENT_LEN tokens is scored by one wave per slice with the slice's state (column
@@ -111,7 +114,7 @@ typedef struct {
 
 typedef struct {
 	int32_t algorithm;       /* vk_algorithm */
-	int32_t len_t;           /* query tokens, 1..VK_MAX_QUERY_LEN (alignments: ..VK_MAX_LONG_QUERY_LEN) */
+	int32_t len_t;           /* query tokens, 1..VK_MAX_QUERY_LEN (alignments over slices of at most VK_MAX_SENT_LEN tokens: ..VK_MAX_LONG_QUERY_LEN) */
 	const void *q_vectors;   /* host [len_t x d] row-major */
 	int32_t q_dtype;         /* vk_dtype */
 	int32_t q_normalize;     /* 1: rows are L2-normalised by the library (Vectors.normalized) */

@@ -359,6 +359,7 @@ static int set_slices_impl(vk_corpus_t *c, const int64_t *start, const int64_t *
 	c->n_entries = n_entries;
 	c->d_wide_order.reset(); c->d_xlong_order.reset(); c->d_apart_order.reset();
 	c->n_wide_order = c->n_xlong_order = c->n_apart_order = -1;   // the work list of the one-wave-per-slice pass follows the table
+	c->lq.order.reset(); c->lq.n_order = -1;                      // ... and that of the long queries' block form
 	c->n_long_groups = (int)long_groups.size();
 	c->max_len = max_len;
 	c->max_short_len = max_short;

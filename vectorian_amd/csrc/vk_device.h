@@ -304,7 +304,7 @@ struct VkLongqParams {
 	int32_t locality;
 	int32_t gap_mode;          // 0 linear, 1 affine, 2 general
 	float gs, gt, a_s, a_t, open_s, open_t;
-	const float *ws;           // general: w_s[0 .. 64]
+	const float *ws;           // general: w_s[0 .. 64] (block form: [0 .. 512 + 8])
 	const float *wt;           // general: w_t[0 .. len_t]
 	int32_t wt_tail;           // general, scoring pass: w_t[k] == w_t[wt_tail] for every k >= wt_tail up to len_t (0: no such tail)
 	const int8_t *pos_s;       // tag-weighted similarity modifier (null: off)
@@ -325,6 +325,11 @@ struct VkLongqParams {
 	int32_t out_stride;
 	uint8_t *scratch;          // one region of scratch_stride bytes per workgroup (vk_longq_scratch_bytes): the matrix of general gaps, the cells' records
 	int64_t scratch_stride;
+	// the block form (slices of up to 512 tokens, vk_launch_longq_blocks): the scoring pass's work list -- rows of the slice table of
+	// 65 .. 512 tokens, longest first -- and where the records and the unmodified similarities begin in a scratch region (vk_longq_host.h)
+	const int32_t *order;
+	int32_t n_order;
+	int64_t dm_off, su_off;
 };
 
 #ifdef __cplusplus
@@ -338,6 +343,10 @@ int32_t vk_longq_blocks(int32_t len_t, int32_t max_len, int64_t n_sent, int32_t 
 int32_t vk_longq_hm_in_lds(int32_t len_t, int32_t max_len);
 int32_t vk_longq_stride(int32_t max_len);
 hipError_t vk_launch_longq(const VkLongqParams *p, int32_t flow_k, hipStream_t stream);
+// the block form: flow_k == 0 scores the p->n_order rows of p->order, flow_k > 0 retraces the winners of p->keys (of any length);
+// max_len: the corpus's longest slice of at most 512 tokens (the scratch regions' rows)
+hipError_t vk_launch_longq_blocks(const VkLongqParams *p, int32_t max_len, int32_t flow_k, hipStream_t stream);
+int32_t vk_longq_blocks_grid(int32_t len_t, int32_t max_len, int32_t gap_mode, int32_t flow_k, int64_t n_items);
 hipError_t vk_launch_wide(const VkWideParams *p, int32_t flow_k, hipStream_t stream);
 // whole documents under linear / affine gaps, queries of at most 16 tokens: the skewed sweep (vk_doc.hip); flow_k > 0: p->dp_rows required
 hipError_t vk_launch_doc(const VkWideParams *p, int32_t flow_k, hipStream_t stream);

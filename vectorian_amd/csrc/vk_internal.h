@@ -237,6 +237,8 @@ struct vk_corpus : vk_corpus_shape {
 		vk_devbuf<int32_t> il;
 		vk_devbuf<float> table;
 		vk_devbuf<uint8_t> scratch, fscratch;
+		vk_devbuf<uint8_t> bscratch;                     // scratch of the block form's scoring pass (slices of 65 .. VK_MAX_SENT_LEN tokens)
+		vk_devbuf<int32_t> order; int32_t n_order = -1;   // ... its work list: those rows of the slice table, longest first (-1: not built)
 		vk_devbuf<float> raw, sim;
 		vk_devbuf<int16_t> map;
 	} lq;

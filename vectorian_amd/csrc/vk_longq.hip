@@ -1,6 +1,6 @@
 // vk_longq.hip -- alignments of queries of 65 .. 512 tokens (round 4; refused until then: a lane per query column bounds the other
 // kernels at 64 tokens, upstream's only bound is the int16 of a mapping, vectorian/core/cpp/metric/alignment.h:357-358).
-#include "vk_common.hip.h"
+#include "vk_longq.hip.h"
 
 // ---------------------------------------------------------------------------
 // Roles swapped, anti-diagonal sweep.  One wave per slice (slices of at most 64 tokens: sentences), lane = slice token u - 1,
@@ -25,60 +25,17 @@
 // kernel.
 // ---------------------------------------------------------------------------
 
-// the strip's row: the corpus's longest slice rounded up to 16 columns (a 32-token corpus takes half the LDS of a 64-token one:
-// twice the waves per CU)
-static inline int longq_stride(int max_len) { const int w = (max_len + 15) / 16 * 16; return w < 16 ? 16 : w > 64 ? 64 : w; }
+// Strides, the carve-up of LDS and of a scratch region, grids: vk_longq_host.h (host only; both forms of the kernel)
+extern "C" int32_t vk_longq_stride(int32_t max_len) { return vk_host::longq_stride(max_len); }
 
-struct VkLongqGeom { int lt_pad; size_t s_bytes, hm_bytes, dm_bytes, su_bytes; };
-
-static inline VkLongqGeom longq_geom(int len_t, bool general, bool flow, bool tagged) {
-	VkLongqGeom g;
-	g.lt_pad = (len_t + 15) / 16 * 16;
-	g.s_bytes = (size_t)g.lt_pad * 64 * 4;
-	g.hm_bytes = general ? (size_t)(len_t + 1) * 64 * 4 : 0;            // H[v][lane]
-	g.dm_bytes = flow ? (size_t)(len_t + 1) * 64 * 2 : 0;               // direction | flags | gap length per cell
-	g.su_bytes = (flow && tagged) ? (size_t)g.lt_pad * 64 * 4 : 0;      // unmodified similarities (reported per edge)
-	return g;
-}
-
-extern "C" int32_t vk_longq_stride(int32_t max_len) { return longq_stride(max_len); }
-
+// (the three below: this unit's form, over slices of at most 64 tokens, as its callers have known them)
 extern "C" size_t vk_longq_scratch_bytes(int32_t len_t, int32_t gap_mode, int32_t flow, int32_t tagged) {
-	const VkLongqGeom g = longq_geom(len_t, gap_mode == 2, flow != 0, tagged != 0);
-	return (g.hm_bytes + g.dm_bytes + g.su_bytes + 255) / 256 * 256 + 256;
+	return vk_host::longq_geometry_of(len_t, 64, gap_mode, flow != 0, tagged != 0).scratch_bytes;
 }
 
 extern "C" size_t vk_longq_lds_bytes(int32_t len_t, int32_t max_len, int32_t flow) {
-	return (size_t)((len_t + 15) / 16 * 16) * longq_stride(max_len) * 4 + (flow ? VK_CANON_LDS : 0) + 64;
+	return vk_host::longq_geometry_of(len_t, max_len > 64 ? 64 : max_len, 0, flow != 0, false).lds_bytes;
 }
-
-// value of lane - 1 (lane 0: `border`): one DPP move across the wave (wave_shr:1; the first version shifted through ds_bpermute, an LDS
-// round trip per step and register, and twice per step)
-__device__ __forceinline__ float lane_up(float x, float border) {
-	return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, border), __builtin_bit_cast(int, x), 0x138, 0xf, 0xf, false));
-}
-
-// 300-d bf16 rows: the slice's token tiles (up to three at a time) stay in registers as A fragments while the query's tiles stream
-// past them -- each query tile is fetched from L2 once per slice (the second and third use hit the L1) instead of once per token
-// tile, and the token tiles once instead of once per query tile: 407 -> 97 KB of L2 traffic per 32-token slice and 100-token query,
-// which is what the first form of this pass was bound by (39 -> ms per million slices).  Plain loads for the query
-// tile (it is re-read by every wave), same MFMA sequence as sim_tile.
-template <int NK, bool HALF>
-__device__ __forceinline__ f32x4 longq_sim_tile(const QFrag<NK, HALF> &f, const uint8_t *__restrict__ qtile, int lane) {
-	bf16x8 x[NK];
-#pragma unroll
-	for (int t = 0; t < NK; t++) {
-		if (HALF && t == NK - 1) x[t] = load_half_block(qtile + t * 1024, lane, false);
-		else x[t] = *reinterpret_cast<const bf16x8 *>(qtile + t * 1024 + lane * 16);
-	}
-	f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-	for (int t = 0; t < NK; t++) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.q[t], x[t], acc, 0, 0, 0);
-	acc[0] = clip01(acc[0]); acc[1] = clip01(acc[1]); acc[2] = clip01(acc[2]); acc[3] = clip01(acc[3]);
-	return acc;
-}
-
-enum { LQ_STOP = 0, LQ_DIAG = 1, LQ_UP = 2, LQ_LEFT = 3 };   // D_* of the oracle; bits 0-1 of a cell's record, bit 2: E extended, bit 3: F extended, bits 4..: gap length
 
 // HL: general gaps, scoring pass: the matrix H[v][lane] in LDS behind the strip (queries of up to ~280 tokens over 64-token slices,
 // ~570 over 32-token ones: vk_longq_hm_in_lds) instead of the workgroup's scratch region in global memory -- the candidate scans
@@ -369,11 +326,7 @@ __global__ __launch_bounds__(64) void vk_longq_kernel(VkLongqParams p) {
 	}
 }
 
-// general gaps, scoring pass: does the matrix fit the LDS behind the strip (leaving room for at least two workgroups per CU)?
-extern "C" int32_t vk_longq_hm_in_lds(int32_t len_t, int32_t max_len) {
-	const size_t hm = (size_t)(len_t + 1) * longq_stride(max_len) * 4;
-	return vk_longq_lds_bytes(len_t, max_len, 0) + hm <= 78 * 1024 ? 1 : 0;
-}
+extern "C" int32_t vk_longq_hm_in_lds(int32_t len_t, int32_t max_len) { return vk_host::longq_hm_in_lds(len_t, max_len) ? 1 : 0; }
 
 template <bool FLOW>
 static hipError_t launch_longq(const VkLongqParams *p, int grid, size_t smem, hipStream_t stream) {
@@ -391,20 +344,14 @@ static hipError_t launch_longq(const VkLongqParams *p, int grid, size_t smem, hi
 
 // workgroups (one wave each) of the scoring pass: as many as the CUs hold with this much LDS each, at most one per slice
 extern "C" int32_t vk_longq_blocks(int32_t len_t, int32_t max_len, int64_t n_sent, int32_t hm_in_lds) {
-	int dev = 0, cus = 256;
-	if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-	const size_t smem = vk_longq_lds_bytes(len_t, max_len, 0) + (hm_in_lds ? (size_t)(len_t + 1) * longq_stride(max_len) * 4 : 0);
-	int per_cu = (int)((160 * 1024) / ((smem + 511) / 512 * 512 + 512));
-	if (per_cu < 1) per_cu = 1;
-	if (per_cu > 16) per_cu = 16;
-	const int64_t want = (int64_t)cus * per_cu;
-	return (int32_t)(n_sent < want ? (n_sent < 1 ? 1 : n_sent) : want);
+	const size_t smem = vk_longq_lds_bytes(len_t, max_len, 0) + (hm_in_lds ? (size_t)(len_t + 1) * vk_host::longq_stride(max_len) * 4 : 0);
+	return (int32_t)vk_host::longq_grid(longq_device_cus(), smem, n_sent);
 }
 
 // flow_k == 0: scores of all p->n_sent slices (grid: vk_longq_blocks; scratch regions: one per workgroup when gap_mode == 2);
 // flow_k > 0: the flow_k winners of p->keys (one workgroup each, scratch regions likewise)
 extern "C" hipError_t vk_launch_longq(const VkLongqParams *p, int32_t flow_k, hipStream_t stream) {
-	const int max_len = p->s_stride;   // (the host sets the strip's stride from the corpus's longest slice: vk_longq_stride)
+	const int max_len = p->s_stride;   // (the host sets the strip's stride from the longest slice of at most 64 tokens: vk_longq_stride)
 	if (flow_k > 0) return launch_longq<true>(p, flow_k, vk_longq_lds_bytes(p->len_t, max_len, 1), stream);
 	const int hl = (p->gap_mode == 2 && p->scratch == nullptr) ? 1 : 0;
 	return launch_longq<false>(p, vk_longq_blocks(p->len_t, max_len, p->n_sent, hl), vk_longq_lds_bytes(p->len_t, max_len, 0), stream);

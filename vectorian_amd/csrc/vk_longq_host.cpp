@@ -1,10 +1,13 @@
 // vk_longq_host.cpp -- C-ABI: alignments of queries of 65 .. VK_MAX_LONG_QUERY_LEN tokens (vk_longq_kernel: roles swapped, one wave
 // per slice, anti-diagonal sweep).  Called by vk_query's body for such queries; the same stages as there -- scoring pass over all
 // slices (MFMA similarities), selection of k + 8, canonical retrace of those, the k best returned -- with buffers of their own.
+// A corpus that holds slices of 65 .. VK_MAX_SENT_LEN tokens: the scoring pass leaves them at -inf and a second launch, the kernel's
+// block form over the list of those rows, overwrites that; the winners all go through the block form.
 // No CPU compute fallback exists.
 
 #include "vk_internal.h"
 #include "vk_guard.h"
+#include "vk_longq_host.h"
 
 int vk_longq_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_host_keep &keep) {
 	int rc = VK_OK;
@@ -30,8 +33,13 @@ int vk_longq_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_
 	const vk_host::gap_form g = vk_host::classify_gaps(q->gap_s, q->gap_t);
 	p.gap_mode = g.gap_mode;
 	gap_fields(p, g);
-	// one host block for the small per-query arrays: w_s[0 .. 64 + pad], w_t[0 .. LT], tag weights, POS codes, token ids
-	const size_t n_ws = 80, n_wt = (size_t)LT + 16;
+	// slices of more than 64 tokens (at most VK_MAX_SENT_LEN: vk_validate_query): the block form takes them, `short_len` is the longest
+	// slice of the pass over the others
+	const bool blocks = c->max_len > VK_FAST_SENT_LEN;
+	const int short_len = blocks ? c->max_short_len : c->max_len;
+	// one host block for the small per-query arrays: w_s[0 .. longest slice + pad] (at least [0 .. 64 + pad]), w_t[0 .. LT], tag
+	// weights, POS codes, token ids
+	const size_t n_ws = blocks ? ((size_t)c->max_len + 63) / 64 * 64 + 16 : 80, n_wt = (size_t)LT + 16;
 	std::vector<float> &fl = keep.vec<float>(n_ws + n_wt + (size_t)LTP);
 	std::vector<int32_t> &il = keep.vec<int32_t>(2 * (size_t)LTP);
 	for (size_t i = 0; i < n_ws; i++) fl[i] = (int)i <= c->max_len ? gap_cost(q->gap_s, (int)i) : 0.0f;
@@ -62,7 +70,7 @@ int vk_longq_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_
 
 	corpus_fields_ids(p, c);
 	p.table = lq.table; p.table_stride = table_stride; p.n_sent = (int32_t)n;
-	p.qtile = lq.qt; p.nq = nq; p.len_t = LT; p.locality = q->locality; p.s_stride = vk_longq_stride(c->max_len);
+	p.qtile = lq.qt; p.nq = nq; p.len_t = LT; p.locality = q->locality; p.s_stride = vk_longq_stride(short_len);
 	p.ws = lq.fl; p.wt = lq.fl + n_ws;
 	if (q->tag_weights) {
 		p.pos_s = c->d_pos; p.tw = lq.fl + n_ws + n_wt; p.tpos = lq.il;
@@ -83,13 +91,35 @@ int vk_longq_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_
 			int kt_ = LT;
 			while (kt_ > 1 && fl[n_ws + (size_t)kt_ - 1] == fl[n_ws + (size_t)LT]) kt_--;
 			if (kt_ < LT) p.wt_tail = kt_;
-			if (!vk_longq_hm_in_lds(LT, c->max_len)) {   // the matrix of the scans: in LDS behind the strip where it fits, else a region per workgroup
+			if (!vk_longq_hm_in_lds(LT, short_len)) {   // the matrix of the scans: in LDS behind the strip where it fits, else a region per workgroup
 				const size_t per = vk_longq_scratch_bytes(LT, 2, 0, 0);
-				if ((rc = lq.scratch.reserve(per * (size_t)vk_longq_blocks(LT, c->max_len, n, 0), &c->device_bytes))) return rc;
+				if ((rc = lq.scratch.reserve(per * (size_t)vk_longq_blocks(LT, short_len, n, 0), &c->device_bytes))) return rc;
 				p.scratch = lq.scratch; p.scratch_stride = (int64_t)per;
 			}
 		}
 		VK_HIP(vk_launch_longq(&p, 0, st));
+		if (blocks) {
+			// ... then the rows it left at -inf, longest first (the list follows the slice table: built when first needed)
+			if (lq.n_order < 0) {
+				std::vector<int32_t> ord;
+				for (int32_t e : *c->h_apart) if ((*c->h_end)[(size_t)e] - (*c->h_start)[(size_t)e] > VK_FAST_SENT_LEN) ord.push_back(e);
+				std::stable_sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) {
+					return (*c->h_end)[(size_t)a] - (*c->h_start)[(size_t)a] > (*c->h_end)[(size_t)b] - (*c->h_start)[(size_t)b]; });
+				if ((rc = lq.order.reserve(ord.size() + 1, &c->device_bytes))) return rc;
+				VK_HIP(hipMemcpyAsync(lq.order, ord.data(), ord.size() * 4, hipMemcpyHostToDevice, st));
+				VK_HIP(hipStreamSynchronize(st));
+				lq.n_order = (int32_t)ord.size();
+			}
+			VkLongqParams b = p;
+			const vk_host::longq_geometry geo = vk_host::longq_geometry_of(LT, c->max_len, p.gap_mode, false, false);
+			b.s_stride = geo.s_stride; b.order = lq.order; b.n_order = lq.n_order; b.dm_off = (int64_t)geo.dm_off; b.su_off = (int64_t)geo.su_off;
+			b.scratch = nullptr; b.scratch_stride = 0;
+			if (p.gap_mode == 2) {
+				if ((rc = lq.bscratch.reserve(geo.scratch_bytes * (size_t)vk_longq_blocks_grid(LT, c->max_len, 2, 0, lq.n_order), &c->device_bytes))) return rc;
+				b.scratch = lq.bscratch; b.scratch_stride = (int64_t)geo.scratch_bytes;
+			}
+			VK_HIP(vk_launch_longq_blocks(&b, c->max_len, 0, st));
+		}
 	}
 	VK_HIP(hipEventRecord(c->ev[2], st));
 	c->ev2_recorded = true;
@@ -102,15 +132,17 @@ int vk_longq_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_
 	const uint64_t *d_sel = c->d_keys[0];   // the selected keys on the device, best first
 	if (only) {
 		std::vector<uint64_t> &hk = keep.vec<uint64_t>((size_t)q->n_only);
-		for (int i = 0; i < q->n_only; i++) hk[(size_t)i] = vk_host::key_of_row(q->only_slices[i]);   // (no long slices: rows == slices, no sent_entry)
+		for (int i = 0; i < q->n_only; i++) hk[(size_t)i] = vk_host::key_of_row(row_of_sentence(c, q->only_slices[i]));   // (long slices sit in padded groups: rows != slices)
 		VK_HIP(hipMemcpyAsync(c->d_keys[0], hk.data(), hk.size() * 8, hipMemcpyHostToDevice, st));
 	} else if ((rc = kk <= 64 ? select_waves(c, sel_floor, kk, st, &d_sel) : select_blocks(c, sel_floor, kk, st, &d_sel))) return rc;
 	VK_HIP(hipEventRecord(c->ev[3], st));
 
 	// ---- the winners' tracebacks
 	if (do_flow) {
-		const size_t per = vk_longq_scratch_bytes(LT, p.gap_mode, 1, q->tag_weights != nullptr);
-		if ((rc = lq.fscratch.reserve(per * (size_t)kk, &c->device_bytes))) return rc;
+		// a scratch region per workgroup: one per winner, the block form at most vk_host::kLongqFlowGrid of them (MBs each)
+		const vk_host::longq_geometry geo = vk_host::longq_geometry_of(LT, blocks ? c->max_len : VK_FAST_SENT_LEN, p.gap_mode, true, q->tag_weights != nullptr);
+		const size_t per = geo.scratch_bytes;
+		if ((rc = lq.fscratch.reserve(per * (size_t)(blocks ? vk_longq_blocks_grid(LT, c->max_len, p.gap_mode, kk, kk) : kk), &c->device_bytes))) return rc;
 		if ((rc = lq.raw.reserve((size_t)kk, &c->device_bytes))) return rc;
 		if ((rc = lq.map.reserve((size_t)kk * LTP, &c->device_bytes))) return rc;
 		if ((rc = lq.sim.reserve((size_t)kk * LTP, &c->device_bytes))) return rc;
@@ -118,7 +150,10 @@ int vk_longq_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_
 		f.wt_tail = 0;   // (the tracebacks meet every candidate, in the oracle's order)
 		f.keys = d_sel; f.n_keys = kk; f.raw_out = lq.raw; f.mapping = lq.map; f.edge_sim = lq.sim; f.out_stride = LTP;
 		f.scratch = lq.fscratch; f.scratch_stride = (int64_t)per;
-		VK_HIP(vk_launch_longq(&f, kk, st));
+		if (blocks) {
+			f.s_stride = geo.s_stride; f.dm_off = (int64_t)geo.dm_off; f.su_off = (int64_t)geo.su_off;
+			VK_HIP(vk_launch_longq_blocks(&f, c->max_len, kk, st));
+		} else VK_HIP(vk_launch_longq(&f, kk, st));
 	}
 	VK_HIP(hipEventRecord(c->ev[4], st));
 

@@ -44,9 +44,10 @@ int vk_validate_query(const vk_corpus *c, const vk_query_desc *q, const vk_topk_
 	if (q->len_t < 1) return fail(VK_ERR_INVALID, "empty query");
 	if (q->len_t > VK_MAX_LONG_QUERY_LEN) return fail(VK_ERR_UNSUPPORTED, "query longer than VK_MAX_LONG_QUERY_LEN (512) tokens");
 	if (q->len_t > VK_MAX_QUERY_LEN) {
-		// 65 .. 512 tokens: the role-swapped one-wave-per-slice kernel (vk_longq_kernel) -- alignments over slices of at most 64 tokens
+		// 65 .. 512 tokens: the role-swapped one-wave-per-slice kernel (vk_longq_kernel) -- alignments over slices of at most
+		// VK_MAX_SENT_LEN tokens (those of more than 64: its block form)
 		if (q->algorithm != VK_ALG_ALIGN) return fail(VK_ERR_UNSUPPORTED, "queries of more than VK_MAX_QUERY_LEN (64) tokens: alignments only (the transports keep a lane per query token)");
-		if (c->max_len > VK_FAST_SENT_LEN) return fail(VK_ERR_UNSUPPORTED, "queries of more than 64 tokens over a corpus that holds a slice of more than 64 tokens: a lane per slice token");
+		if (c->max_len > VK_MAX_SENT_LEN) return fail(VK_ERR_UNSUPPORTED, "queries of more than 64 tokens over a corpus that holds a slice of more than VK_MAX_SENT_LEN (512) tokens: the state of such a slice does not fit a workgroup's LDS");
 		if (q->submatch_weight != 0.0f) return fail(VK_ERR_UNSUPPORTED, "queries of more than 64 tokens with a submatch weight");
 		if (out->sim_rows) return fail(VK_ERR_UNSUPPORTED, "queries of more than 64 tokens: similarity rows of the winners are not returned");
 		if (q->max_matches > VK_MAX_MATCHES) return fail(VK_ERR_UNSUPPORTED, "queries of more than 64 tokens: max_matches <= VK_MAX_MATCHES");
