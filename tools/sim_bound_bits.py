@@ -11,7 +11,12 @@ first chunk; odd-numbered: ten random words), with its seed; the benchmark's own
 of the same kind, not the same vectors.  N and X, the corpus-wide constants of the bound, are the first chunk's maxima widened by
 5e-3; the output says whether every later chunk stayed below them (`constants_hold`).
 
-  python tools/sim_bound_bits.py --slices 1000000 --chunk 25000 --queries 16 --threads 16 --out profiles/bound_fp6_sim.json"""
+--tail K[,K...]: the E2M3 bounds once more per K under the slice-gap table made flat beyond K entries (w'(k) = w(k) for
+k <= K, the minimum of w(K + 1 .. 32) beyond), which is what the flat-tailed bound kernels compute; per K the size of round 2 and
+the largest (tail bound - full-table bound).
+
+  python tools/sim_bound_bits.py --slices 1000000 --chunk 25000 --queries 16 --threads 16 --out profiles/bound_fp6_sim.json
+  python tools/sim_bound_bits.py --slices 200000 --chunk 25000 --queries 16 --threads 16 --tail 3,4,6 --out profiles/bound_tail_sim.json"""
 import argparse
 import json
 import os
@@ -85,6 +90,21 @@ def make_queries(corpus, n_queries, seed):
 	return qs
 
 
+def flat_tailed(gap, k):
+	"""the table flat beyond k entries: its tail costs the least of the entries k + 1 .. LEN_S (vk_host::bound_tail_cost)"""
+	w = gap[1].copy()
+	w[k + 1:] = w[k + 1:LEN_S + 1].min()
+	return ("table", w)
+
+
+def rounds(ub, ex, floor):
+	"""(theta, size of round 2) as vk_query.cpp takes its rounds"""
+	first = np.argsort(-ub, kind="stable")[:M]
+	best = np.sort(ex[first][ex[first] > floor])[::-1]
+	theta = float(best[KK - 1]) if len(best) >= KK else floor
+	return theta, int((ub >= theta).sum() if len(best) >= KK else (ub > theta).sum())
+
+
 def main():
 	ap = argparse.ArgumentParser()
 	ap.add_argument("--slices", type=int, default=50_000)
@@ -92,13 +112,17 @@ def main():
 	ap.add_argument("--queries", type=int, default=8)
 	ap.add_argument("--threads", type=int, default=16)
 	ap.add_argument("--seed", type=int, default=3456, help="seed of the queries (bench.py draws its queries with 3456)")
+	ap.add_argument("--tail", default="", help="K[,K...]: the E2M3 bounds again under the table flat beyond K entries")
 	ap.add_argument("--out", default=None)
 	a = ap.parse_args()
+	tails = [int(x) for x in a.tail.split(",") if x]
+	assert all(1 <= k < LEN_S for k in tails), tails
 	t0 = time.time()
 	n_chunks = (a.slices + a.chunk - 1) // a.chunk
 	names = list(QUANTIZERS)
 	exact = np.empty((a.queries, a.slices), dtype=F)
 	bound = {q: np.empty((a.queries, a.slices), dtype=F) for q in names}
+	bound_tail = {k: np.empty((a.queries, a.slices), dtype=F) for k in tails}
 	qs, qb, qq, const, holds = None, None, {}, {}, True
 	for c in range(n_chunks):
 		n = min(a.chunk, a.slices - c * a.chunk)
@@ -130,6 +154,9 @@ def main():
 				S.append(np.clip(ub, F(0), F(1)))
 			for i, r in enumerate(vo.find_many(S_rows=S, **kw)):
 				bound[name][i, lo:lo + n] = r["all_scores"]
+			for k in tails if name == "e2m3" else ():
+				for i, r in enumerate(vo.find_many(S_rows=S, **dict(kw, gap_s=flat_tailed(EXP5, k)))):
+					bound_tail[k][i, lo:lo + n] = r["all_scores"]
 		print(f"chunk {c + 1}/{n_chunks}: {time.time() - t0:.0f} s", file=sys.stderr, flush=True)
 	floor = -1e-5
 	out = {"slices": a.slices, "tokens_per_slice": LEN_S, "d": D, "len_t": LEN_T, "k": K, "kk": KK, "round1": M, "gap": "exp5", "locality": "local",
@@ -139,17 +166,30 @@ def main():
 		for i in range(a.queries):
 			ub, ex = bound[name][i], exact[i]
 			assert (ub >= ex).all(), (name, i, float((ub - ex).min()))
-			first = np.argsort(-ub, kind="stable")[:M]
-			best = np.sort(ex[first][ex[first] > floor])[::-1]
-			theta = float(best[KK - 1]) if len(best) >= KK else floor
+			theta, round2 = rounds(ub, ex, floor)
 			rows.append({"query": i, "planted": i % 2 == 0, "slack_max": round(float((ub - ex).max()), 5), "slack_mean": round(float((ub - ex).mean()), 5),
-				"theta": round(theta, 5), "round2": int((ub >= theta).sum() if len(best) >= KK else (ub > theta).sum())})
+				"theta": round(theta, 5), "round2": round2})
 		r2p = [r["round2"] for r in rows if r["planted"]]
 		r2r = [r["round2"] for r in rows if not r["planted"]]
 		out["quantizers"][name] = {"slack_max": max(r["slack_max"] for r in rows), "slack_mean": [min(r["slack_mean"] for r in rows), max(r["slack_mean"] for r in rows)],
 			"round2_planted": [min(r2p), max(r2p)], "round2_random": [min(r2r), max(r2r)] if r2r else None,
 			"round2_mean": round(float(np.mean(r2p + r2r)), 1), "round2_max": max(r2p + r2r), "fallback_line": max(a.slices // 16, 1024), "queries": rows}
 		print(name, {k: v for k, v in out["quantizers"][name].items() if k != "queries"})
+	if tails:
+		out["tail"] = {"quantizer": "e2m3", "full_table_round2_mean": out["quantizers"]["e2m3"]["round2_mean"], "by_k": {}}
+	for k in tails:
+		rows = []
+		for i in range(a.queries):
+			ub, ex, ub_full = bound_tail[k][i], exact[i], bound["e2m3"][i]
+			assert (ub >= ub_full).all(), (k, i, float((ub - ub_full).min()))   # a flat tail only raises a bound
+			theta, round2 = rounds(ub, ex, floor)
+			rows.append({"query": i, "planted": i % 2 == 0, "over_full_table_max": round(float((ub - ub_full).max()), 5), "theta": round(theta, 5), "round2": round2})
+		r2p = [r["round2"] for r in rows if r["planted"]]
+		r2r = [r["round2"] for r in rows if not r["planted"]]
+		out["tail"]["by_k"][str(k)] = {"over_full_table_max": max(r["over_full_table_max"] for r in rows), "round2_planted": [min(r2p), max(r2p)],
+			"round2_random": [min(r2r), max(r2r)] if r2r else None, "round2_mean": round(float(np.mean(r2p + r2r)), 1), "round2_max": max(r2p + r2r),
+			"fallback_line": max(a.slices // 16, 1024), "queries": rows}
+		print("tail", k, {key: v for key, v in out["tail"]["by_k"][str(k)].items() if key != "queries"})
 	out["seconds"] = round(time.time() - t0)
 	if a.out:
 		with open(a.out, "w") as f:

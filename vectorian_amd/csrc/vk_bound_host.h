@@ -223,6 +223,24 @@ struct bound_backoff {
 	}
 };
 
+// ---- the flat tail of the slice-gap table: under general gaps the bound kernel may score under
+//     w'(k) = w(k) for k <= K,   w'(k) = c_tail = min over K < j <= rows of w(j) for k > K         (rows: 32 or 64, the form's history)
+// which is <= w entry by entry, so its scores bound those under w from above.  w[0 .. rows]; a minimum, not w[K + 1]: the table need
+// not rise.  K >= rows: no entry is in the tail, +inf (the identity of the minimum; no row of the kernel reads it).
+inline float bound_tail_cost(const float *w, int k, int rows) {
+	float c = INFINITY;
+	for (int j = k + 1; j <= rows; j++) c = w[j] < c ? w[j] : c;
+	return c;
+}
+// VK_BOUND_TAIL as the environment holds it (null: unset) and VK_BOUND_PASS as bound_pass_mode reads it (-1 off, 0 by size, 1 force):
+// "0" never, "1" use the tail, anything else the default -- on where the pass is switched on by size, off under force (the tests of
+// the bound pass pin its bounds and the size of round 2 under force, as they pinned the 8-bit shadow: bound_bits_wanted)
+inline bool bound_tail_choice(const char *env, int mode) {
+	if (env && !strcmp(env, "0")) return false;
+	if (env && !strcmp(env, "1")) return true;
+	return mode == 0;
+}
+
 } // namespace vk_host
 
 #endif

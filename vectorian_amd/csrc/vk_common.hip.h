@@ -327,6 +327,12 @@ __device__ __forceinline__ f32x4 cell_tile_fp6(const f32x4 acc, const f32x2 m, c
 #ifndef VK_FP6_TILES
 #define VK_FP6_TILES 2
 #endif
+#ifndef VK_FP6_TILES_TAIL
+#define VK_FP6_TILES_TAIL 2     // ... of the flat-tailed 32-row form (GAP 8 of vk_score_kernel)
+#endif
+#ifndef VK_FP6_TILES_TAIL64
+#define VK_FP6_TILES_TAIL64 1   // ... of the flat-tailed 64-row form (GAP 9)
+#endif
 template <int T>
 __device__ __forceinline__ void sim_tiles_fp6(f32x4 (&ub)[T], const uint8_t *__restrict__ qlds, const uint8_t *__restrict__ tile, int tile_bytes, int lane, int live6) {
 	i32x4 lo[T][VK_DEV_FP6_STEPS];
@@ -964,6 +970,90 @@ __device__ __forceinline__ float dp_general_reg(const float *__restrict__ S, int
 			float c = fmaxf(diag + s, floor0);
 #pragma unroll
 			for (int k = 1; k <= u; k++) c = fmaxf(c, hreg[u - k] - wsr[k]);
+			float hc = fmaxf(c, bcur - wt_border);
+			if (LT > 1) hc = fmaxf(hc, dpp_zero<0x111>(c) - wtv[1]);
+			if (LT > 2) hc = fmaxf(hc, dpp_zero<0x112>(c) - wtv[2]);
+			if (LT > 3) hc = fmaxf(hc, dpp_zero<0x113>(c) - wtv[3]);
+			if (LT > 4) hc = fmaxf(hc, dpp_zero<0x114>(c) - wtv[4]);
+			if (LT > 5) hc = fmaxf(hc, dpp_zero<0x115>(c) - wtv[5]);
+			if (LT > 6) hc = fmaxf(hc, dpp_zero<0x116>(c) - wtv[6]);
+			if (LT > 7) hc = fmaxf(hc, dpp_zero<0x117>(c) - wtv[7]);
+			if (LT > 8) hc = fmaxf(hc, dpp_zero<0x118>(c) - wtv[8]);
+			if (LT > 9) hc = fmaxf(hc, dpp_zero<0x119>(c) - wtv[9]);
+			if (LT > 10) hc = fmaxf(hc, dpp_zero<0x11a>(c) - wtv[10]);
+			if (LT > 11) hc = fmaxf(hc, dpp_zero<0x11b>(c) - wtv[11]);
+			if (LT > 12) hc = fmaxf(hc, dpp_zero<0x11c>(c) - wtv[12]);
+			if (LT > 13) hc = fmaxf(hc, dpp_zero<0x11d>(c) - wtv[13]);
+			if (LT > 14) hc = fmaxf(hc, dpp_zero<0x11e>(c) - wtv[14]);
+			if (LT > 15) hc = fmaxf(hc, dpp_zero<0x11f>(c) - wtv[15]);
+			hreg[u] = hc;
+			h = act ? hc : h;
+			if (is_local || last_col) best = fmaxf(best, h);
+		}
+	}
+	float m;
+	if (is_local) m = v < a.len_t ? best : 0.0f;
+	else if (is_global) m = last_col ? h : VK_NEG_INF;
+	else m = v < a.len_t ? fmaxf(h, last_col ? best : 0.0f) : 0.0f;
+	m = row_max_to_lane15(m);
+	return (is_global) ? m : fmaxf(m, 0.0f);
+}
+
+// General gap costs, register history, under a slice-gap table that is flat beyond KT entries: the bound pass only.
+//     w'(k) = w_s(k) for k <= KT,   w'(k) = c_tail = min over KT < j <= MAXLEN of w_s(j) for k > KT      (the host: vk_bound_host.h)
+// wsr[0 .. KT] = w_s[0 .. KT], wsr[KT + 1] = c_tail.  Under w' the candidates k > KT of a row share one cost, and
+//     max_j fl(h_j - c) = fl(max_j h_j - c)       (fl(x - c) is non-decreasing in x, max is exact),
+// so they are ONE candidate, R - c_tail, with R = max(hreg[0 .. u-KT-1]) kept as a running maximum -- one v_max per row in place of
+// u - KT subtractions and as many maxima.  R starts from hreg[0]: under global locality the border row is in it, as it is among
+// dp_general_reg's candidates k = u.  Everything else -- border, in-row candidates, floor, best, the final reduction, the asm
+// treatment of loc / vsel -- is dp_general_reg's, and the function is bit-identical to dp_general_reg fed the table w'
+// (tests/test_gpu_bound_tail.py rests on that).
+// Why it is an upper bound of dp_general_reg under w_s itself, float for float: w' <= w_s entry by entry; fl(x - c) is non-decreasing
+// in x and non-increasing in c; fl(x + s) is non-decreasing in x; max is exact and monotone.  By induction over the cells in the
+// order they are computed, every hreg[u] here is >= the same cell there, hence every h, best and the result.  The history needs
+// KT + 1 live rows and R instead of MAXLEN + 1, the table KT + 2 scalars instead of MAXLEN + 1.
+template <int LT, int MAXLEN, int KT, bool FRESH = true>
+__device__ __forceinline__ float dp_general_tail_reg(const float *__restrict__ S, int rowbase, int len, int maxlen, int v,
+	const DpArgs &a, const float (&wsr)[KT + 2], const float (&wtr)[LT]) {
+	static_assert(KT >= 1 && KT < MAXLEN, "the tail begins inside the table");
+	int loc = a.locality, vsel = v;
+	if constexpr (FRESH) {
+		asm volatile("" : "+v"(loc));
+		asm volatile("" : "+v"(vsel));
+		loc = __builtin_amdgcn_readfirstlane(loc);
+	}
+	const bool is_local = loc == VK_DEV_LOCAL;
+	const bool is_global = loc == VK_DEV_GLOBAL;
+	const float floor0 = is_local ? 0.0f : VK_NEG_INF;
+	const bool last_col = v == a.len_t - 1;
+	const float wt_border = a.wt[v + 1];
+	const float wt_border0 = a.wt0[v + 1];
+	const float c_tail = wsr[KT + 1];
+
+	float wtv[16];
+#pragma unroll
+	for (int k = 1; k < LT; k++) wtv[k] = vsel >= k ? wtr[k] : __builtin_inff();
+
+	float hreg[MAXLEN + 1];   // (fully unrolled: a row is dead once R has taken it, KT + 1 rows after it was made)
+	float h = is_global ? -wt_border0 : 0.0f;
+	hreg[0] = h;
+	float R = h;
+	float best = 0.0f;
+#pragma unroll
+	for (int u = 1; u <= MAXLEN; u++) {
+		if (u <= maxlen) {
+			const bool act = u <= len;
+			const float s = S[(rowbase + (act ? u - 1 : 0)) * LT + v];
+			const float bprev = is_global ? -wsr[u - 1 <= KT ? u - 1 : KT + 1] : 0.0f;
+			const float bcur = is_global ? -wsr[u <= KT ? u : KT + 1] : 0.0f;
+			const float diag = dpp_f<DPP_ROW_SHR1>(bprev, hreg[u - 1]);
+			float c = fmaxf(diag + s, floor0);
+#pragma unroll
+			for (int k = 1; k <= (u < KT ? u : KT); k++) c = fmaxf(c, hreg[u - k] - wsr[k]);
+			if (u > KT) {
+				if (u > KT + 1) R = fmaxf(R, hreg[u - KT - 1]);
+				c = fmaxf(c, R - c_tail);
+			}
 			float hc = fmaxf(c, bcur - wt_border);
 			if (LT > 1) hc = fmaxf(hc, dpp_zero<0x111>(c) - wtv[1]);
 			if (LT > 2) hc = fmaxf(hc, dpp_zero<0x112>(c) - wtv[2]);

@@ -622,6 +622,14 @@ int vk_bound_pass_bits(vk_corpus_t *c, int64_t *bits) {
 	return VK_OK;
 }
 
+// Internal (tests; not part of the ABI): K where the last query's bound pass ran a flat-tailed form (general gaps under a slice-gap
+// table flat beyond K entries), else 0
+int vk_bound_pass_tail(vk_corpus_t *c, int32_t *k) {
+	if (!c || !k) return fail(VK_ERR_INVALID, "null argument");
+	*k = c->bp.ran ? (int32_t)c->bp.tail_k : 0;
+	return VK_OK;
+}
+
 // Internal (tests; not part of the ABI): the handle's shadow as the device holds it.  format[5]: bits (0: no shadow, the rest zero
 // then), K-steps per tile, live quarters of the last K-step, bytes per tile, tiles (the zero tile behind the corpus included);
 // nx[2]: the corpus-wide constants N and X.  out (null: none wanted): the bytes of tiles tile0 .. tile0 + n - 1.

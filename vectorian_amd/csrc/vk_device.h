@@ -28,6 +28,13 @@
 // bytes of a corpus tile with live6 quarters in its last K-step: the K-steps, then 16 x (s_x, e_x)
 #define VK_DEV_FP6_TILE_BYTES(live6) ((VK_DEV_FP6_STEPS - 1) * VK_DEV_FP6_STEP_BYTES + 384 * (live6) + 128)
 
+// The bound pass under general gaps may score under a slice-gap table that is flat beyond this many entries (GAP 8 / 9 of
+// vk_score_kernel).  A unit that instantiates those forms reports the K it was compiled with (vk_score_m8t_tail_k,
+// vk_score_m7t_tail_k): the host computes the tail's cost for that K.
+#ifndef VK_BOUND_TAIL_K
+#define VK_BOUND_TAIL_K 4
+#endif
+
 struct VkScoreParams {
 	// corpus
 	const uint8_t *tiles;      // contextual: token tiles
@@ -54,7 +61,7 @@ struct VkScoreParams {
 	const uint8_t *qtile;      // query in tile order (16 rows, rows >= len_t are zero)
 	int32_t len_t;
 	int32_t locality;
-	int32_t gap_mode;          // 0 linear, 1 affine, 2 general, 3 general (register history), 4 RWMD
+	int32_t gap_mode;          // 0 linear, 1 affine, 2 general, 3 general (register history), 4 RWMD; 8 / 9: 3 / 6 with a flat tail (bound pass)
 	int32_t rwmd_symmetric, rwmd_normalize_bow;
 	int32_t wmd_bound;         // 0: RWMD score; 1: upper bound of the full WMD score, nbow; 2: same, bow
 	float gs, gt;              // linear: w(k) = g*k; affine: b (extension)
@@ -88,6 +95,7 @@ struct VkScoreParams {
 	int32_t s_rows_per_wave;   // rows of the similarity staging area
 	int32_t h_rows;            // general gap: history rows per sentence (max_len + 1)
 	int32_t m_rows;            // GAP 7, static layout: floats per sentence of the mass scratch (after the S strip)
+	float bound_tail_cost;     // gap_mode 8 / 9: the cost of every gap over more than K slice tokens (vk_host::bound_tail_cost)
 };
 
 struct VkRwmdBatchParams {
@@ -400,6 +408,8 @@ hipError_t vk_launch_filter_gather(const void *src, void *dst, int32_t elem_byte
 hipError_t vk_launch_table(const uint8_t *etiles, const uint8_t *qtile, int32_t n_tiles, int32_t nk32, int32_t tail,
 	int32_t tile_bytes, float *table, const int32_t *q_ids, int32_t len_t, int32_t V, int32_t prec, hipStream_t stream);
 hipError_t vk_launch_score(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
+int32_t vk_score_m8t_tail_k(void);   // K of the flat-tailed bound kernels over the 6-bit shadow (vk_score_m8t.hip) ...
+int32_t vk_score_m7t_tail_k(void);   // ... and over the 8-bit shadow (vk_score_m7t.hip)
 hipError_t vk_launch_span(const VkScoreParams *p, hipStream_t stream);
 hipError_t vk_launch_score_batch(const VkScoreBatchParams *p, int32_t lt, size_t smem, hipStream_t stream);
 hipError_t vk_launch_topk_scores(const float *scores, int64_t n, float min_score, int32_t k, uint64_t *out,

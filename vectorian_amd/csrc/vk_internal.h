@@ -81,6 +81,9 @@ inline int bound_bits_wanted(int mode) {
 	if (e && !strcmp(e, "8")) return 8;
 	return mode > 0 ? 8 : 6;
 }
+// VK_BOUND_TAIL, read per query: whether the bound pass of a query with general gaps scores under the flat-tailed slice-gap table
+// (vk_host::bound_tail_choice, by the same rule: the default is on where the pass is switched on by size)
+inline bool bound_tail_wanted(int mode) { return vk_host::bound_tail_choice(getenv("VK_BOUND_TAIL"), mode); }
 
 } // namespace
 
@@ -213,6 +216,7 @@ struct vk_corpus : vk_corpus_shape {
 		bool pruned = false;          // d_scores holds the contenders' scores only: vk_last_scores runs `full` first
 		VkScoreParams full{}; int full_grid = 0; size_t full_smem = 0;   // the exact pass of the last query (its workspaces stay until the next)
 		int64_t ran = 0, round1 = 0, round2 = 0, fell_back = 0;           // the last query: bound pass ran, candidates of the rounds, full pass after all
+		int64_t tail_k = 0;                                                // ... under a slice-gap table flat beyond this many entries (0: the caller's table)
 		int64_t queries = 0, fallbacks = 0, survivors = 0;                // since the handle was made
 		vk_host::bound_backoff backoff;                                    // default mode: when the handle stops trying (vk_bound_host.h)
 	} bp;

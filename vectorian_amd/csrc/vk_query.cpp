@@ -198,8 +198,10 @@ void vk_pack_query(const vk_corpus *c, const vk_query_desc *q, std::vector<uint8
 // p.raw) hold today's floats for every slice that can be among the kk best above sel_floor, and something below the kk-th best
 // (-inf, or the exact score of a contender's neighbour in its group of four) everywhere else.  Records ev[2] right after the bound
 // kernel: the peer's turn begins there.  smem_list: the dynamic LDS of the exact kernel with one wave per workgroup (group_list).
+// gap_s, tail: general gaps with the flat tail wanted (bound_tail_wanted) -- the bound kernel scores under the caller's slice-gap table made
+// flat beyond the K its unit was compiled with, an upper bound of the bound (vk_host::bound_tail_cost)
 static int score_bounded(vk_corpus *c, const VkScoreParams &p, int grid, size_t smem, size_t smem_bound, size_t smem_list, int kk, float sel_floor,
-	vk_host_keep &keep, hipStream_t st, const uint64_t **d_sel) {
+	const vk_gap &gap_s, bool tail, vk_host_keep &keep, hipStream_t st, const uint64_t **d_sel) {
 	*d_sel = nullptr;
 	const int64_t n = c->n_entries;
 	vk_corpus::bound_state &b = c->bp;
@@ -218,6 +220,15 @@ static int score_bounded(vk_corpus *c, const VkScoreParams &p, int grid, size_t 
 	const vk_host::shadow_format &sf = c->shadow_format;
 	pb.tiles = c->shadow; pb.nk32 = sf.steps; pb.tail = 0; pb.tile_bytes = sf.tile_bytes(); pb.bound_bits = sf.bits; pb.bound_live = sf.live;
 	pb.q_mode3 = 0; pb.q_lds = 0; pb.qtile = c->d_qtile8; pb.scores = c->d_ub; pb.raw = nullptr;
+	b.tail_k = 0;
+	if (tail && (p.gap_mode == 3 || p.gap_mode == 6)) {
+		const int rows = p.gap_mode == 3 ? 32 : 64, K = sf.bits == 6 ? vk_score_m8t_tail_k() : vk_score_m7t_tail_k();
+		float w[65];
+		for (int j = 0; j <= rows; j++) w[j] = gap_cost(gap_s, j);
+		pb.gap_mode = p.gap_mode == 3 ? 8 : 9;
+		pb.bound_tail_cost = vk_host::bound_tail_cost(w, K, rows);
+		b.tail_k = K;
+	}
 	VK_HIP(vk_launch_score(&pb, grid, smem_bound, st));
 	VK_HIP(hipEventRecord(c->ev[2], st));
 	c->ev2_recorded = true;
@@ -275,7 +286,7 @@ static int score_bounded(vk_corpus *c, const VkScoreParams &p, int grid, size_t 
 static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_host_keep &keep) {
 	int rc = VK_OK;
 	VK_HIP(hipSetDevice(c->device));
-	c->bp.pruned = false; c->bp.ran = c->bp.round1 = c->bp.round2 = c->bp.fell_back = 0;
+	c->bp.pruned = false; c->bp.ran = c->bp.round1 = c->bp.round2 = c->bp.fell_back = c->bp.tail_k = 0;
 	for (int64_t &x : c->query_route) x = -1;
 	if (q->len_t > VK_MAX_QUERY_LEN) return vk_longq_query(c, q, out, keep);   // 65 .. 512 tokens (vk_longq_host.cpp)
 	hipStream_t st = c->stream;
@@ -634,7 +645,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		const size_t smem_bound = smem_strips + (size_t)c->shadow_format.qtile_bytes() + VK_DEV_BOUND_CONST_BYTES;
 		// the exact kernel over a group_list: one wave per workgroup, its strip and the exact query tile
 		const size_t smem_list = (size_t)lds_floats * 4 + qlds + (size_t)p.q_lds;
-		if ((rc = score_bounded(c, p, grid, smem, smem_bound, smem_list, kk, sel_floor, keep, st, &d_sel_bounded))) return rc;
+		if ((rc = score_bounded(c, p, grid, smem, smem_bound, smem_list, kk, sel_floor, q->gap_s, bound_tail_wanted(bound_mode), keep, st, &d_sel_bounded))) return rc;
 	} else if (r.plan != vk_host::PLAN_LISTED) VK_HIP(vk_launch_score(&p, grid, smem, st));
 	if (r.pass[vk_host::CLASS_MID] == vk_host::PASS_FUSED_LONG) {
 		// slices longer than VK_FAST_SENT_LEN: one per wave, one wave per workgroup, LDS strip for the longest;

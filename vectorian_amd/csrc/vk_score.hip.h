@@ -23,7 +23,10 @@
 //      4 relaxed word mover's distance (no DP: row / column minima of 1 - S),
 //      5 word rotator's distance, upper bound of the score (stage 1),
 //      6 as 3 for sentences <= 64 tokens,
-//      7 relaxed word mover's distance, 1:n form (greedy fill by ascending distance).
+//      7 relaxed word mover's distance, 1:n form (greedy fill by ascending distance),
+//      8 as 3 under a slice-gap table that is flat beyond VK_BOUND_TAIL_K entries (dp_general_tail_reg): an upper bound of 3,
+//        the bound pass only (MODE 7 / 8),
+//      9 as 6, likewise.
 // LT: padded query length (4, 8, 12, 16).
 // ---------------------------------------------------------------------------
 
@@ -100,11 +103,15 @@ __global__ __launch_bounds__(256) VK_SCORE_KERNEL_ATTR void vk_score_kernel(VkSc
 	}
 
 	// general gap, fast form: gap tables in (scalar) registers for the whole kernel
-	constexpr int WSN = GAP == 6 ? 65 : 33;
+	// (the flat-tailed forms: w_s[0 .. K] and the tail's cost, which comes by value)
+	constexpr bool FLAT = GAP == 8 || GAP == 9;
+	static_assert(!FLAT || MODE == 7 || MODE == 8, "a flat-tailed table gives a bound, not a score");
+	constexpr int WSN = FLAT ? VK_BOUND_TAIL_K + 2 : GAP == 6 ? 65 : 33;
 	float wsr[WSN], wtr[LT];
-	if (GAP == 3 || GAP == 6) {
+	if (GAP == 3 || GAP == 6 || FLAT) {
 #pragma unroll
-		for (int k = 0; k < WSN; k++) wsr[k] = p.ws[k];
+		for (int k = 0; k < (FLAT ? WSN - 1 : WSN); k++) wsr[k] = p.ws[k];
+		if (FLAT) wsr[WSN - 1] = p.bound_tail_cost;
 #pragma unroll
 		for (int k = 0; k < LT; k++) wtr[k] = p.wt[k];
 	}
@@ -193,7 +200,8 @@ __global__ __launch_bounds__(256) VK_SCORE_KERNEL_ATTR void vk_score_kernel(VkSc
 				// wave-uniform: a tile past the group's last is neither loaded nor written to the strip
 				// the 64-row history (GAP 6) keeps one tile per trip: with two its forms allocate 128 registers, past the 120 that the
 				// 32-row forms keep to; no corpus of that shape has been measured either way
-				constexpr int T = GAP == 6 ? 1 : VK_FP6_TILES;
+				// the flat-tailed forms keep K + 1 rows of history: VK_FP6_TILES_TAIL / VK_FP6_TILES_TAIL64 (vk_score_m8t.hip)
+				constexpr int T = GAP == 6 ? 1 : GAP == 8 ? VK_FP6_TILES_TAIL : GAP == 9 ? VK_FP6_TILES_TAIL64 : VK_FP6_TILES;
 				const auto tiles = [&](auto tc, int ti) {
 					constexpr int N = decltype(tc)::value;
 					f32x4 ub[N];
@@ -259,6 +267,8 @@ __global__ __launch_bounds__(256) VK_SCORE_KERNEL_ATTR void vk_score_kernel(VkSc
 		// 65 KB of LDS per workgroup admit two per CU, so 111 registers buy nothing there where 187 fit, and redoing 80 selects per
 		// group cost 1 % of the kernel (4.40 -> 4.44 ms)
 		else if constexpr (GAP == 6) raw = dp_general_reg<LT, 64, MODE != 7>(S, rb, lenc, maxlen, v, a, wsr, wtr);
+		else if constexpr (GAP == 8) raw = dp_general_tail_reg<LT, 32, VK_BOUND_TAIL_K>(S, rb, lenc, maxlen, v, a, wsr, wtr);
+		else if constexpr (GAP == 9) raw = dp_general_tail_reg<LT, 64, VK_BOUND_TAIL_K, MODE != 7>(S, rb, lenc, maxlen, v, a, wsr, wtr);
 		else if constexpr (GAP == 4) {
 			// stage 1 of the full WMD over normalised bags of words = the WRD bound with unit magnitudes
 			if (a.wmd_bound == 1) raw = wrd_bound_rows<LT>(S, rb, lenc, maxlen, v, a, nullptr, nullptr, 1.0f / (float)a.len_t);
@@ -356,6 +366,7 @@ static hipError_t launch_sized(K kernel, const VkScoreParams &p, int want_blocks
 	// ms_per_step 1.59 at 2 per CU, 1.44 at 3, 1.40 at 4 on a machine where the kernel before it (118 VGPRs, one tile per trip)
 	// took 1.47 at 3, 1.53 - 1.56 at 4 and 1.53 at 5 -- at 4 that kernel alone was faster (1.35 ms) and the step slower, the
 	// rounds waiting for the peer's pass; this one keeps ms_per_step within 0.02 ms of kernel_ms at 4
+	// its flat-tailed form (GAP 8, the same 104 VGPRs): ms_per_step 1.275 - 1.287 at 3 per CU, 1.270 - 1.271 at 4
 	// the 12-step shadow (768-d rows, 1 M slices of 8 .. 64 tokens, 64-row history): LDS and registers admit two per CU -- 4.40 ms; one: 5.98 ms
 	const int stream_cap = ((p.bound_bits == 0 && p.nk32 >= 5 && p.nk32 <= 7) || p.bound_bits == 6) ? 4 : 3;
 	if (occ > stream_cap && !dp_bound && !bound_pass) occ = stream_cap;   // the static layout is DP-bound, not a stream: keep full residency

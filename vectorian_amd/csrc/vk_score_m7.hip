@@ -13,6 +13,7 @@
 // 289 .. 304 features (five K-steps of 64 int8) and 753 .. 768 (twelve, two batches of six in flight: dot_tile_i8); alignments over
 // slices of at most 64 tokens only: the gap modes of the main launch
 extern "C" hipError_t vk_launch_score_m7w(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
+extern "C" hipError_t vk_launch_score_m7t(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);   // the flat-tailed forms (vk_score_m7t.hip)
 template <int NK64>
 static hipError_t launch_m7(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream) {
 	switch (p->gap_mode) {
@@ -26,6 +27,7 @@ static hipError_t launch_m7(const VkScoreParams *p, int32_t grid, size_t smem_by
 extern "C" hipError_t vk_launch_score_m7(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream) {
 	if (p->bound_live < 1 || p->bound_live > 4) return hipErrorInvalidValue;
 	if (p->pos_s) return hipErrorInvalidValue;   // no tag weights under a bound (vk_score.hip.h, TAGS)
+	if (p->gap_mode == 8 || p->gap_mode == 9) return vk_launch_score_m7t(p, grid, smem_bytes, stream);
 	if (p->nk32 == 5) return launch_m7<5>(p, grid, smem_bytes, stream);
 	if (p->nk32 == 12) return launch_m7<12>(p, grid, smem_bytes, stream);
 	return hipErrorInvalidValue;

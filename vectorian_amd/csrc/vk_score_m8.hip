@@ -10,6 +10,7 @@
 // 289 .. 304 features (three K-steps of 128 E2M3 codes, the last with bound_live of its four quarters); alignments over slices of at
 // most 64 tokens only: the gap modes of the main launch
 extern "C" hipError_t vk_launch_score_m8w(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
+extern "C" hipError_t vk_launch_score_m8t(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);   // the flat-tailed forms (vk_score_m8t.hip)
 extern "C" hipError_t vk_launch_score_m8(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream) {
 	if (p->bound_live < 1 || p->bound_live > 4 || p->tile_bytes != VK_DEV_FP6_TILE_BYTES(p->bound_live)) return hipErrorInvalidValue;
 	if (p->pos_s) return hipErrorInvalidValue;   // no tag weights under a bound (vk_score.hip.h, TAGS)
@@ -18,6 +19,7 @@ extern "C" hipError_t vk_launch_score_m8(const VkScoreParams *p, int32_t grid, s
 	case 1: return launch_score_lt<8, VK_DEV_FP6_STEPS, false, 1>(*p, grid, smem_bytes, stream);
 	case 3: return launch_score_lt<8, VK_DEV_FP6_STEPS, false, 3>(*p, grid, smem_bytes, stream);
 	case 6: return vk_launch_score_m8w(p, grid, smem_bytes, stream);
+	case 8: case 9: return vk_launch_score_m8t(p, grid, smem_bytes, stream);
 	default: return hipErrorInvalidValue;
 	}
 }
