@@ -254,6 +254,20 @@ int vk_corpus_view(vk_corpus_t *src, vk_corpus_t **out);
  * passed, as upstream's do (flow.cpp:49-60 maps them back).  The static layout shares the vocabulary vectors with
  * `src` (reference-counted: either may be freed first). */
 int vk_corpus_filter(vk_corpus_t *src, uint64_t pos_mask, uint64_t tag_mask, vk_corpus_t **out);
+/* The operator chain of a ModifiedVectorSim over the cosine (vectorian/sim/vector.py:179-200; the operators:
+ * vectorian/sim/kernel.py:14-76): n_ops operators, applied in order to the UNCLIPPED cosine of every cell, in fp32 with one rounding
+ * per numpy operation of the reference -- before sim[id(t_j)][j] = 1 (metric/static.cpp:58-67) and before the clip (:75), where the
+ * reference's callback runs (:46-50).  kinds[i] with args[i]:
+ *   BIAS b: x + b;  SCALE s: x * s;  THRESHOLD t: y = max(0, x - t), then y > 0 ? y + t : 0;  ONE_MINUS: max(0, 1 - x) (argument
+ *   ignored, must be finite);  POWER e: powf(max(x, 0), e);  RADIAL_BASIS g: expf((-g) * (x * x)).
+ * State of the handle (an index has one similarity): allowed before or after vk_corpus_finalize, n_ops = 0 clears it; vk_corpus_view
+ * and vk_corpus_filter copy the chain of `src` into the handle they create, after that each handle is set on its own.
+ * VK_ERR_INVALID: more than VK_MAX_SIM_OPS operators, an unknown kind, an argument that is not finite.  VK_ERR_UNSUPPORTED: a
+ * chain (n_ops > 0) on VK_LAYOUT_CONTEXTUAL. */
+#define VK_MAX_SIM_OPS 8
+enum { VK_SIMOP_BIAS = 0, VK_SIMOP_SCALE = 1, VK_SIMOP_THRESHOLD = 2,
+       VK_SIMOP_ONE_MINUS = 3, VK_SIMOP_POWER = 4, VK_SIMOP_RADIAL_BASIS = 5 };
+int vk_corpus_set_sim_ops(vk_corpus_t *c, const int32_t *kinds, const float *args, int32_t n_ops);
 int vk_corpus_free(vk_corpus_t *c);
 int vk_corpus_device_bytes(const vk_corpus_t *c, int64_t *bytes);
 

@@ -37,6 +37,8 @@ def main():
 	ap.add_argument("--precision", choices=["bf16", "f32"], default="bf16", help="how the unit rows are kept in HBM")
 	ap.add_argument("--handles", type=int, default=1, help="queries in flight (vk_corpus_view handles, one host thread each), as bench.py keeps them")
 	ap.add_argument("--filter", type=float, default=0.0, help="share of tokens a pos_filter drops: times vk_corpus_filter, then queries the filtered corpus")
+	ap.add_argument("--sim-ops", type=int, default=0, help="static layout: after the plain run, the same queries under a chain of this many operators "
+		"on the cosine (vk_corpus_set_sim_ops; Bias / Scale in turn), reported beside it as phases_ms_mean_sim_ops")
 	args = ap.parse_args()
 
 	import torch
@@ -69,23 +71,33 @@ def main():
 			if len(qi) < args.len_t:
 				qi = np.concatenate([qi, rng.integers(0, V, size=args.len_t - len(qi))])
 			qs.append((np.ascontiguousarray(E[qi], dtype=np.float32), np.asarray(qi, dtype=np.int32)))
-		for i in range(args.warmup):
-			corpus.query(qs[i][0], q_token_ids=qs[i][1], algorithm=alg, locality=loc, gap_s=gap, gap_t=gap, max_matches=args.k, want_flow=args.alg == "align")
-		torch.cuda.synchronize()
-		ph = []
-		t0 = time.perf_counter()
-		for i in range(args.steps):
-			q = qs[args.warmup + i]
-			corpus.query(q[0], q_token_ids=q[1], algorithm=alg, locality=loc, gap_s=gap, gap_t=gap, max_matches=args.k, want_flow=args.alg == "align")
-			ph.append(corpus.last_timings())
-		el = time.perf_counter() - t0
+		def timed():
+			for i in range(args.warmup):
+				corpus.query(qs[i][0], q_token_ids=qs[i][1], algorithm=alg, locality=loc, gap_s=gap, gap_t=gap, max_matches=args.k, want_flow=args.alg == "align")
+			torch.cuda.synchronize()
+			ph = []
+			t0 = time.perf_counter()
+			for i in range(args.steps):
+				q = qs[args.warmup + i]
+				corpus.query(q[0], q_token_ids=q[1], algorithm=alg, locality=loc, gap_s=gap, gap_t=gap, max_matches=args.k, want_flow=args.alg == "align")
+				ph.append(corpus.last_timings())
+			return ph, time.perf_counter() - t0
+		ph, el = timed()
+		ph_ops = None
+		if args.sim_ops > 0:
+			# ((cos + 1/2) * 1/2 + 1/2) * 1/2 ...: stays inside [0, 1], so the scoring pass sees cells like the plain ones
+			corpus.set_sim_ops([(core.VK_SIMOP_BIAS, 0.5) if i % 2 == 0 else (core.VK_SIMOP_SCALE, 0.5) for i in range(args.sim_ops)])
+			ph_ops, _ = timed()
+			corpus.set_sim_ops([])
 		score_ms = float(np.mean([p["score_ms"] for p in ph]))
 		cells = float(n_tok) * args.len_t
 		print(json.dumps({"layout": "static", "alg": args.alg, "gap": args.gap, "d": args.d, "len_t": args.len_t, "len_s": [args.min_len, args.max_len],
 			"sentences": args.sentences, "pairs_per_s": args.sentences * args.steps / el, "ms_per_query": el / args.steps * 1e3,
 			"score_kernel_ms": score_ms, "GCUPS": cells / (score_ms * 1e-3) / 1e9,
 			"token_id_GBps": n_tok * 4 / (score_ms * 1e-3) / 1e9,
-			"phases_ms_mean": {k: float(np.mean([p[k] for p in ph])) for k in ph[0]}}))
+			"phases_ms_mean": {k: float(np.mean([p[k] for p in ph])) for k in ph[0]},
+			**({"sim_ops": args.sim_ops, "phases_ms_mean_sim_ops": {k: float(np.mean([p[k] for p in ph_ops])) for k in ph_ops[0]},
+				"prepare_ms_each": [p["prepare_ms"] for p in ph], "prepare_ms_each_sim_ops": [p["prepare_ms"] for p in ph_ops]} if ph_ops else {})}))
 		corpus.close()
 		return
 	corpus = core.Corpus(layout=core.VK_LAYOUT_CONTEXTUAL, d=args.d, n_tokens=n_tok, n_sentences=args.sentences,

@@ -67,10 +67,11 @@ static int batch_winner_rows(vk_corpus *c, const vk_query_desc *qs, int n_querie
 	std::vector<int32_t> &hq = keep.vec<int32_t>(n_cand, 0);
 	// static layout: the token ids of every query, 16 per query (-1: none) -- the rows kernel sets sim[id(t_j)][j] = 1 from them
 	const bool is_static = c->desc.layout == VK_LAYOUT_STATIC;
-	std::vector<int32_t> &hids = keep.vec<int32_t>(is_static ? (size_t)n_queries * 16 : 0, -1);
+	std::vector<int32_t> &hids = keep.vec<int32_t>(is_static ? (size_t)n_queries * 17 : 0, -1);   // ... and behind them every query's length
 	if (is_static) {
 		for (int i = 0; i < n_queries; i++)
 			for (int j = 0; j < qs[i].len_t && j < 16 && qs[i].q_token_ids; j++) hids[(size_t)i * 16 + j] = qs[i].q_token_ids[j];
+		for (int i = 0; i < n_queries; i++) hids[(size_t)n_queries * 16 + i] = qs[i].len_t;
 		if ((rc = c->d_bqids.reserve(hids.size(), &c->device_bytes))) return rc;
 		VK_HIP(hipMemcpyAsync(c->d_bqids, hids.data(), hids.size() * 4, hipMemcpyHostToDevice, st));
 	}
@@ -92,7 +93,7 @@ static int batch_winner_rows(vk_corpus *c, const vk_query_desc *qs, int n_querie
 	stamp("uploads issued");
 	VkWrdParams w{};
 	corpus_fields_ids(w, c);
-	if (is_static) { w.q_ids = c->d_bqids; w.q_ids_stride = 16; }
+	if (is_static) { w.q_ids = c->d_bqids; w.q_ids_stride = 16; w.cand_len_t = c->d_bqids + (size_t)n_queries * 16; }
 	w.qtile = c->d_bqt; w.qtile_stride = c->tile_bytes; w.cand_query = c->d_bcandq; w.nq = 1; w.len_t = qs[0].len_t;
 	w.d = c->desc.d;   // canonical similarity rows (sim_canon)
 	w.keys = c->d_bcand; w.rows_out = c->d_brows;
@@ -628,7 +629,22 @@ static int query_batch_body(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_q
 			}
 		if ((rc = c->d_bfix.reserve(fix.size() + 16, &c->device_bytes))) return rc;
 		if (!fix.empty()) VK_HIP(hipMemcpyAsync(c->d_bfix, fix.data(), fix.size() * 8, hipMemcpyHostToDevice, st));
-		VK_HIP(vk_launch_table_batch(c->d_tiles, c->n_tiles, c->tile_bytes, nk16, c->d_bq, n_qtiles, c->d_btable, st));
+		// under the handle's operator chain: which rows of every query tile hold a token (the others stay zero, vk_table_batch_kernel)
+		const uint32_t *d_live = nullptr;
+		if (c->sim_ops.n > 0) {
+			std::vector<uint32_t> &live = keep.vec<uint32_t>((size_t)n_qtiles);
+			std::fill(live.begin(), live.end(), 0u);
+			for (int i = 0; i < n_queries; i++)
+				for (int j = 0; j < qs[i].len_t; j++) {
+					int tile, hd, acc;
+					slot_of(i, j, tile, hd, acc);
+					live[(size_t)tile] |= 1u << (16 * hd + acc);
+				}
+			if ((rc = c->d_blive.reserve((size_t)n_qtiles + 16, &c->device_bytes))) return rc;
+			VK_HIP(hipMemcpyAsync(c->d_blive, live.data(), (size_t)n_qtiles * 4, hipMemcpyHostToDevice, st));
+			d_live = c->d_blive;
+		}
+		VK_HIP(vk_launch_table_batch(c->d_tiles, c->n_tiles, c->tile_bytes, nk16, c->d_bq, n_qtiles, c->d_btable, c->desc.vocab_size, &c->sim_ops, d_live, st));
 		VK_HIP(vk_launch_table_batch_fix(c->d_btable, c->d_bfix, (int32_t)fix.size(), st));
 		p.tok_id = c->d_tok_id; p.sent_start = c->d_sent_start; p.sent_end = c->d_sent_end;
 		p.table = c->d_btable; p.table_row = table_row; p.zero_row = (int32_t)((c->n_tiles - 1) * 16);   // the zero tile behind the vocabulary

@@ -380,7 +380,8 @@ __device__ __forceinline__ f32x4 sim_tile_f32_qlds(const uint8_t *__restrict__ q
 // 24 VGPRs, so the narrower rows keep the four-deep form and their occupancy.
 // PREC: -1 the row type is the runtime argument `prec`; 0 / 1: bf16 / fp32 rows known at compile time (the scoring kernel
 // instantiates one form per row type, so that the registers of the fp32 batches do not count against the bf16 kernels).
-template <bool DEEP = false, int PREC = -1>
+// CLIP = false: the sums as the matrix pipe leaves them (vk_table_kernel under an operator chain, which runs before the clip).
+template <bool DEEP = false, int PREC = -1, bool CLIP = true>
 __device__ __forceinline__ f32x4 sim_tile_generic(const uint8_t *__restrict__ qtile, const uint8_t *__restrict__ tile,
 	int nk, int half, int lane, int prec = 0) {
 	f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -420,7 +421,7 @@ __device__ __forceinline__ f32x4 sim_tile_generic(const uint8_t *__restrict__ qt
 #pragma unroll
 			for (int e = 0; e < 4; e++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(q[e], x[e], acc, 0, 0, 0);
 		}
-		acc[0] = clip01(acc[0]); acc[1] = clip01(acc[1]); acc[2] = clip01(acc[2]); acc[3] = clip01(acc[3]);
+		if constexpr (CLIP) { acc[0] = clip01(acc[0]); acc[1] = clip01(acc[1]); acc[2] = clip01(acc[2]); acc[3] = clip01(acc[3]); }
 		return acc;
 	}
 	const int nfull = half ? nk - 1 : nk;
@@ -456,7 +457,7 @@ __device__ __forceinline__ f32x4 sim_tile_generic(const uint8_t *__restrict__ qt
 		const bf16x8 x = load_half_block(tile + nfull * 1024, lane, true);
 		acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q, x, acc, 0, 0, 0);
 	}
-	acc[0] = clip01(acc[0]); acc[1] = clip01(acc[1]); acc[2] = clip01(acc[2]); acc[3] = clip01(acc[3]);
+	if constexpr (CLIP) { acc[0] = clip01(acc[0]); acc[1] = clip01(acc[1]); acc[2] = clip01(acc[2]); acc[3] = clip01(acc[3]); }
 	return acc;
 }
 
@@ -649,14 +650,22 @@ __device__ __forceinline__ const uint8_t *canon_row_ptr_static(const uint8_t *__
 	return etiles + (int64_t)(id >> 4) * tile_bytes + (id & 15) * 16;
 }
 
-// static layout: the cell of the per-query table (metric/static.cpp:9-78) for vocabulary entry `id` and query columns
-// c0 .. c0 + NC - 1 in the canonical arithmetic: cosine, then sim[id(t_j)][j] = 1 (:58-67), then the clip (:75)
+// static layout: one cell of the per-query table (metric/static.cpp:9-78) from its unclipped cosine -- the handle's operator chain
+// (the ModifiedVectorSim callback, :46-50; vk_sim_ops_host.h) on the columns the query holds, then sim[id(t_j)][j] = 1 (:58-67: `own`),
+// then the clip (:75).  The columns past the query keep their zeros.  The chain is a kernel argument: the branch is wave-uniform, and
+// without a chain the cell is what it was before there were chains.
+__device__ __forceinline__ float static_cell(float cosine, bool own, bool in_query, const vk_host::sim_ops &ops) {
+	if (ops.n > 0 && in_query) cosine = vk_host::sim_ops_apply(cosine, ops);
+	return own ? 1.0f : clip01(cosine);
+}
+
+// ... for vocabulary entry `id` and query columns c0 .. c0 + NC - 1 (of len_t) in the canonical arithmetic
 template <int NC>
 __device__ __forceinline__ void static_sim_canon(const uint8_t *__restrict__ etiles, int tile_bytes, int id, const uint8_t *__restrict__ qtiles,
-	int c0, int d, int prec, const int32_t *__restrict__ q_ids, float (&out)[NC]) {
+	int c0, int d, int prec, const int32_t *__restrict__ q_ids, int len_t, const vk_host::sim_ops &ops, float (&out)[NC]) {
 	sim_canon<NC>(etiles + (int64_t)(id >> 4) * tile_bytes, id & 15, qtiles + (int64_t)(c0 >> 4) * tile_bytes, c0 & 15, d, prec, out);
 #pragma unroll
-	for (int c = 0; c < NC; c++) out[c] = (q_ids && q_ids[c0 + c] == id) ? 1.0f : clip01(out[c]);
+	for (int c = 0; c < NC; c++) out[c] = static_cell(out[c], q_ids && q_ids[c0 + c] == id, c0 + c < len_t, ops);
 }
 
 // TagWeightedSlice::similarity (vectorian/core/cpp/slice/static.h:237-264): S * weight(i, j) with
@@ -702,7 +711,7 @@ __device__ __forceinline__ void static_vocab_fixup(float *__restrict__ S, int st
 	const float *__restrict__ table, int64_t table_stride, const uint32_t *__restrict__ bits, const int32_t *qkey,
 	const float *tw, const int32_t *tpos, float keep, float thr, int l,
 	const uint8_t *__restrict__ etiles = nullptr, int tile_bytes = 0, const uint8_t *__restrict__ qtiles = nullptr, int d = 0, int prec = 0,
-	const int32_t *__restrict__ q_ids = nullptr) {
+	const int32_t *__restrict__ q_ids = nullptr, const vk_host::sim_ops &ops = vk_host::sim_ops{}) {
 	const unsigned long long mask = static_vocab_shared(len_s, len_t, tok, tag, bits, qkey);
 	if (!mask) return;
 	for (int u = l; u < len_s; u += NL) {
@@ -717,7 +726,7 @@ __device__ __forceinline__ void static_vocab_fixup(float *__restrict__ S, int st
 				float raw;
 				if constexpr (CANON) {
 					float v1[1];
-					static_sim_canon<1>(etiles, tile_bytes, id, qtiles, j, d, prec, q_ids, v1);
+					static_sim_canon<1>(etiles, tile_bytes, id, qtiles, j, d, prec, q_ids, len_t, ops, v1);
 					raw = v1[0];
 				} else raw = table[(int64_t)(j >> 4) * table_stride + (int64_t)id * 16 + (j & 15)];
 				S[u * stride + j] = tag_weighted(raw, tw[RESTORE ? j : ft], pos[u], tpos[j], keep, thr);

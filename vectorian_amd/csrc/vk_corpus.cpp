@@ -469,6 +469,24 @@ int vk_corpus_finalize(vk_corpus_t *c) {
 	return VK_OK;
 }
 
+// The operator chain of a ModifiedVectorSim on the cosine (vk_sim_ops_host.h): host state of the handle, read when a query fills its
+// kernels' parameters.  Contextual corpora refuse a chain: their ~28 clip sites and the bound pass know the clipped cosine only.
+int vk_corpus_set_sim_ops(vk_corpus_t *c, const int32_t *kinds, const float *args, int32_t n_ops) {
+	if (!c || (n_ops > 0 && (!kinds || !args))) return fail(VK_ERR_INVALID, "null argument");
+	int bad = -1;
+	if (vk_host::sim_ops_check(kinds, args, n_ops, &bad) != VK_OK) {
+		if (bad < 0) return fail(VK_ERR_INVALID, "n_ops must be 0 .. VK_MAX_SIM_OPS (8), got " + std::to_string(n_ops));
+		return fail(VK_ERR_INVALID, "similarity operator " + std::to_string(bad) + ": unknown kind or an argument that is not finite");
+	}
+	if (n_ops > 0 && c->desc.layout != VK_LAYOUT_STATIC)
+		return fail(VK_ERR_UNSUPPORTED, "similarity operators run over VK_LAYOUT_STATIC only: this corpus is VK_LAYOUT_CONTEXTUAL");
+	vk_host::sim_ops ops{};
+	ops.n = n_ops;
+	for (int i = 0; i < n_ops; i++) { ops.kind[i] = kinds[i]; ops.arg[i] = args[i]; }
+	c->sim_ops = ops;
+	return VK_OK;
+}
+
 // The filtered corpus: keep flags and their scan on the device, slice table re-indexed, token rows / ids / codes /
 // magnitudes gathered.  A handle of its own (stream, workspaces); the static layout shares the vocabulary arrays.
 int vk_corpus_filter(vk_corpus_t *src, uint64_t pos_mask, uint64_t tag_mask, vk_corpus_t **out) {
@@ -525,6 +543,7 @@ int vk_corpus_filter(vk_corpus_t *src, uint64_t pos_mask, uint64_t tag_mask, vk_
 			c->rows_total = c->rows_appended = src->rows_total; c->n_tiles = src->n_tiles;
 			c->d_tiles = src->d_tiles; c->d_mag = src->d_mag; c->shares_vectors = true;
 			c->vectors_of = src->shares_vectors ? src->vectors_of : src->shared;   // the vocabulary stays alive with this handle
+			c->sim_ops = src->sim_ops;   // the source's similarity (a contextual corpus has no chain)
 			if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return fail(VK_ERR_HIP, "hipStreamCreate failed");
 			for (auto &e : c->ev) if (hipEventCreate(&e) != hipSuccess) return fail(VK_ERR_HIP, "hipEventCreate failed");
 			int r;

@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vk_sim_ops_host.h"   // vk_host::sim_ops: the operator chain on the cosine of the static layout, by value in the structs below
+
 #define VK_DEV_LOCAL 0
 #define VK_DEV_GLOBAL 1
 #define VK_DEV_SEMIGLOBAL 2
@@ -166,6 +168,7 @@ struct VkWrdParams {
 	const int32_t *cand_query; // vk_rows_kernel, batches: candidate w belongs to query cand_query[w], whose tile sits at qtile + that * qtile_stride
 	int64_t qtile_stride;      // (static layout: its token ids at q_ids + that * q_ids_stride)
 	int32_t q_ids_stride;
+	const int32_t *cand_len_t; // ... and has cand_len_t[that] tokens (null: len_t for all; the operator chain runs on a query's own columns only)
 	// queries of more than 16 tokens over slices of more than VK_DEV_MAX_SENT_LEN tokens
 	const int32_t *group_list; // vk_long_bound_kernel: groups of the slice table that hold one long slice (row 4 g)
 	int32_t n_list;
@@ -178,6 +181,7 @@ struct VkWrdParams {
 	uint8_t *scratch;          // vk_wrd_exact_long_kernel, nq > 1: flows, costs and similarity rows of one candidate per workgroup
 	int64_t scratch_stride;
 	int32_t n_cand;
+	vk_host::sim_ops sim_ops;  // static layout: the operator chain between the cosine and sim[id(t_j)][j] = 1 / the clip (static_cell, vk_common.hip.h); n = 0: none
 };
 
 struct VkFlowParams {
@@ -207,6 +211,7 @@ struct VkFlowParams {
 	float *raw_out;            // [k]
 	int16_t *mapping;          // [k x 16]
 	float *edge_sim;           // [k x 16]
+	vk_host::sim_ops sim_ops;  // static layout: the operator chain between the cosine and sim[id(t_j)][j] = 1 / the clip (static_cell, vk_common.hip.h); n = 0: none
 };
 
 // a batch of at most 4 queries with common options over one pass of a contextual corpus (vk_score_batch_kernel)
@@ -292,6 +297,7 @@ struct VkWideParams {
 	int32_t dp_rows_len;       //   [k][dp_rows_len][16 nq], row 0 = a winner's first token; null: the kernel restates them itself
 	int32_t h_ring;            // vk_wide_kernel, global-state form with ws_tail: rows of the LDS ring of the column history (vk_wide_ring_rows; 0: history in the scratch)
 	int32_t ws_tail;           // vk_wide_kernel, general gaps: w_s[k] == w_s[ws_tail] for every k >= ws_tail up to max_len (0: no such tail)
+	vk_host::sim_ops sim_ops;  // static layout: the operator chain between the cosine and sim[id(t_j)][j] = 1 / the clip (static_cell, vk_common.hip.h); n = 0: none
 };
 
 // queries of 65 .. VK_MAX_QUERY_LEN tokens (vk_longq_kernel): one wave per slice, lane = slice token, anti-diagonal sweep
@@ -338,6 +344,7 @@ struct VkLongqParams {
 	const int32_t *order;
 	int32_t n_order;
 	int64_t dm_off, su_off;
+	vk_host::sim_ops sim_ops;  // static layout: the operator chain between the cosine and sim[id(t_j)][j] = 1 / the clip (static_cell, vk_common.hip.h); n = 0: none
 };
 
 #ifdef __cplusplus
@@ -406,7 +413,7 @@ hipError_t vk_launch_filter_rows(const uint8_t *src, uint8_t *dst, const int32_t
 hipError_t vk_launch_filter_gather(const void *src, void *dst, int32_t elem_bytes, const int32_t *src_of, int64_t n_kept,
 	hipStream_t stream);
 hipError_t vk_launch_table(const uint8_t *etiles, const uint8_t *qtile, int32_t n_tiles, int32_t nk32, int32_t tail,
-	int32_t tile_bytes, float *table, const int32_t *q_ids, int32_t len_t, int32_t V, int32_t prec, hipStream_t stream);
+	int32_t tile_bytes, float *table, const int32_t *q_ids, int32_t len_t, int32_t V, int32_t prec, const vk_host::sim_ops *ops, hipStream_t stream);
 hipError_t vk_launch_score(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
 int32_t vk_score_m8t_tail_k(void);   // K of the flat-tailed bound kernels over the 6-bit shadow (vk_score_m8t.hip) ...
 int32_t vk_score_m7t_tail_k(void);   // ... and over the 8-bit shadow (vk_score_m7t.hip)
@@ -430,9 +437,11 @@ hipError_t vk_launch_batch_pack(const uint8_t *src_tiles, uint8_t *dst_tiles, co
 	int64_t n, int32_t tps, int32_t tile_bytes, hipStream_t stream);
 int vk_rwmd_batch_supported(int32_t nk, int32_t half);
 // the static layout's batch: table[V rows][n_qtiles][2][16] from the packed 32-row query tiles (any row width), its diagonal cells
-// (sim[id(t_j)][j] = 1, metric/static.cpp:58-67: `offsets` floats of the table set to 1), and the gather + epilogue pass
+// (sim[id(t_j)][j] = 1, metric/static.cpp:58-67: `offsets` floats of the table set to 1), and the gather + epilogue pass.
+// ops->n > 0: the chain on the cells of the V vocabulary rows x the query rows a token holds -- bit 16 h + a of live[tile]: lane half h,
+// accumulator slot a; the padding of either side stays zero, as the epilogues' maxima expect
 hipError_t vk_launch_table_batch(const uint8_t *etiles, int64_t n_vtiles, int32_t tile_bytes, int32_t nk16, const uint8_t *qtiles, int32_t n_qtiles,
-	uint16_t *table, hipStream_t stream);
+	uint16_t *table, int32_t V, const vk_host::sim_ops *ops, const uint32_t *live, hipStream_t stream);
 hipError_t vk_launch_table_batch_fix(uint16_t *table, const int64_t *offsets, int32_t n, hipStream_t stream);
 hipError_t vk_launch_rwmd_static32(const VkRwmdBatchParams *p, int32_t w64, hipStream_t stream);
 hipError_t vk_launch_topk_wave_batch(const float *scores, const uint64_t *keys_in, int64_t n, float min_score, int32_t k,

@@ -10,6 +10,7 @@
 #include "vk_result_host.h"
 #include "vk_bound_host.h"
 #include "vk_route_host.h"
+#include "vk_sim_ops_host.h"
 
 #include <algorithm>
 #include <atomic>
@@ -149,6 +150,9 @@ struct vk_corpus_shape {
 	const uint8_t *shadow = nullptr;
 	vk_host::shadow_format shadow_format;
 	float shadow_n = 0.0f, shadow_x = 0.0f;
+	// the operator chain on the cosine (vk_corpus_set_sim_ops; static layout only): a view and a filtered corpus start with their
+	// source's, after that each handle is set on its own
+	vk_host::sim_ops sim_ops{};
 };
 
 // vk_corpus::batch_state by index (the internal export vk_batch_state hands the array out in this order; the tests name the
@@ -223,6 +227,7 @@ struct vk_corpus : vk_corpus_shape {
 	vk_devbuf<int32_t> d_sb_id[2]; int64_t sb_n[2] = {0, 0}; bool sb_built = false; int64_t sb_empty = 0;
 	vk_devbuf<uint16_t> d_btable;
 	vk_devbuf<int64_t> d_bfix;
+	vk_devbuf<uint32_t> d_blive;  // ... under an operator chain: per query tile of the batch, the rows that hold a token
 	vk_devbuf<int32_t> d_bqids;   // token ids of a batch's queries, 16 per query (the winners' rows: sim[id(t_j)][j] = 1)
 	vk_devbuf<uint64_t> d_sort[2]; vk_devbuf<uint8_t> d_sort_temp;   // result sets beyond VK_MAX_MATCHES: all keys, sorted
 	// route and form of the last vk_query_batch on this handle (vk_batch_state in vk_corpus.cpp, for the tests; host integers only),
@@ -279,9 +284,13 @@ template <typename P> void corpus_fields(P &p, const vk_corpus *c) {
 	p.tiles = c->d_tiles; p.sent_start = c->d_sent_start; p.sent_end = c->d_sent_end;
 	p.nk32 = c->nk32; p.tail = c->tail; p.tile_bytes = c->tile_bytes;
 }
+// the handle's operator chain into the structs of the kernels that restate cells of the static layout (the others have no such field)
+template <typename P> auto sim_ops_field(P &p, const vk_corpus *c, int) -> decltype((void)p.sim_ops) { p.sim_ops = c->sim_ops; }
+template <typename P> void sim_ops_field(P &, const vk_corpus *, long) {}
 // ... and those of the structs that serve both layouts and both precisions (d_tok_id is null unless the layout is static)
 template <typename P> void corpus_fields_ids(P &p, const vk_corpus *c) {
 	corpus_fields(p, c);
+	sim_ops_field(p, c, 0);
 	p.tok_id = c->d_tok_id; p.prec = c->prec;
 	p.layout = c->desc.layout == VK_LAYOUT_STATIC ? VK_DEV_LAYOUT_STATIC : VK_DEV_LAYOUT_CONTEXTUAL;
 }

@@ -65,7 +65,7 @@ int vk_longq_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_
 		if ((rc = lq.table.reserve((size_t)nq * (size_t)table_stride, &c->device_bytes))) return rc;
 		for (int t = 0; t < nq; t++)   // one [V_pad x 16] table per 16 query tokens: cosine, sim[id(t_j)][j] = 1, clip (metric/static.cpp:9-78)
 			VK_HIP(vk_launch_table(c->d_tiles, lq.qt + (size_t)t * c->tile_bytes, (int32_t)c->n_tiles, c->nk32, c->tail, c->tile_bytes,
-				lq.table + (size_t)t * table_stride, q->q_token_ids ? lq.il + LTP + t * 16 : nullptr, std::min(16, LT - t * 16), c->desc.vocab_size, c->prec, st));
+				lq.table + (size_t)t * table_stride, q->q_token_ids ? lq.il + LTP + t * 16 : nullptr, std::min(16, LT - t * 16), c->desc.vocab_size, c->prec, &c->sim_ops, st));
 	}
 
 	corpus_fields_ids(p, c);

@@ -224,12 +224,21 @@ extern "C" hipError_t vk_launch_fp6_bound_probe(const uint8_t *qtile6, const uin
 // static layout: per-query similarity table [V_pad x 16] (metric/static.cpp:9-78)
 // ---------------------------------------------------------------------------
 
+// OPS: under an operator chain (vk_corpus_set_sim_ops) -- the tile product without its clip, the chain on the cells of the V vocabulary
+// rows x the len_t query columns, then the clip; the padding of either side stays zero.  Without a chain: the kernel as it always was.
+template <bool OPS>
 __global__ __launch_bounds__(256) void vk_table_kernel(const uint8_t *__restrict__ etiles, const uint8_t *__restrict__ qtile,
-	int32_t n_tiles, int32_t nk32, int32_t tail, int32_t tile_bytes, float *__restrict__ table, int32_t prec) {
+	int32_t n_tiles, int32_t nk32, int32_t tail, int32_t tile_bytes, float *__restrict__ table, int32_t prec, int32_t len_t, int32_t V,
+	const vk_host::sim_ops ops) {
 	const int lane = threadIdx.x & 63;
 	const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
 	if (tile >= n_tiles) return;
-	const f32x4 acc = sim_tile_generic(qtile, etiles + (int64_t)tile * tile_bytes, nk32, tail, lane, prec);
+	f32x4 acc = sim_tile_generic<false, -1, !OPS>(qtile, etiles + (int64_t)tile * tile_bytes, nk32, tail, lane, prec);
+	if constexpr (OPS) {
+		const bool word = tile * 16 + (lane & 15) < V;
+#pragma unroll
+		for (int r = 0; r < 4; r++) acc[r] = static_cell(acc[r], false, word && (lane >> 4) * 4 + r < len_t, ops);
+	}
 	*reinterpret_cast<f32x4 *>(table + ((int64_t)tile * 16 + (lane & 15)) * 16 + (lane >> 4) * 4) = acc;
 }
 
@@ -254,8 +263,9 @@ extern "C" hipError_t vk_launch_pack(const void *in, int32_t dtype_bf16, int64_t
 }
 
 extern "C" hipError_t vk_launch_table(const uint8_t *etiles, const uint8_t *qtile, int32_t n_tiles, int32_t nk32, int32_t tail,
-	int32_t tile_bytes, float *table, const int32_t *q_ids, int32_t len_t, int32_t V, int32_t prec, hipStream_t stream) {
-	vk_table_kernel<<<(n_tiles + 3) / 4, 256, 0, stream>>>(etiles, qtile, n_tiles, nk32, tail, tile_bytes, table, prec);
+	int32_t tile_bytes, float *table, const int32_t *q_ids, int32_t len_t, int32_t V, int32_t prec, const vk_host::sim_ops *ops, hipStream_t stream) {
+	if (ops && ops->n > 0) vk_table_kernel<true><<<(n_tiles + 3) / 4, 256, 0, stream>>>(etiles, qtile, n_tiles, nk32, tail, tile_bytes, table, prec, len_t, V, *ops);
+	else vk_table_kernel<false><<<(n_tiles + 3) / 4, 256, 0, stream>>>(etiles, qtile, n_tiles, nk32, tail, tile_bytes, table, prec, len_t, V, vk_host::sim_ops{});
 	if (q_ids) vk_table_fix_kernel<<<1, 64, 0, stream>>>(table, q_ids, len_t, V);
 	return hipGetLastError();
 }

@@ -445,7 +445,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		VK_HIP(hipMemcpyAsync(c->d_qids, ids, 80 * sizeof(int32_t), hipMemcpyHostToDevice, st));
 		for (int t = 0; t < nq && !only; t++)   // one [V_pad x 16] table per 16 query tokens (the traceback kernels restate their cells themselves)
 			VK_HIP(vk_launch_table(c->d_tiles, c->d_qtile + (size_t)t * c->tile_bytes, (int32_t)c->n_tiles, c->nk32, c->tail, c->tile_bytes,
-				c->d_table + t * table_stride, q->q_token_ids ? c->d_qids + t * 16 : nullptr, std::min(16, q->len_t - t * 16), c->desc.vocab_size, c->prec, st));
+				c->d_table + t * table_stride, q->q_token_ids ? c->d_qids + t * 16 : nullptr, std::min(16, q->len_t - t * 16), c->desc.vocab_size, c->prec, &c->sim_ops, st));
 	}
 
 	// ---- the size of the selection (known before the scoring pass: the bound pass prunes against it)
@@ -1068,6 +1068,30 @@ int vk_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out) {
 	const int rc = vk_validate_query(c, q, out);
 	if (rc) return rc;
 	if (q->abort && *q->abort) { out->n_out = 0; return fail(VK_ERR_ABORTED, "query aborted by the caller"); }
+	// Under an operator chain (vk_corpus_set_sim_ops) the winners of an alignment are restated in the canonical arithmetic whether
+	// or not the caller wants their tracebacks: an operator such as THRESHOLD makes a score discontinuous in its cells, so the sums of
+	// the scoring pass (matrix pipe order) state no score to within a rounding error as they do for the plain cosine.  The query runs
+	// with tracebacks into arrays of its own; the caller's mapping / edge_sim stay untouched, as without a chain.
+	vk_query_desc q_flow;
+	vk_topk_out out_flow;
+	std::vector<int16_t> own_map;
+	std::vector<float> own_sim;
+	bool restate = false;
+	if (c->sim_ops.n > 0 && q->algorithm == VK_ALG_ALIGN && !q->want_flow && !q->only_slices && q->submatch_weight == 0.0f) {
+		q_flow = *q; q_flow.want_flow = 1;
+		out_flow = *out;
+		own_map.assign((size_t)out->capacity * (size_t)q->len_t, (int16_t)-1);
+		own_sim.assign((size_t)out->capacity * (size_t)q->len_t, 0.0f);
+		out_flow.mapping = own_map.data(); out_flow.edge_sim = own_sim.data();
+		restate = vk_validate_query(c, &q_flow, &out_flow) == VK_OK;   // (a result set too large to retrace stays on the scoring pass's scores)
+	}
+	if (restate) {
+		const int rc2 = vk_run_guarded([&](vk_host_keep &keep) { return query_body(c, &q_flow, &out_flow, keep); },
+			[&]() { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream); },
+			[](const char *what) { return fail(VK_ERR_INVALID, std::string("vk_query: ") + what); });
+		out->n_out = out_flow.n_out;
+		return rc2;
+	}
 	// an error inside the body leaves no copy in flight behind: the stream is drained before the body's host buffers die
 	return vk_run_guarded([&](vk_host_keep &keep) { return query_body(c, q, out, keep); },
 		[&]() { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream); },

@@ -788,8 +788,14 @@ __global__ __launch_bounds__(64 * NW) void vk_rwmd_batch32d_kernel(VkRwmdBatchPa
 // the canonical restating covers it, vk_batch.cpp), the scores a caller with flows receives are restated from canonical rows.
 // ---------------------------------------------------------------------------
 
+// OPS: under an operator chain (vk_corpus_set_sim_ops) the cells of the V vocabulary rows x the query rows that hold a token (bit
+// 16 h + i of live[qt]: lane half h, accumulator slot i) go through the chain before the clip and the rounding.  Everything else --
+// the zero tile behind the vocabulary that a sentence's padding points at, the query tiles' empty rows -- stays 0: the epilogues'
+// maxima count on it.
+template <bool OPS>
 __global__ __launch_bounds__(256) void vk_table_batch_kernel(const uint8_t *__restrict__ etiles, int64_t n_vtiles, int tile_bytes, int nk16,
-	const uint8_t *__restrict__ qtiles, int n_qtiles, uint16_t *__restrict__ table) {
+	const uint8_t *__restrict__ qtiles, int n_qtiles, uint16_t *__restrict__ table, int32_t V, const vk_host::sim_ops ops,
+	const uint32_t *__restrict__ live) {
 	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 	const int n32 = lane & 31, h = lane >> 5;
 	const int64_t pair = (int64_t)blockIdx.x * 4 + wv;           // vocabulary tiles 2 pair, 2 pair + 1: 32 words = the 32 columns
@@ -808,6 +814,12 @@ __global__ __launch_bounds__(256) void vk_table_batch_kernel(const uint8_t *__re
 			const bf16x8 av = *reinterpret_cast<const bf16x8 *>(a + t * 1024);
 			const bf16x8 bv = *reinterpret_cast<const bf16x8 *>(tp + (t >> 1) * 1024 + (2 * (t & 1) + h) * 256);
 			acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8n, av), __builtin_bit_cast(bf16x8n, bv), acc, 0, 0, 0);
+		}
+		if constexpr (OPS) {
+			const bool word = tile * 16 + (n32 & 15) < V;
+			const uint32_t rows = live[qt] >> (16 * h);
+#pragma unroll
+			for (int i = 0; i < 16; i++) acc[i] = static_cell(acc[i], false, word && ((rows >> i) & 1u), ops);
 		}
 		// clip to [0, 1] (SimilarityMatrix::clip, metric/metric.h:28-30), then 16-bit fixed point: slots 2 k, 2 k + 1 in one dword
 		uint32_t w[8];
@@ -889,10 +901,13 @@ __global__ __launch_bounds__(256) void vk_rwmd_static32_kernel(VkRwmdBatchParams
 }
 
 extern "C" hipError_t vk_launch_table_batch(const uint8_t *etiles, int64_t n_vtiles, int32_t tile_bytes, int32_t nk16, const uint8_t *qtiles, int32_t n_qtiles,
-	uint16_t *table, hipStream_t stream) {
+	uint16_t *table, int32_t V, const vk_host::sim_ops *ops, const uint32_t *live, hipStream_t stream) {
 	const int64_t pairs = (n_vtiles + 1) / 2;
 	if (pairs < 1 || n_qtiles < 1) return hipSuccess;
-	vk_table_batch_kernel<<<(unsigned)((pairs + 3) / 4), 256, 0, stream>>>(etiles, n_vtiles, tile_bytes, nk16, qtiles, n_qtiles, table);
+	if (ops && ops->n > 0) {
+		if (!live) return hipErrorInvalidValue;
+		vk_table_batch_kernel<true><<<(unsigned)((pairs + 3) / 4), 256, 0, stream>>>(etiles, n_vtiles, tile_bytes, nk16, qtiles, n_qtiles, table, V, *ops, live);
+	} else vk_table_batch_kernel<false><<<(unsigned)((pairs + 3) / 4), 256, 0, stream>>>(etiles, n_vtiles, tile_bytes, nk16, qtiles, n_qtiles, table, V, vk_host::sim_ops{}, nullptr);
 	return hipGetLastError();
 }
 

@@ -83,7 +83,7 @@ __device__ __forceinline__ int transport_sim_rows(const VkWrdParams &p, float *S
 				const int c0 = 16 * b + (lane >> 4) * 4;
 #pragma unroll
 				for (int r = 0; r < 4; r++) {
-					val[r] = (is_static && p.q_ids && p.q_ids[c0 + r] == id) ? 1.0f : clip01(val[r]);   // sim[id(t_j)][j] = 1 (metric/static.cpp:58-67)
+					val[r] = is_static ? static_cell(val[r], p.q_ids && p.q_ids[c0 + r] == id, c0 + r < p.len_t, p.sim_ops) : clip01(val[r]);   // chain, sim[id(t_j)][j] = 1 (metric/static.cpp:46-67), clip
 					if (p.pos_s) val[r] = tag_weighted(val[r], p.tw[c0 + r], ps, p.tpos[c0 + r], p.tw_keep, p.tw_threshold);
 				}
 				*reinterpret_cast<float4 *>(S + (ti * 16 + (lane & 15)) * N + c0) = make_float4(val[0], val[1], val[2], val[3]);
@@ -92,7 +92,7 @@ __device__ __forceinline__ int transport_sim_rows(const VkWrdParams &p, float *S
 		if (is_static && p.qid_bits && p.pos_s) {   // tag-weighted vocabulary transport: cells upstream writes twice (static_vocab_fixup, vk_common.hip.h)
 			wave_lds_fence();
 			static_vocab_fixup<64, true>(S, N, m, p.len_t, p.tok_id + t_a, p.tag_s + t_a, p.pos_s + t_a, p.table, p.table_stride,
-				p.qid_bits, p.qkey, p.tw, p.tpos, p.tw_keep, p.tw_threshold, lane, p.tiles, p.tile_bytes, p.qtile, p.d, p.prec, p.q_ids);
+				p.qid_bits, p.qkey, p.tw, p.tpos, p.tw_keep, p.tw_threshold, lane, p.tiles, p.tile_bytes, p.qtile, p.d, p.prec, p.q_ids, p.sim_ops);
 		}
 		return is_static ? 0 : t_a - tile0 * 16;
 	}
@@ -691,6 +691,7 @@ __global__ __launch_bounds__(64) void vk_rows_kernel(VkWrdParams p) {
 	if (p.cand_query) {   // a batch: every candidate against its own query (static layout: its own token ids)
 		p.qtile += (int64_t)p.cand_query[w] * p.qtile_stride;
 		if (p.q_ids) p.q_ids += (int64_t)p.cand_query[w] * p.q_ids_stride;
+		if (p.cand_len_t) p.len_t = p.cand_len_t[p.cand_query[w]];
 	}
 	if (key != 0) {
 		const int64_t g = (int64_t)(uint32_t)(key & 0xffffffffu);
@@ -741,7 +742,7 @@ __global__ __launch_bounds__(64) void vk_canon_rows_kernel(VkWrdParams p) {
 		const int c0 = 16 * b + (lane >> 4) * 4;
 #pragma unroll
 		for (int r = 0; r < 4; r++) {
-			val[r] = (is_static && p.q_ids && p.q_ids[c0 + r] == id) ? 1.0f : clip01(val[r]);
+			val[r] = is_static ? static_cell(val[r], p.q_ids && p.q_ids[c0 + r] == id, c0 + r < p.len_t, p.sim_ops) : clip01(val[r]);
 			if (p.pos_s) val[r] = tag_weighted(val[r], p.tw[c0 + r], ps, p.tpos[c0 + r], p.tw_keep, p.tw_threshold);
 		}
 		if (live) *reinterpret_cast<float4 *>(out + c0) = make_float4(val[0], val[1], val[2], val[3]);

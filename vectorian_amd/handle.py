@@ -101,6 +101,14 @@ class Corpus:
 		_core._check(_core.lib().vk_corpus_set_slices(self._h, _core._np_ptr(start), _core._np_ptr(end), len(start)))
 		self._max_len = int((end - start).max()) if len(start) else 0
 
+	def set_sim_ops(self, ops):
+		"""the operator chain on the cosine (vk_corpus_set_sim_ops): ops is a sequence of (kind, arg) pairs, or of operators of
+		vectorian_amd.kernel (anything with `sim_op`); empty clears it.  Views and filtered corpora made afterwards inherit it."""
+		pairs = [tuple(op.sim_op) if hasattr(op, "sim_op") else tuple(op) for op in ops]
+		kinds = np.ascontiguousarray([int(k) for k, _ in pairs], dtype=np.int32)
+		args = np.ascontiguousarray([a for _, a in pairs], dtype=np.float32)
+		_core._check(_core.lib().vk_corpus_set_sim_ops(self._h, _core._np_ptr(kinds), _core._np_ptr(args), len(pairs)))
+
 	def finalize(self):
 		_core._check(_core.lib().vk_corpus_finalize(self._h))
 

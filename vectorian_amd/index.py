@@ -26,7 +26,7 @@ from vectorian_amd.lanes import LanesMixin
 from vectorian_amd.match import HipMatch, Match, PyMatch, Region, TokenMatch, TokenMatchEdge, TokenMatchT, _Winners
 from vectorian_amd.options import _QUERY_OPTION_WHITELIST, _split_gap, backend_args
 from vectorian_amd.query import PreparedQuery, Query, default_tokenizer
-from vectorian_amd.sim import CosineSim, EmbeddingTokenSim, OptimizedSpanSim
+from vectorian_amd.sim import CosineSim, EmbeddingTokenSim, ModifiedVectorSim, OptimizedSpanSim
 
 PartitionData = collections.namedtuple("PartitionData", ["level", "window_size", "window_step"])
 _NO_LOCK = contextlib.nullcontext()   # backends without a per-handle lock (the test double)
@@ -104,10 +104,10 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 			raise TypeError(f"{type(sim).__name__}: the HIP index implements OptimizedSpanSim")
 		token_sim = sim.token_sim
 		if not isinstance(token_sim, EmbeddingTokenSim):
-			raise NotImplementedError("token similarity modifiers are outside the HIP path (SURVEY 2.1)")
-		if not isinstance(token_sim.similarity, CosineSim):
-			raise NotImplementedError(f"{token_sim.similarity.name}: the HIP path computes CosineSim")
+			raise NotImplementedError("token similarity modifiers are outside the HIP path (SURVEY 2.1): they combine clipped "
+				"similarity matrices and leave values outside [0, 1]; shape ONE cosine with ModifiedVectorSim instead")
 		self._embedding = token_sim.embedding
+		self._sim_ops = self._operator_chain(token_sim.similarity, self._embedding)
 		self._metric_name = token_sim.to_args(self)["name"]
 		session = self.session
 		level, size = partition.level, partition.window_size
@@ -173,6 +173,9 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 				vocab_size=max(1, session.vocab.size), keep_magnitudes=True, device=device, precision=precision)
 			E = vocab_vectors.unmodified if session.vocab.size else np.zeros((1, emb.dimension), np.float32)
 			self._corpus.append_vectors(E, normalize=True)
+			if self._sim_ops:
+				# state of the handle: the views (find_many) and filtered corpora made later inherit it through the library
+				self._corpus.set_sim_ops(self._sim_ops)
 			ids = np.concatenate([session.doc_token_ids(i) for i in range(len(session.documents))]) if n_tokens else np.zeros(0, np.int32)
 			self._corpus.set_token_ids(np.ascontiguousarray(ids[t0:t1]))
 			self._token_ids = np.asarray(ids, dtype=np.int32)
@@ -207,6 +210,33 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 			self._corpus.set_slices(dev_start, dev_end)
 		self._corpus.finalize()
 		self._max_slice_len = int((np.asarray(dev_end) - np.asarray(dev_start)).max()) if len(dev_start) else 0   # of the resident part
+
+	@staticmethod
+	def _operator_chain(similarity, embedding):
+		"""the (kind, float32 arg) pairs of the vector similarity's operator chain -- empty for the plain CosineSim -- or the
+		reason this similarity does not run here"""
+		if isinstance(similarity, CosineSim):
+			return []
+		if not isinstance(similarity, ModifiedVectorSim):
+			raise NotImplementedError(f"{similarity.name}: the HIP path computes CosineSim")
+		source, operators = similarity.source, similarity.operators
+		if isinstance(source, ModifiedVectorSim):
+			raise NotImplementedError(f"{similarity.name}: nested ModifiedVectorSim; give ONE ModifiedVectorSim all the operators, in order")
+		if not isinstance(source, CosineSim):
+			raise NotImplementedError(f"{similarity.name}: the HIP path modifies CosineSim only, not {source.name}")
+		if len(operators) > core.VK_MAX_SIM_OPS:
+			raise NotImplementedError(f"{similarity.name}: {len(operators)} operators; the HIP path takes at most {core.VK_MAX_SIM_OPS}")
+		if not embedding.is_static:
+			raise NotImplementedError(f"{similarity.name}: operators on the cosine run over static embeddings only; "
+				f"{embedding.name} is contextual")
+		ops = []
+		for op in operators:
+			try:
+				kind, arg = op.sim_op
+			except (AttributeError, NotImplementedError):
+				raise NotImplementedError(f"{type(op).__name__}: not an operator of vectorian_amd.kernel (the device runs those six)") from None
+			ops.append((int(kind), np.float32(arg)))
+		return ops
 
 	@property
 	def metric_name(self):

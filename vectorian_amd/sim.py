@@ -1,17 +1,21 @@
 """Similarity operators: the surface of `vectorian.sim` on the hot path.
 
 VectorSim / CosineSim   vectorian/sim/vector.py:17-78
+ModifiedVectorSim       vectorian/sim/vector.py:179-200 (its operators: vectorian_amd/kernel.py, re-exported here)
 TokenSim / EmbeddingTokenSim   vectorian/sim/token.py:4-44
 SpanSim / OptimizedSpanSim     vectorian/sim/span.py:9-71
-The other VectorSims and the modifier combinators of the reference are out of scope
-(SURVEY 2.1); the tag-weighted variant is a "next" row and is rejected
-explicitly rather than ignored.
+A ModifiedVectorSim over CosineSim -- a chain of up to 8 operators on the unclipped cosine -- runs on the device over static
+embeddings: `EmbeddingTokenSim(emb, ModifiedVectorSim(CosineSim(), Bias(1), Scale(0.5)))`.  The other VectorSims,
+chains over contextual embeddings and the token-similarity modifier combinators of the reference are out of scope
+and are rejected explicitly rather than ignored; the tag-weighted variant is a "next" row.
 """
 
 import numpy as np
 
 from vectorian_amd.alignment import ConstantGapCost, LocalAlignment, Optimizer
 from vectorian_amd.embedding import AbstractVectors
+from vectorian_amd.kernel import (  # noqa: F401  (the reference's users import the operators next to the similarities)
+	Bias, DistanceToSimilarity, Kernel, Power, RadialBasis, Scale, Threshold, UnaryOperator)
 
 
 class VectorSim:
@@ -38,6 +42,30 @@ class CosineSim(VectorSim):
 	@property
 	def name(self):
 		return "cosine"
+
+
+class ModifiedVectorSim(VectorSim):
+	"""a VectorSim whose output is modified by one or more operators (vectorian/sim/vector.py:179-200)"""
+
+	def __init__(self, source: VectorSim, *operators: UnaryOperator):
+		self._source = source
+		self._kernel = Kernel(operators)
+
+	@property
+	def source(self):
+		return self._source
+
+	@property
+	def operators(self):
+		return self._kernel.operators
+
+	def compute(self, a, b, out):
+		self._source(a, b, out)
+		self._kernel(out)
+
+	@property
+	def name(self):
+		return self._kernel.name(self._source.name)
 
 
 class TokenSim:
