@@ -1,12 +1,26 @@
 #!/usr/bin/env python3
 """Register / scratch / LDS use of every kernel of one translation unit, from hipcc's resource remarks.
-  python tools/kernel_regs.py vectorian_amd/csrc/vk_score_m0.hip [substring-filter] [-- extra hipcc flags]"""
+  python tools/kernel_regs.py vectorian_amd/csrc/vk_score_m0.hip [substring-filter] [-- extra hipcc flags]
+  python tools/kernel_regs.py --bound    every unit of the bound pass: vk_score_m7 / m7w / m7t (8-bit), m8 / m8w / m8t (6-bit), m9 / m9w / m9t
+                                         (6-bit, compact tiles: DESIGN 11.11), compiled side by side"""
+import os
 import re
 import subprocess
 import sys
 
+BOUND_UNITS = ["vk_score_m%s%s.hip" % (m, w) for m in (7, 8, 9) for w in ("", "w", "t")]
+
+
 def main():
 	args = sys.argv[1:]
+	if args[:1] == ["--bound"]:
+		here = os.path.dirname(os.path.abspath(__file__))
+		procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), os.path.join(here, "..", "vectorian_amd", "csrc", u)] + args[1:],
+			stdout=subprocess.PIPE, text=True) for u in BOUND_UNITS]
+		for u, p in zip(BOUND_UNITS, procs):
+			print(u)
+			print(p.communicate()[0], end="")
+		return
 	extra = []
 	if "--" in args:
 		i = args.index("--")

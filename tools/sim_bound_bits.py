@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""CPU simulation of the bound pass under three quantizers of the shadow -- int8 (s = max|x| / 127), int6 (s = max|x| / 31)
-and E2M3 (s = max|x| / 7.5) -- on a `synth` corpus of n slices x 32 tokens x 300-d, generated and scored one chunk at a
+"""CPU simulation of the bound pass under six quantizers of the shadow -- int8 (s = max|x| / 127), int6 (s = max|x| / 31),
+E2M3 (s = max|x| / 7.5), E2M3 as the compact shadow stores it (e2m3c: s and e rounded UP to bf16, the codes computed with
+that s) and the two 4-bit grids E2M1 (0, 0.5, 1, 1.5, 2, 3, 4, 6; s = max|x| / 6) and int4 (s = max|x| / 7) -- on a `synth` corpus of n slices x 32 tokens x 300-d, generated and scored one chunk at a
 time.  No GPU: the exact scores are the oracle's (bf16 rows, `want_all_scores`), the bounds are the oracle's DP over a numpy
 restatement of the bound cell (`S_rows`: ub = clip01((s_x s_q) q^ . x^ + e_x a_q + e_q N + gamma), float32 in the kernel's order), and
 rounds 1 and 2 are taken as vk_query.cpp takes them (M = 64 largest bounds, theta = the kk-th best exact score among them, kk = 18;
@@ -16,7 +17,8 @@ k <= K, the minimum of w(K + 1 .. 32) beyond), which is what the flat-tailed bou
 the largest (tail bound - full-table bound).
 
   python tools/sim_bound_bits.py --slices 1000000 --chunk 25000 --queries 16 --threads 16 --out profiles/bound_fp6_sim.json
-  python tools/sim_bound_bits.py --slices 200000 --chunk 25000 --queries 16 --threads 16 --tail 3,4,6 --out profiles/bound_tail_sim.json"""
+  python tools/sim_bound_bits.py --slices 200000 --chunk 25000 --queries 16 --threads 16 --tail 3,4,6 --out profiles/bound_tail_sim.json
+  python tools/sim_bound_bits.py --slices 200000 --chunk 25000 --queries 16 --threads 16 --out profiles/bound_compact_sim.json"""
 import argparse
 import json
 import os
@@ -58,15 +60,45 @@ def grid_e2m3(x):
 	return np.copysign(a, x) * (s > 0)[:, None], s
 
 
-QUANTIZERS = {"int8": grid_uniform(127), "int6": grid_uniform(31), "e2m3": grid_e2m3}
+def bf16_up(v):
+	"""the least bf16 value >= v (v >= 0), as float32"""
+	u = np.ascontiguousarray(v, dtype=F).view(np.uint32).astype(np.uint64)
+	return np.where(u & 0xffff, (u | 0xffff) + 1, u).astype(np.uint32).view(F)
+
+
+def grid_e2m3_compact(x):
+	"""vk_host::quantize_row<grid_e2m3> under bf16_meta: the scale rounded up to bf16 first, the codes computed with it"""
+	s = bf16_up((np.abs(x).max(axis=1) / F(7.5)).astype(F))
+	safe = np.where(s > 0, s, F(1)).astype(F)
+	t = np.minimum(F(7.5), np.abs(x / safe[:, None]))
+	step = np.where(t < 2, F(0.125), np.where(t < 4, F(0.25), F(0.5))).astype(F)
+	a = np.minimum(F(7.5), np.rint(t / step) * step).astype(F)
+	return np.copysign(a, x) * (s > 0)[:, None], s
+
+
+E2M1 = np.array([0, 0.5, 1, 1.5, 2, 3, 4, 6], dtype=F)
+
+
+def grid_e2m1(x):
+	"""the nearest of the eight E2M1 magnitudes (a midpoint goes to the lower one)"""
+	s = (np.abs(x).max(axis=1) / F(6)).astype(F)
+	safe = np.where(s > 0, s, F(1)).astype(F)
+	t = np.minimum(F(6), np.abs(x / safe[:, None]))
+	mid = (E2M1[1:] + E2M1[:-1]) / 2
+	a = E2M1[np.searchsorted(mid, t, side="left")]
+	return np.copysign(a, x) * (s > 0)[:, None], s
+
+
+QUANTIZERS = {"int8": grid_uniform(127), "int6": grid_uniform(31), "e2m3": grid_e2m3, "e2m3c": grid_e2m3_compact, "e2m1": grid_e2m1, "int4": grid_uniform(7)}
 
 
 def quantize(name, x):
-	"""x^ (float32, exact grid values), s, e >= |x - s x^|, n >= |s x^|, a >= |x|"""
+	"""x^ (float32, exact grid values), s, e >= |x - s x^|, n >= |s x^|, a >= |x|; e2m3c: e rounded up to bf16 as well"""
 	xq, s = QUANTIZERS[name](x)
 	xs = s.astype(np.float64)[:, None] * xq
 	norm = lambda t: np.sqrt(np.einsum("ij,ij->i", t, t))
-	return xq, s, up(norm(x.astype(np.float64) - xs)), up(norm(xs)), up(norm(x.astype(np.float64)))
+	e = up(norm(x.astype(np.float64) - xs))
+	return xq, s, bf16_up(e) if name == "e2m3c" else e, up(norm(xs)), up(norm(x.astype(np.float64)))
 
 
 def stored(x):
@@ -113,13 +145,15 @@ def main():
 	ap.add_argument("--threads", type=int, default=16)
 	ap.add_argument("--seed", type=int, default=3456, help="seed of the queries (bench.py draws its queries with 3456)")
 	ap.add_argument("--tail", default="", help="K[,K...]: the E2M3 bounds again under the table flat beyond K entries")
+	ap.add_argument("--quantizers", default=",".join(QUANTIZERS), help="which of " + ", ".join(QUANTIZERS))
 	ap.add_argument("--out", default=None)
 	a = ap.parse_args()
 	tails = [int(x) for x in a.tail.split(",") if x]
 	assert all(1 <= k < LEN_S for k in tails), tails
 	t0 = time.time()
 	n_chunks = (a.slices + a.chunk - 1) // a.chunk
-	names = list(QUANTIZERS)
+	names = [q for q in a.quantizers.split(",") if q]
+	assert all(q in QUANTIZERS for q in names) and (not tails or "e2m3" in names), names
 	exact = np.empty((a.queries, a.slices), dtype=F)
 	bound = {q: np.empty((a.queries, a.slices), dtype=F) for q in names}
 	bound_tail = {k: np.empty((a.queries, a.slices), dtype=F) for k in tails}
@@ -141,7 +175,7 @@ def main():
 			xq, s_x, e_x, n_x, a_x = quantize(name, X)
 			if c == 0:
 				const[name] = (F(n_x.max() * (1 + 5e-3)), F(a_x.max() * (1 + 5e-3)))
-				qq[name] = [quantize(name, q) for q in qs]
+				qq[name] = [quantize("e2m3" if name == "e2m3c" else name, q) for q in qs]   # the query's tile is the same under either layout
 			N, Xm = const[name]
 			holds = holds and bool(n_x.max() <= N and a_x.max() <= Xm)
 			P = xq @ np.concatenate([t[0] for t in qq[name]]).T          # exact in float32: see the module's text

@@ -31,6 +31,10 @@ namespace vk_host {
 //   8 bit  v_mfma_i32_16x16x64_i8             64             1,024             5      4      5,248                 320   (289 .. 304 features)
 //   8 bit                                     64             1,024             12     4      12,416                768   (753 .. 768)
 //   6 bit  v_mfma_scale_f32_16x16x128_f8f6f4  128            1,536             3      live   3,200 + 384 live      320   (289 .. 304)
+//   6 bit, compact             128            1,536; 576        3      2      3,712                 320   (289 .. 304)
+// Compact: the last K-step is part P, 32 lanes x 12 bytes -- words 0 .. 2 of quarter 0 (lanes 0 .. 15) and of quarter 1 (16 .. 31),
+// which are all of quarter 1's live words at every width up to 304 -- then part Q, 16 lanes x 12 bytes, words 3 .. 5 of quarter 0;
+// behind it 16 x (s_x, e_x) as two bf16 in one word, s_x the low half (fp6c_meta), both rounded up (quantize_row, bf16_meta).
 // The query's tile keeps every K-step whole (qtile_bytes; in LDS the cells' constants follow in VK_DEV_BOUND_CONST_BYTES, vk_device.h).
 struct shadow_format {
 	int bits = 0;            // 0: no shadow; 8: int8 codes (MODE 7); 6: E2M3 codes (MODE 8)
@@ -38,15 +42,20 @@ struct shadow_format {
 	int steps = 0, step_features = 0;
 	int live = 0, kept = 0;  // quarters of the last K-step: fetched, stored (1 .. 4)
 	int gamma_width = 0;     // the exact kernel's padded K, nk32 * 32: the d_pad of bound_cell_constants
+	int compact = 0;         // 6 bit only: the compact last K-step (parts P and Q, 576 bytes) and 64 bytes of (s, e) as bf16 pairs
 	constexpr int step_bytes() const { return step_features * bits * 2; }   // 16 rows of step_features codes
-	constexpr int meta_offset() const { return (steps - 1) * step_bytes() + kept * (step_bytes() / 4); }   // where the 16 x (s, e) sit
-	constexpr int tile_bytes() const { return meta_offset() + 128; }
+	constexpr int last_step_bytes() const { return compact ? 48 * 12 : kept * (step_bytes() / 4); }
+	constexpr int meta_offset() const { return (steps - 1) * step_bytes() + last_step_bytes(); }   // where the 16 x (s, e) sit
+	constexpr int tile_bytes() const { return meta_offset() + (compact ? 64 : 128); }
 	constexpr int qtile_bytes() const { return steps * step_bytes(); }
-	constexpr int width() const { return (steps - 1) * step_features + kept * (step_features / 4); }   // features a tile has room for
+	// features a tile has room for (compact: quarter 1 of the last K-step keeps three words, sixteen codes)
+	constexpr int width() const { return (steps - 1) * step_features + (compact ? 48 : kept * (step_features / 4)); }
+	constexpr int walk() const { return (width() + 31) / 32 * 32; }   // ... in whole lane operands of either grid: what quantize_row walks
 };
+constexpr int bits6_compact = 60;   // bits_wanted of shadow_format_of: six bits in the compact layout
 // The format of the shadow of a corpus, or none (bits = 0): contextual bf16 rows whose exact kernel is one of the two compile-time
 // forms that rescore the contenders -- nk32 = 10 with a half K-step (289 .. 304 features) or nk32 = 24 (753 .. 768).  Six bits exist
-// for the first only; asked of the second they give its 8-bit form.
+// for the first only; asked of the second they give its 8-bit form.  bits_wanted: 8, 6 or bits6_compact.
 constexpr shadow_format shadow_format_of(int d, int nk32, int tail, int prec, int layout, int bits_wanted) {
 	shadow_format f;
 	const int steps8 = (nk32 == 10 && tail == 1) ? 5 : (nk32 == 24 && tail == 0) ? 12 : 0;
@@ -55,6 +64,9 @@ constexpr shadow_format shadow_format_of(int d, int nk32, int tail, int prec, in
 	if (steps8 == 5 && bits_wanted == 6) {
 		f.bits = 6; f.steps = 3; f.step_features = 128;
 		f.live = f.kept = (d - 256 + 31) / 32;   // the quarters of 32 features that hold any: 2
+	} else if (steps8 == 5 && bits_wanted == bits6_compact) {
+		f.bits = 6; f.steps = 3; f.step_features = 128;
+		f.live = f.kept = 2; f.compact = 1;      // d <= 304: quarter 1 holds at most 16 features, three words of a lane's six
 	} else {
 		f.bits = 8; f.steps = steps8; f.step_features = 64;
 		f.live = (d - 64 * (steps8 - 1) + 15) / 16; f.kept = 4;   // the kernel steps over whole blocks
@@ -65,6 +77,10 @@ constexpr shadow_format shadow_format_of(int d, int nk32, int tail, int prec, in
 // ---- the quantizer of one row x (the bf16 values as stored, handed over as floats) on a grid of codes: s = max|x| / top, code k the
 // grid value nearest to x[k] / s; e >= |x - s x^|, n >= |s x^|, a >= |x| with s x^ the row the codes stand for (Euclidean norms,
 // summed in double in k order, then rounded UP to float: quant_up).  A row of zeros gives zeros throughout.
+// bf16_meta (the compact shadow, which stores s and e as bf16): s is the least bf16 >= max|x| / top and the codes are computed with
+// THAT s, so |x / s| <= top still holds and nothing new clips; e is the least bf16 >= quant_up(|x - s x^|); n is taken from the rows
+// s x^ as quantized with that s.  The bound of DESIGN 11.2 holds for any s > 0 and any e at least the true error: it uses s only
+// through the row s x^ that the codes stand for, and e only as an upper bound of |x - s x^|.
 struct quant_meta { float s = 0.0f, e = 0.0f, n = 0.0f, a = 0.0f; };
 // x (1 + 1e-6) as a float, then the next float up (nextafterf towards +inf; FLT_MAX and beyond give +inf)
 VK_HOST_DEVICE inline float quant_up(double x) {
@@ -72,6 +88,16 @@ VK_HOST_DEVICE inline float quant_up(double x) {
 	const float f = (float)(x * (1.0 + 1e-6));
 	if (!(f < INFINITY)) return f;
 	return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, f) + 1u);
+}
+
+// the least bf16 value >= f, as a float (f >= 0 or +inf; a NaN stays one)
+VK_HOST_DEVICE inline float bf16_up(float f) {
+	const uint32_t u = __builtin_bit_cast(uint32_t, f);
+	return __builtin_bit_cast(float, (u & 0xffffu) ? (u | 0xffffu) + 1u : u);
+}
+// 16 x (s, e) of a compact tile: one word per token, s the low half, e the high half (both bf16 values already)
+VK_HOST_DEVICE inline uint32_t fp6c_meta(float s, float e) {
+	return (__builtin_bit_cast(uint32_t, s) >> 16) | (__builtin_bit_cast(uint32_t, e) & 0xffff0000u);
 }
 
 // The int8 grid: the integers -127 .. 127, ties to even (nearbyintf).  The code is the integer; sixteen of them are a lane's operand
@@ -113,11 +139,12 @@ struct grid_e2m3 {
 
 // get(k): x[k] for k < d; put(k, code): every k < width in turn, zero codes from d on (width >= d: the features a tile has room for).
 // Walks the row a lane's operand at a time, so that a put which collects one sees a constant k % lane_codes once the loop is unrolled.
-template <typename Grid, typename Get, typename Put> VK_HOST_DEVICE inline quant_meta quantize_row(int d, int width, Get get, Put put) {
+template <typename Grid, typename Get, typename Put> VK_HOST_DEVICE inline quant_meta quantize_row(int d, int width, Get get, Put put, bool bf16_meta = false) {
 	float m = 0.0f;
 	for (int k = 0; k < d; k++) m = fmaxf(m, fabsf(get(k)));
 	quant_meta r;
 	r.s = m / Grid::top;
+	if (bf16_meta) r.s = bf16_up(r.s);
 	double e2 = 0.0, n2 = 0.0, a2 = 0.0;
 	for (int k0 = 0; k0 < width; k0 += Grid::lane_codes) {
 		VK_UNROLL
@@ -136,13 +163,14 @@ template <typename Grid, typename Get, typename Put> VK_HOST_DEVICE inline quant
 		}
 	}
 	r.e = quant_up(sqrt(e2)); r.n = quant_up(sqrt(n2)); r.a = quant_up(sqrt(a2));
+	if (bf16_meta) r.e = bf16_up(r.e);
 	return r;
 }
 inline quant_meta quantize_row_i8(const float *x, int d, int8_t *xq) {
 	return quantize_row<grid_i8>(d, d, [=](int k) { return x[k]; }, [=](int k, int code) { xq[k] = (int8_t)code; });
 }
-inline quant_meta quantize_row_e2m3(const float *x, int d, uint8_t *xq) {
-	return quantize_row<grid_e2m3>(d, d, [=](int k) { return x[k]; }, [=](int k, int code) { xq[k] = (uint8_t)code; });
+inline quant_meta quantize_row_e2m3(const float *x, int d, uint8_t *xq, bool bf16_meta = false) {
+	return quantize_row<grid_e2m3>(d, d, [=](int k) { return x[k]; }, [=](int k, int code) { xq[k] = (uint8_t)code; }, bf16_meta);
 }
 
 // ---- the order of a tile.  int8: K-step k / 64, lane 16 ((k % 64) / 16) + i, byte k % 16 of the lane's 16.
@@ -175,6 +203,26 @@ inline void fp6_put_row(uint8_t *tile, int kept, int i, const uint8_t *codes, in
 			fp6_pack32(c32, w);
 			fp6_store_lane(tile + (size_t)t * 1536, t == 2 ? kept : 4, 16 * g + i, w);
 		}
+}
+// The last K-step of a compact tile: lane 16 g + i (g = 0, 1) stores words 0 .. 2 in part P at 12 lane, quarter 0 its words 3 .. 5 in
+// part Q at 384 + 12 lane; quarter 1's words 3 .. 5 are features 304 .. 319, zero codes, and are not stored
+VK_HOST_DEVICE inline void fp6c_store_lane(uint8_t *step, int lane, const uint32_t *w) {
+	uint32_t *p = reinterpret_cast<uint32_t *>(step + (size_t)lane * 12);
+	p[0] = w[0]; p[1] = w[1]; p[2] = w[2];
+	if (lane >= 16) return;
+	uint32_t *q = reinterpret_cast<uint32_t *>(step + 384 + (size_t)lane * 12);
+	q[0] = w[3]; q[1] = w[4]; q[2] = w[5];
+}
+// one row's codes (d <= 304 of them, zeros beyond) into row i of a compact tile
+inline void fp6c_put_row(uint8_t *tile, int i, const uint8_t *codes, int d) {
+	fp6_put_row(tile, 0, i, codes, d);   // the two whole K-steps
+	uint8_t c32[32];
+	uint32_t w[6];
+	for (int g = 0; g < 2; g++) {
+		for (int j = 0; j < 32; j++) { const int k = 256 + 32 * g + j; c32[j] = k < d ? codes[k] : 0; }
+		fp6_pack32(c32, w);
+		fp6c_store_lane(tile + 2 * 1536, 16 * g + i, w);
+	}
 }
 
 // ---- the query's side.  The constants of query column j in a cell of the bound pass, ub = clip01((s_x cs) I + e_x ca + cb) (I the

@@ -267,8 +267,14 @@ __device__ __forceinline__ uint32_t fp6_lane_offset(int lane) {
 	return o16;
 }
 // one tile's operands as its six loads leave them: lo / hi per K-step, and the 16 x (s_x, e_x) behind them
-template <bool META>
-__device__ __forceinline__ void load_tile_fp6(i32x4 (&lo)[VK_DEV_FP6_STEPS], i32x2 (&hi)[VK_DEV_FP6_STEPS], f32x2 &meta, const uint8_t *__restrict__ tile, int lane, int live6, uint32_t o16) {
+// COMPACT (MODE 9, the 3,712-byte tile of DESIGN 11.11): seven loads -- the whole K-steps as before, then part P (lanes 0 .. 31, three
+// words at 12 lane), part Q (lanes 0 .. 15, three words behind P) and the token's (s_x, e_x) word, which stays packed in meta[0] until
+// the cell expands it (cell_tile_fp6).  A load of three words requests those twelve bytes only: the last lane of Q ends where the
+// (s_x, e_x) words begin, the last of those where the tile ends.  live6 is not read, lo / hi of the last K-step are not written; pq
+// (P and Q as they are loaded, one operand once the MFMA takes them) is the compact form's alone.
+typedef __attribute__((ext_vector_type(3))) int i32x3;
+template <bool META, bool COMPACT>
+__device__ __forceinline__ void load_tile_fp6(i32x4 (&lo)[VK_DEV_FP6_STEPS], i32x2 (&hi)[VK_DEV_FP6_STEPS], i32x3 (&pq)[2], f32x2 &meta, const uint8_t *__restrict__ tile, int lane, int live6, uint32_t o16) {
 	const uint32_t o8 = o16 >> 1;
 #pragma unroll
 	for (int t = 0; t < VK_DEV_FP6_STEPS - 1; t++) {
@@ -276,18 +282,39 @@ __device__ __forceinline__ void load_tile_fp6(i32x4 (&lo)[VK_DEV_FP6_STEPS], i32
 		lo[t] = __builtin_nontemporal_load(reinterpret_cast<const i32x4 *>(step + o16));
 		hi[t] = __builtin_nontemporal_load(reinterpret_cast<const i32x2 *>(step + 1024 + o8));
 	}
-	// (s_x, e_x) of the lane's token: behind the whole K-steps (in front of the tile's loads the forms take more registers) and in
-	// front of the last one's masked loads
-	if constexpr (META) meta = __builtin_nontemporal_load(reinterpret_cast<const f32x2 *>(tile + (VK_DEV_FP6_TILE_BYTES(live6) - 128) + (lane & 15) * 8));
 	constexpr int t = VK_DEV_FP6_STEPS - 1;
 	const uint8_t *step = tile + t * VK_DEV_FP6_STEP_BYTES;
-	lo[t] = i32x4{0, 0, 0, 0}; hi[t] = i32x2{0, 0};
-	if (lane < 16 * live6) {
-		lo[t] = __builtin_nontemporal_load(reinterpret_cast<const i32x4 *>(step + o16));
-		hi[t] = __builtin_nontemporal_load(reinterpret_cast<const i32x2 *>(step + live6 * 256 + o8));
+	if constexpr (COMPACT) {
+		const uint32_t o12 = o16 - (o16 >> 2);
+		if constexpr (META) {
+			meta[0] = __builtin_nontemporal_load(reinterpret_cast<const float *>(tile + VK_DEV_FP6C_META_OFFSET + (lane & 15) * 4));
+			meta[1] = 0.0f;
+		}
+		// P and Q through the tile's buffer descriptor, 3,648 bytes from its first: a lane that has nothing to fetch gets an offset
+		// beyond them, for which the range check answers zeros without a request to memory.  No branch: under a lane mask the compiler
+		// puts the two halves of the operand together where they are loaded, behind a wait for every load of the tile.
+		// (the tile's address is the same in every lane; read from the first, it is in scalar registers for the compiler too, which
+		// otherwise loops over the lanes' values around each load)
+		const uint64_t ta = reinterpret_cast<uint64_t>(tile);
+		const uint64_t tu = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ta) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(ta >> 32)) << 32;
+		const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<uint8_t *>(tu), 0, VK_DEV_FP6C_META_OFFSET, 0x00020000);
+		constexpr uint32_t last = t * VK_DEV_FP6_STEP_BYTES, none = 0x80000000u;
+		const auto P = __builtin_amdgcn_raw_buffer_load_b96(rs, lane < 32 ? last + o12 : none, 0, 2);   // aux 2: nontemporal
+		const auto Q = __builtin_amdgcn_raw_buffer_load_b96(rs, lane < 16 ? last + VK_DEV_FP6C_Q_OFFSET + o12 : none, 0, 2);
+		pq[0] = i32x3{(int)P[0], (int)P[1], (int)P[2]}; pq[1] = i32x3{(int)Q[0], (int)Q[1], (int)Q[2]};
+	} else {
+		// (s_x, e_x) of the lane's token: behind the whole K-steps (in front of the tile's loads the forms take more registers) and in
+		// front of the last one's masked loads
+		if constexpr (META) meta = __builtin_nontemporal_load(reinterpret_cast<const f32x2 *>(tile + (VK_DEV_FP6_TILE_BYTES(live6) - 128) + (lane & 15) * 8));
+		lo[t] = i32x4{0, 0, 0, 0}; hi[t] = i32x2{0, 0};
+		if (lane < 16 * live6) {
+			lo[t] = __builtin_nontemporal_load(reinterpret_cast<const i32x4 *>(step + o16));
+			hi[t] = __builtin_nontemporal_load(reinterpret_cast<const i32x2 *>(step + live6 * 256 + o8));
+		}
 	}
 }
-__device__ __forceinline__ f32x4 mma_tile_fp6(const i32x4 (&lo)[VK_DEV_FP6_STEPS], const i32x2 (&hi)[VK_DEV_FP6_STEPS], const uint8_t *__restrict__ qlds, uint32_t o16) {
+template <bool COMPACT>
+__device__ __forceinline__ f32x4 mma_tile_fp6(const i32x4 (&lo)[VK_DEV_FP6_STEPS], const i32x2 (&hi)[VK_DEV_FP6_STEPS], const i32x3 (&pq)[2], const uint8_t *__restrict__ qlds, uint32_t o16) {
 	const uint32_t o8 = o16 >> 1;
 	int one = 0x7f7f7f7f;   // E8M0 127 in every byte: x 1
 	asm volatile("" : "+v"(one));
@@ -296,22 +323,34 @@ __device__ __forceinline__ f32x4 mma_tile_fp6(const i32x4 (&lo)[VK_DEV_FP6_STEPS
 	for (int t = 0; t < VK_DEV_FP6_STEPS; t++) {
 		const uint8_t *qs = qlds + t * VK_DEV_FP6_STEP_BYTES;
 		const i32x8 q = fp6_operand(*reinterpret_cast<const i32x4 *>(qs + o16), *reinterpret_cast<const i32x2 *>(qs + 1024 + o8));
-		acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(q, fp6_operand(lo[t], hi[t]), acc, 2, 2, 0, one, 0, one);
+		i32x8 x;
+		// (P is loaded where the operand has it; Q cannot be, a register tuple starts at an even register: three moves)
+		if (COMPACT && t == VK_DEV_FP6_STEPS - 1) x = i32x8{pq[0][0], pq[0][1], pq[0][2], pq[1][0], pq[1][1], pq[1][2], 0, 0};
+		else x = fp6_operand(lo[t], hi[t]);
+		acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(q, x, acc, 2, 2, 0, one, 0, one);
 	}
 	return acc;
 }
 // the product alone (the probe of tests/test_gpu_bound6_product.py reads the MFMA's floats)
+template <bool COMPACT = false>
 __device__ __forceinline__ f32x4 dot_tile_fp6(const uint8_t *__restrict__ qlds, const uint8_t *__restrict__ tile, int lane, int live6) {
 	i32x4 lo[VK_DEV_FP6_STEPS];
 	i32x2 hi[VK_DEV_FP6_STEPS];
+	i32x3 pq[2];
 	f32x2 meta;
 	const uint32_t o16 = fp6_lane_offset(lane);
-	load_tile_fp6<false>(lo, hi, meta, tile, lane, live6, o16);
-	return mma_tile_fp6(lo, hi, qlds, o16);
+	load_tile_fp6<false, COMPACT>(lo, hi, pq, meta, tile, lane, live6, o16);
+	return mma_tile_fp6<COMPACT>(lo, hi, pq, qlds, o16);
 }
 
 // the cell is sim_tile_i8's with the MFMA's float in place of (float) I; the 16 x (s_x, e_x) follow the tile's K-steps
-__device__ __forceinline__ f32x4 cell_tile_fp6(const f32x4 acc, const f32x2 m, const uint8_t *__restrict__ qlds, int lane) {
+// COMPACT: m[0] holds s_x and e_x as two bf16, s_x the low half; either becomes its float by a shift or a mask
+template <bool COMPACT>
+__device__ __forceinline__ f32x4 cell_tile_fp6(const f32x4 acc, f32x2 m, const uint8_t *__restrict__ qlds, int lane) {
+	if constexpr (COMPACT) {
+		const uint32_t w = __builtin_bit_cast(uint32_t, m[0]);
+		m = f32x2{__builtin_bit_cast(float, w << 16), __builtin_bit_cast(float, w & 0xffff0000u)};
+	}
 	const float *cst = reinterpret_cast<const float *>(qlds + VK_DEV_FP6_QTILE_BYTES) + (lane >> 4) * 4;
 	const f32x4 cs = *reinterpret_cast<const f32x4 *>(cst), ca = *reinterpret_cast<const f32x4 *>(cst + 16), cb = *reinterpret_cast<const f32x4 *>(cst + 32);
 	f32x4 ub;
@@ -321,7 +360,7 @@ __device__ __forceinline__ f32x4 cell_tile_fp6(const f32x4 acc, const f32x2 m, c
 }
 
 // T consecutive tiles per trip of the kernel's tile loop (VK_FP6_TILES; what is left of a group goes one tile at a time): the
-// loads of all T, their (s_x, e_x) included, are issued before the first MFMA waits for any -- T times 3,968 bytes in flight per
+// loads of all T, their (s_x, e_x) included, are issued before the first MFMA waits for any -- T times 3,968 bytes (compact: 3,712) in flight per
 // wave where one tile per trip kept one.  No branch on the number of tiles in here: a join between the loads and the
 // MFMAs makes the compiler wait for every load of every tile before the first product.
 #ifndef VK_FP6_TILES
@@ -333,21 +372,25 @@ __device__ __forceinline__ f32x4 cell_tile_fp6(const f32x4 acc, const f32x2 m, c
 #ifndef VK_FP6_TILES_TAIL64
 #define VK_FP6_TILES_TAIL64 1   // ... of the flat-tailed 64-row form (GAP 9)
 #endif
-template <int T>
+template <int T, bool COMPACT>
 __device__ __forceinline__ void sim_tiles_fp6(f32x4 (&ub)[T], const uint8_t *__restrict__ qlds, const uint8_t *__restrict__ tile, int tile_bytes, int lane, int live6) {
 	i32x4 lo[T][VK_DEV_FP6_STEPS];
 	i32x2 hi[T][VK_DEV_FP6_STEPS];
+	i32x3 pq[T][2];
 	f32x2 meta[T];
 	const uint32_t o16 = fp6_lane_offset(lane);
 #pragma unroll
-	for (int i = 0; i < T; i++) load_tile_fp6<true>(lo[i], hi[i], meta[i], tile + (int64_t)i * tile_bytes, lane, live6, o16);
+	for (int i = 0; i < T; i++) load_tile_fp6<true, COMPACT>(lo[i], hi[i], pq[i], meta[i], tile + (int64_t)i * tile_bytes, lane, live6, o16);
 	if constexpr (T > 1) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
 	for (int i = 0; i < T; i++) {
-		ub[i] = cell_tile_fp6(mma_tile_fp6(lo[i], hi[i], qlds, o16), meta[i], qlds, lane);
+		ub[i] = cell_tile_fp6<COMPACT>(mma_tile_fp6<COMPACT>(lo[i], hi[i], pq[i], qlds, o16), meta[i], qlds, lane);
 		// the cells are taken as used HERE: the caller stores them under a lane guard, and whatever only that store reads the
 		// compiler sinks into the guarded block -- the last tile's (s_x, e_x) load went there, behind the first wait
 		asm volatile("" : "+v"(ub[i]));
+		// compact: the next tile's Q reaches its operand by three moves, which the scheduler otherwise hoists in front of this
+		// tile's last MFMA -- with a wait for every load of both tiles
+		if constexpr (COMPACT && T > 1) __builtin_amdgcn_sched_barrier(0);
 	}
 }
 

@@ -633,7 +633,8 @@ int vk_bound_pass_state(vk_corpus_t *c, float *bounds, int64_t n, int64_t *count
 	return VK_OK;
 }
 
-// Internal (tests; not part of the ABI): the format of the handle's shadow -- 0 none, 8 int8 (MODE 7), 6 E2M3 (MODE 8) -- which is
+// Internal (tests; not part of the ABI): the format of the handle's shadow -- 0 none, 8 int8 (MODE 7), 6 E2M3 (MODE 8, or MODE 9 where
+// vk_bound_pass_shadow reports tiles of 3,712 bytes) -- which is
 // the format of every bound pass vk_bound_pass_state reports on
 int vk_bound_pass_bits(vk_corpus_t *c, int64_t *bits) {
 	if (!c || !bits) return fail(VK_ERR_INVALID, "null argument");
@@ -742,6 +743,29 @@ int vk_fp6_bound_tile_probe(const uint8_t *q, const uint8_t *x, int32_t live6, f
 	VK_HIP(vk_launch_fp6_bound_probe(d, d + xoff, live6, (float *)(d + ooff), nullptr));
 	VK_HIP(hipDeviceSynchronize());
 	VK_HIP(hipMemcpy(out, d + ooff, 1024, hipMemcpyDeviceToHost));
+	return VK_OK;
+}
+
+// Internal (tests): the same through MODE 9's loads (dot_tile_fp6<true>).  The token tile is packed compact (vk_host::fp6c_put_row:
+// x's codes at features >= d are left out, d <= 304) and every byte of the buffer behind the tile's 3,712 is `fill`: a lane that read
+// past the tile would carry it into the product
+int vk_fp6c_bound_tile_probe(const uint8_t *q, const uint8_t *x, int32_t d, int32_t fill, float *out) {
+	if (!q || !x || !out) return fail(VK_ERR_INVALID, "null argument");
+	if (d < 0 || d > 304) return fail(VK_ERR_INVALID, "d is 0 .. 304");
+	const size_t xoff = VK_DEV_FP6_QTILE_BYTES, ooff = xoff + 5120;
+	vk_devbuf<uint8_t> buf;
+	if (int rc = buf.reserve(ooff + 1024, nullptr)) return rc;
+	uint8_t *dv = buf;
+	std::vector<uint8_t> pk(ooff, 0);
+	for (int i = 0; i < 16; i++) {
+		vk_host::fp6_put_row(pk.data(), 4, i, q + (size_t)i * 384, 384);
+		vk_host::fp6c_put_row(pk.data() + xoff, i, x + (size_t)i * 384, d);
+	}
+	memset(pk.data() + xoff + VK_DEV_FP6C_TILE_BYTES, fill, 5120 - VK_DEV_FP6C_TILE_BYTES);
+	VK_HIP(hipMemcpy(dv, pk.data(), ooff, hipMemcpyHostToDevice));
+	VK_HIP(vk_launch_fp6c_bound_probe(dv, dv + xoff, (float *)(dv + ooff), nullptr));
+	VK_HIP(hipDeviceSynchronize());
+	VK_HIP(hipMemcpy(out, dv + ooff, 1024, hipMemcpyDeviceToHost));
 	return VK_OK;
 }
 

@@ -29,6 +29,12 @@
 #define VK_DEV_FP6_QTILE_BYTES (VK_DEV_FP6_STEPS * VK_DEV_FP6_STEP_BYTES)   // the query tile: every K-step whole
 // bytes of a corpus tile with live6 quarters in its last K-step: the K-steps, then 16 x (s_x, e_x)
 #define VK_DEV_FP6_TILE_BYTES(live6) ((VK_DEV_FP6_STEPS - 1) * VK_DEV_FP6_STEP_BYTES + 384 * (live6) + 128)
+// MODE 9, the compact 6-bit shadow of 289 .. 304 features: the whole K-steps as MODE 8's; the last one is part P (32
+// lanes x 12 bytes: words 0 .. 2 of quarters 0 and 1) and part Q (16 lanes x 12 bytes: words 3 .. 5 of quarter 0); then 16 words of
+// (s_x, e_x) as two bf16, s_x the low half
+#define VK_DEV_FP6C_Q_OFFSET 384       // part Q within the last K-step
+#define VK_DEV_FP6C_META_OFFSET ((VK_DEV_FP6_STEPS - 1) * VK_DEV_FP6_STEP_BYTES + 576)
+#define VK_DEV_FP6C_TILE_BYTES (VK_DEV_FP6C_META_OFFSET + 64)   // 3,712: 29 lines of 128 bytes
 
 // The bound pass under general gaps may score under a slice-gap table that is flat beyond this many entries (GAP 8 / 9 of
 // vk_score_kernel).  A unit that instantiates those forms reports the K it was compiled with (vk_score_m8t_tail_k,
@@ -98,6 +104,8 @@ struct VkScoreParams {
 	int32_t h_rows;            // general gap: history rows per sentence (max_len + 1)
 	int32_t m_rows;            // GAP 7, static layout: floats per sentence of the mass scratch (after the S strip)
 	float bound_tail_cost;     // gap_mode 8 / 9: the cost of every gap over more than K slice tokens (vk_host::bound_tail_cost)
+	int32_t bound_compact;     // bound_bits 6: 1 = the compact layout (MODE 9: tile_bytes = VK_DEV_FP6C_TILE_BYTES, bound_live 2); the
+	                           // dispatch reads it, no kernel does (last: the kernels' argument offsets are what they were)
 };
 
 struct VkRwmdBatchParams {
@@ -389,6 +397,8 @@ hipError_t vk_launch_i8_bound_probe(const uint8_t *qtile8, const uint8_t *tile8,
 hipError_t vk_launch_i8_probe(const int8_t *q, const int8_t *x, int32_t *out, hipStream_t stream);
 // one 6-bit query tile (VK_DEV_FP6_QTILE_BYTES) against one shadow tile through dot_tile_fp6: out[16 j + i] (vk_pack.hip; tests)
 hipError_t vk_launch_fp6_bound_probe(const uint8_t *qtile6, const uint8_t *tile6, int32_t live6, float *out, hipStream_t stream);
+// the same against one compact tile (VK_DEV_FP6C_TILE_BYTES) through dot_tile_fp6<true>
+hipError_t vk_launch_fp6c_bound_probe(const uint8_t *qtile6, const uint8_t *tile6c, float *out, hipStream_t stream);
 // rows of the keys (up to the first empty slot of `n`) as groups of four rows of the slice table (vk_score_kernel's group_list)
 // theta on the device: the score of *theta_key (floor_excl when that slot is empty)
 hipError_t vk_launch_select_ge_key(const float *scores, int64_t n, const uint64_t *theta_key, float floor_excl, uint64_t *keys_out,

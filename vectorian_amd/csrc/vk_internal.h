@@ -72,15 +72,18 @@ inline int bound_pass_mode() {
 	const char *e = getenv("VK_BOUND_PASS");
 	return !e ? 0 : !strcmp(e, "off") ? -1 : !strcmp(e, "force") ? 1 : 0;
 }
-// VK_BOUND_BITS, read at finalize: which shadow a corpus of 289 .. 304 features gets -- "8" the int8 one, "6" the E2M3 one.
+// VK_BOUND_BITS, read at finalize: which shadow a corpus of 289 .. 304 features gets -- "8" the int8 one, "6" the E2M3 one in
+// 3,968-byte tiles, "6c" the E2M3 one in compact 3,712-byte tiles.
 // Unset: 8 under VK_BOUND_PASS=force (the sizes below a million slices have been measured with 8 only, and the tests of the 8-bit
-// pass run under force), 6 where the pass is switched on by size (profiles/bound_fp6_ab.json: - 8.9 % per query at 1 M slices).
-// 753 .. 768 features: always 8.  A corpus carries one shadow.
+// pass run under force), 6c where the pass is switched on by size (profiles/bound_fp6_ab.json: - 8.9 % per query at 1 M slices for
+// six bits, profiles/bound_compact_ab.json: a further - 4.6 % for the compact tiles).
+// 753 .. 768 features: always 8.  A corpus carries one shadow.  The value is the bits_wanted of vk_host::shadow_format_of.
 inline int bound_bits_wanted(int mode) {
 	const char *e = getenv("VK_BOUND_BITS");
+	if (e && !strcmp(e, "6c")) return vk_host::bits6_compact;
 	if (e && !strcmp(e, "6")) return 6;
 	if (e && !strcmp(e, "8")) return 8;
-	return mode > 0 ? 8 : 6;
+	return mode > 0 ? 8 : vk_host::bits6_compact;
 }
 // VK_BOUND_TAIL, read per query: whether the bound pass of a query with general gaps scores under the flat-tailed slice-gap table
 // (vk_host::bound_tail_choice, by the same rule: the default is on where the pass is switched on by size)

@@ -116,6 +116,10 @@ template <> struct lane_operand<vk_host::grid_e2m3> {
 		vk_host::fp6_pack32(codes, w);
 		const int t = k >> 7, quarters = t == f.steps - 1 ? f.kept : 4, lane = 16 * ((k & 127) >> 5) + i;
 		uint8_t *step = dst + t * f.step_bytes();
+		if (f.compact && t == f.steps - 1) {   // parts P and Q (quarters 0 and 1: the walk ends at 320 features)
+			vk_host::fp6c_store_lane(step, lane, w);
+			return;
+		}
 		*reinterpret_cast<uint4 *>(step + lane * 16) = uint4{w[0], w[1], w[2], w[3]};
 		*reinterpret_cast<uint2 *>(step + quarters * 256 + lane * 8) = uint2{w[4], w[5]};
 	}
@@ -132,14 +136,15 @@ __global__ __launch_bounds__(256) void vk_shadow_kernel(const uint8_t *__restric
 	const int dk = row < rows_total ? f.d : 0;   // rows past the corpus (the tile's padding, the zero tile): zeros
 	bool bad = false;
 	lane_operand<Grid> op;
-	const vk_host::quant_meta m = vk_host::quantize_row<Grid>(dk, f.width(),
+	const vk_host::quant_meta m = vk_host::quantize_row<Grid>(dk, f.walk(),
 		[&](int k) {
 			const float x = tile_elem(src, i, k, 0);
 			bad = bad || !(fabsf(x) <= 3.4028234e38f);
 			return x;
 		},
-		[&](int k, int code) { op.put(f, dst, i, k, code); });
-	*reinterpret_cast<float2 *>(dst + f.meta_offset() + i * 8) = float2{m.s, m.e};
+		[&](int k, int code) { op.put(f, dst, i, k, code); }, f.compact != 0);
+	if (f.compact) *reinterpret_cast<uint32_t *>(dst + f.meta_offset() + i * 4) = vk_host::fp6c_meta(m.s, m.e);
+	else *reinterpret_cast<float2 *>(dst + f.meta_offset() + i * 8) = float2{m.s, m.e};
 	if (bad) atomicOr(stats + 2, 1u);
 	else {
 		atomicMax(stats + 0, __builtin_bit_cast(uint32_t, m.n));
@@ -155,6 +160,14 @@ constexpr bool fmt6_is_the_devices(int d, int live) {
 }
 static_assert(fmt6_is_the_devices(257, 1) && fmt6_is_the_devices(289, 2) && fmt6_is_the_devices(304, 2) && fmt6_is_the_devices(321, 3) && fmt6_is_the_devices(384, 4),
 	"vk_host::shadow_format and VK_DEV_FP6_*");
+// ... and so is its description of the compact form
+constexpr vk_host::shadow_format fmt6c_of(int d) { return vk_host::shadow_format_of(d, 10, 1, 0, VK_LAYOUT_CONTEXTUAL, vk_host::bits6_compact); }
+constexpr bool fmt6c_is_the_devices(int d) {
+	return fmt6c_of(d).compact == 1 && fmt6c_of(d).bits == 6 && fmt6c_of(d).live == 2 && fmt6c_of(d).steps == VK_DEV_FP6_STEPS && fmt6c_of(d).step_bytes() == VK_DEV_FP6_STEP_BYTES
+		&& fmt6c_of(d).meta_offset() == VK_DEV_FP6C_META_OFFSET && fmt6c_of(d).tile_bytes() == VK_DEV_FP6C_TILE_BYTES && fmt6c_of(d).qtile_bytes() == VK_DEV_FP6_QTILE_BYTES
+		&& fmt6c_of(d).width() == 304 && fmt6c_of(d).walk() == 320;
+}
+static_assert(fmt6c_is_the_devices(289) && fmt6c_is_the_devices(300) && fmt6c_is_the_devices(304), "vk_host::shadow_format and VK_DEV_FP6C_*");
 
 extern "C" hipError_t vk_launch_shadow(const uint8_t *tiles, int64_t n_tiles, int64_t rows_total, int32_t tile_bytes, const vk_host::shadow_format *f,
 	uint8_t *shadow, uint32_t *stats, hipStream_t stream) {
@@ -205,18 +218,24 @@ extern "C" hipError_t vk_launch_i8_bound_probe(const uint8_t *qtile8, const uint
 
 // One 6-bit shadow tile against one 6-bit query tile, both packed already, through the bound kernel's own product: the query tile
 // staged in LDS as MODE 8 stages it, dot_tile_fp6 with `live6` quarters in the tile's last K-step (tests/test_gpu_bound6_product.py)
+// COMPACT: the tile is a compact one (MODE 9's loads, tests/test_gpu_bound_compact_product.py); live6 is not read
+template <bool COMPACT>
 __global__ __launch_bounds__(64) void vk_fp6_bound_probe_kernel(const uint8_t *__restrict__ qtile6, const uint8_t *__restrict__ tile6, int32_t live6,
 	float *__restrict__ out) {
 	__shared__ float4 qlds4[VK_DEV_FP6_QTILE_BYTES / 16];
 	const int lane = threadIdx.x;
 	for (int i = lane; i < VK_DEV_FP6_QTILE_BYTES / 16; i += 64) qlds4[i] = *reinterpret_cast<const float4 *>(qtile6 + i * 16);
 	__syncthreads();
-	const f32x4 acc = dot_tile_fp6(reinterpret_cast<const uint8_t *>(qlds4), tile6, lane, live6);
+	const f32x4 acc = dot_tile_fp6<COMPACT>(reinterpret_cast<const uint8_t *>(qlds4), tile6, lane, live6);
 	for (int r = 0; r < 4; r++) out[(4 * (lane >> 4) + r) * 16 + (lane & 15)] = acc[r];
+}
+extern "C" hipError_t vk_launch_fp6c_bound_probe(const uint8_t *qtile6, const uint8_t *tile6c, float *out, hipStream_t stream) {
+	vk_fp6_bound_probe_kernel<true><<<1, 64, 0, stream>>>(qtile6, tile6c, 2, out);
+	return hipGetLastError();
 }
 extern "C" hipError_t vk_launch_fp6_bound_probe(const uint8_t *qtile6, const uint8_t *tile6, int32_t live6, float *out, hipStream_t stream) {
 	if (live6 < 1 || live6 > 4) return hipErrorInvalidValue;
-	vk_fp6_bound_probe_kernel<<<1, 64, 0, stream>>>(qtile6, tile6, live6, out);
+	vk_fp6_bound_probe_kernel<false><<<1, 64, 0, stream>>>(qtile6, tile6, live6, out);
 	return hipGetLastError();
 }
 

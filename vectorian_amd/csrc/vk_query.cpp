@@ -218,7 +218,7 @@ static int score_bounded(vk_corpus *c, const VkScoreParams &p, int grid, size_t 
 	if ((rc = c->d_counter.reserve(4, &c->device_bytes))) return rc;
 	VkScoreParams pb = p;
 	const vk_host::shadow_format &sf = c->shadow_format;
-	pb.tiles = c->shadow; pb.nk32 = sf.steps; pb.tail = 0; pb.tile_bytes = sf.tile_bytes(); pb.bound_bits = sf.bits; pb.bound_live = sf.live;
+	pb.tiles = c->shadow; pb.nk32 = sf.steps; pb.tail = 0; pb.tile_bytes = sf.tile_bytes(); pb.bound_bits = sf.bits; pb.bound_live = sf.live; pb.bound_compact = sf.compact;
 	pb.q_mode3 = 0; pb.q_lds = 0; pb.qtile = c->d_qtile8; pb.scores = c->d_ub; pb.raw = nullptr;
 	b.tail_k = 0;
 	if (tail && (p.gap_mode == 3 || p.gap_mode == 6)) {

@@ -10,10 +10,12 @@ extern "C" hipError_t vk_launch_score_m3(const VkScoreParams *p, int32_t grid, s
 extern "C" hipError_t vk_launch_score_m3_300(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
 extern "C" hipError_t vk_launch_score_m7(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
 extern "C" hipError_t vk_launch_score_m8(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
+extern "C" hipError_t vk_launch_score_m9(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
 extern "C" hipError_t vk_launch_score_m4(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
 
 extern "C" hipError_t vk_launch_score(const VkScoreParams *pp, int32_t grid, size_t smem_bytes, hipStream_t stream) {
 	const VkScoreParams &p = *pp;
+	if (p.bound_bits == 6 && p.bound_compact) return vk_launch_score_m9(pp, grid, smem_bytes, stream);   // ... over the compact 6-bit shadow
 	if (p.bound_bits == 6) return vk_launch_score_m8(pp, grid, smem_bytes, stream);   // ... over the 6-bit shadow
 	if (p.bound_bits == 8) return vk_launch_score_m7(pp, grid, smem_bytes, stream);   // the bound pass over the 8-bit shadow
 	if (p.layout == VK_DEV_LAYOUT_STATIC) return vk_launch_score_m2(pp, grid, smem_bytes, stream);

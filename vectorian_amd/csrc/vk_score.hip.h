@@ -18,6 +18,7 @@
 //   MODE 7: the 8-bit shadow of a contextual bf16 corpus, NK32 K-steps of 64 int8 (here NK32 counts those): every cell an upper bound of
 //           the cosine MODE 0 / 3 compute, so the score is an upper bound of theirs (the bound pass)
 //   MODE 8: the 6-bit (E2M3) shadow, three K-steps of 128 features (NK32 = 3): as MODE 7, the product on the scaled fp6 MFMA
+//   MODE 9: MODE 8 over the compact 6-bit shadow (3,712-byte tiles): the tile's loads differ, nothing else does
 // GAP: 0 linear, 1 affine, 2 general (LDS history, serial in-row chain),
 //      3 general, sentences <= 32 tokens, strictly subadditive w_t (register history),
 //      4 relaxed word mover's distance (no DP: row / column minima of 1 - S),
@@ -59,8 +60,8 @@ __global__ __launch_bounds__(256) VK_SCORE_KERNEL_ATTR void vk_score_kernel(VkSc
 		__syncthreads();
 		smem += NK32 * 256 + VK_DEV_BOUND_CONST_BYTES / 4;
 	}
-	// MODE 8: the 6-bit query tile (every K-step whole) and the same constants behind it
-	if constexpr (MODE == 8) {
+	// MODE 8 / 9: the 6-bit query tile (every K-step whole) and the same constants behind it
+	if constexpr (MODE == 8 || MODE == 9) {
 		for (int i = threadIdx.x; i < VK_DEV_FP6_QTILE_BYTES / 16 + 12; i += blockDim.x)
 			vk_smem4[i] = *reinterpret_cast<const float4 *>(p.qtile + i * 16);
 		__syncthreads();
@@ -93,7 +94,7 @@ __global__ __launch_bounds__(256) VK_SCORE_KERNEL_ATTR void vk_score_kernel(VkSc
 	// tag-weighted modifier: this lane's four query columns (MFMA layout: 4*(lane>>4) + r)
 	// the bound pass is never taken with tag weights (bound_wanted in vk_route_host.h; the launchers of MODE 7 / 8 refuse pos_s):
 	// its kernels do not carry the lane's eight modifier registers through their loops
-	constexpr bool TAGS = MODE != 7 && MODE != 8;
+	constexpr bool TAGS = MODE != 7 && MODE != 8 && MODE != 9;
 	float twl[4] = {1.0f, 1.0f, 1.0f, 1.0f};
 	int tposl[4] = {0, 0, 0, 0};
 	if (TAGS && p.pos_s) {
@@ -105,7 +106,7 @@ __global__ __launch_bounds__(256) VK_SCORE_KERNEL_ATTR void vk_score_kernel(VkSc
 	// general gap, fast form: gap tables in (scalar) registers for the whole kernel
 	// (the flat-tailed forms: w_s[0 .. K] and the tail's cost, which comes by value)
 	constexpr bool FLAT = GAP == 8 || GAP == 9;
-	static_assert(!FLAT || MODE == 7 || MODE == 8, "a flat-tailed table gives a bound, not a score");
+	static_assert(!FLAT || MODE == 7 || MODE == 8 || MODE == 9, "a flat-tailed table gives a bound, not a score");
 	constexpr int WSN = FLAT ? VK_BOUND_TAIL_K + 2 : GAP == 6 ? 65 : 33;
 	float wsr[WSN], wtr[LT];
 	if (GAP == 3 || GAP == 6 || FLAT) {
@@ -194,7 +195,7 @@ __global__ __launch_bounds__(256) VK_SCORE_KERNEL_ATTR void vk_score_kernel(VkSc
 				tp += p.tile_bytes;
 			}
 			if (ntiles > 0) { prev_tile = tile0 + ntiles - 1; prev_row = ntiles - 1; }
-			if constexpr (MODE == 8) {
+			if constexpr (MODE == 8 || MODE == 9) {
 				// VK_FP6_TILES tiles per trip while the group has that many left, all their loads ahead of the first MFMA; then what
 				// is left (fewer than T; with ti0 = 1 a group may have no tile at all) one tile per trip.  Both bounds are
 				// wave-uniform: a tile past the group's last is neither loaded nor written to the strip
@@ -205,7 +206,7 @@ __global__ __launch_bounds__(256) VK_SCORE_KERNEL_ATTR void vk_score_kernel(VkSc
 				const auto tiles = [&](auto tc, int ti) {
 					constexpr int N = decltype(tc)::value;
 					f32x4 ub[N];
-					sim_tiles_fp6<N>(ub, qlds, tp, p.tile_bytes, lane, p.bound_live);
+					sim_tiles_fp6<N, MODE == 9>(ub, qlds, tp, p.tile_bytes, lane, p.bound_live);
 #pragma unroll
 					for (int i = 0; i < N; i++)
 						if ((lane >> 4) * 4 < LT) *reinterpret_cast<f32x4 *>(S + ((ti + i) * 16 + (lane & 15)) * LT + (lane >> 4) * 4) = ub[i];
