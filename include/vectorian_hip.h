@@ -268,6 +268,21 @@ int vk_corpus_filter(vk_corpus_t *src, uint64_t pos_mask, uint64_t tag_mask, vk_
 enum { VK_SIMOP_BIAS = 0, VK_SIMOP_SCALE = 1, VK_SIMOP_THRESHOLD = 2,
        VK_SIMOP_ONE_MINUS = 3, VK_SIMOP_POWER = 4, VK_SIMOP_RADIAL_BASIS = 5 };
 int vk_corpus_set_sim_ops(vk_corpus_t *c, const int32_t *kinds, const float *args, int32_t n_ops);
+/* The VectorSim the operator chain runs on (the `source` of a ModifiedVectorSim, or the similarity itself), VK_LAYOUT_STATIC only:
+ *   VK_SIMSRC_COSINE (every handle's, arg ignored): the cosine of the normalised rows;
+ *   VK_SIMSRC_PNORM, arg p (finite, > 0): (sum_k |a_k - b_k|^p)^(1/p) (PNormDistance, vectorian/sim/vector.py:135-160) -- a DISTANCE:
+ *     give it a chain that ends in a similarity (SCALE, ONE_MINUS; RADIAL_BASIS);
+ *   VK_SIMSRC_SQRT_COSINE (arg ignored): sum_k sqrt(max(0, a_k b_k)) / (sqrt(sum |a_k|) sqrt(sum |b_k|)), 0 where that is not finite
+ *     (ImprovedSqrtCosineSim, vector.py:98-132).
+ * Both run on the UNMODIFIED fp32 vectors (bf16 rows widened exactly): the rows as vk_corpus_append_vectors receives them, of which
+ * a handle with such a source keeps a second copy (counted by vk_corpus_device_bytes), and vk_query_desc.q_vectors as given
+ * (q_normalize keeps its meaning for the cosine only).  The arithmetic of a cell is stated in csrc/vk_sim_src_host.h; the chain, then
+ * sim[id(t_j)][j] = 1, then the clip follow as above.  Views and filtered corpora share the copy and inherit the source.
+ * VK_ERR_INVALID: null handle, unknown kind, p not finite or <= 0.  VK_ERR_UNSUPPORTED: VK_LAYOUT_CONTEXTUAL; rows of more than 1024
+ * features.  VK_ERR_STATE: a source other than the cosine after the first vk_corpus_append_vectors on a handle that keeps no copy
+ * of the rows (they are gone by then).  VK_SIMSRC_COSINE is accepted at any time. */
+enum { VK_SIMSRC_COSINE = 0, VK_SIMSRC_PNORM = 1, VK_SIMSRC_SQRT_COSINE = 2 };
+int vk_corpus_set_sim_source(vk_corpus_t *c, int32_t kind, float arg);
 int vk_corpus_free(vk_corpus_t *c);
 int vk_corpus_device_bytes(const vk_corpus_t *c, int64_t *bytes);
 

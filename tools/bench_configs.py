@@ -39,6 +39,9 @@ def main():
 	ap.add_argument("--filter", type=float, default=0.0, help="share of tokens a pos_filter drops: times vk_corpus_filter, then queries the filtered corpus")
 	ap.add_argument("--sim-ops", type=int, default=0, help="static layout: after the plain run, the same queries under a chain of this many operators "
 		"on the cosine (vk_corpus_set_sim_ops; Bias / Scale in turn), reported beside it as phases_ms_mean_sim_ops")
+	ap.add_argument("--sim-source", action="append", default=[], metavar="KIND[:ARG]", help="static layout, may be repeated: after the plain run, the same "
+		"queries under this source (vk_corpus_set_sim_source) -- pnorm:P under Scale(s), DistanceToSimilarity with the median cell at one half, "
+		"sqrt-cosine bare -- reported beside the cosine as sim_sources: prepare_ms and the whole query's wall time, each query's")
 	args = ap.parse_args()
 
 	import torch
@@ -56,7 +59,14 @@ def main():
 	if args.layout == "static":
 		# the reference's static-embedding layout: token ids + vocabulary table, per-query [V x |q|] table
 		corpus = core.Corpus(layout=core.VK_LAYOUT_STATIC, d=args.d, n_tokens=n_tok, n_sentences=args.sentences, vocab_size=V)
+		sources = []
+		for text in args.sim_source:
+			kind, _, arg = text.partition(":")
+			sources.append((text, {"pnorm": core.VK_SIMSRC_PNORM, "sqrt-cosine": core.VK_SIMSRC_SQRT_COSINE}[kind], float(arg or 0)))
+		if sources:   # the handle keeps the unmodified rows from its first append on, then goes back to the cosine for the plain run
+			corpus.set_sim_source(sources[0][1], sources[0][2])
 		corpus.append_vectors(E, normalize=True)
+		corpus.set_sim_source(core.VK_SIMSRC_COSINE)
 		corpus.set_token_ids(ids)
 		corpus.set_sentences(off)
 		corpus.finalize()
@@ -89,6 +99,30 @@ def main():
 			corpus.set_sim_ops([(core.VK_SIMOP_BIAS, 0.5) if i % 2 == 0 else (core.VK_SIMOP_SCALE, 0.5) for i in range(args.sim_ops)])
 			ph_ops, _ = timed()
 			corpus.set_sim_ops([])
+		by_source = {}
+		if sources:
+			def each():
+				"""prepare_ms and wall time of every query after the warm-up"""
+				out = []
+				for i in range(args.warmup + args.steps):
+					q = qs[i]
+					torch.cuda.synchronize()
+					t0 = time.perf_counter()
+					corpus.query(q[0], q_token_ids=q[1], algorithm=alg, locality=loc, gap_s=gap, gap_t=gap, max_matches=args.k, want_flow=args.alg == "align")
+					ms = (time.perf_counter() - t0) * 1e3
+					if i >= args.warmup:
+						out.append((corpus.last_timings()["prepare_ms"], ms))
+				return {"prepare_ms_each": [a for a, _ in out], "query_ms_each": [b for _, b in out]}
+			by_source["cosine"] = each()
+			sample = E[rng.integers(0, V, size=256)]
+			for text, kind, arg in sources:
+				corpus.set_sim_source(kind, arg)
+				if kind == core.VK_SIMSRC_PNORM:
+					dist = (np.abs(sample[:128, None] - sample[None, 128:]) ** arg).sum(-1) ** (1 / arg)
+					corpus.set_sim_ops([(core.VK_SIMOP_SCALE, 1 / (2 * float(np.median(dist)))), (core.VK_SIMOP_ONE_MINUS, 0.0)])
+				by_source[text] = each()
+				corpus.set_sim_ops([])
+			corpus.set_sim_source(core.VK_SIMSRC_COSINE)
 		score_ms = float(np.mean([p["score_ms"] for p in ph]))
 		cells = float(n_tok) * args.len_t
 		print(json.dumps({"layout": "static", "alg": args.alg, "gap": args.gap, "d": args.d, "len_t": args.len_t, "len_s": [args.min_len, args.max_len],
@@ -97,7 +131,8 @@ def main():
 			"token_id_GBps": n_tok * 4 / (score_ms * 1e-3) / 1e9,
 			"phases_ms_mean": {k: float(np.mean([p[k] for p in ph])) for k in ph[0]},
 			**({"sim_ops": args.sim_ops, "phases_ms_mean_sim_ops": {k: float(np.mean([p[k] for p in ph_ops])) for k in ph_ops[0]},
-				"prepare_ms_each": [p["prepare_ms"] for p in ph], "prepare_ms_each_sim_ops": [p["prepare_ms"] for p in ph_ops]} if ph_ops else {})}))
+				"prepare_ms_each": [p["prepare_ms"] for p in ph], "prepare_ms_each_sim_ops": [p["prepare_ms"] for p in ph_ops]} if ph_ops else {}),
+			**({"sim_sources": by_source} if by_source else {})}))
 		corpus.close()
 		return
 	corpus = core.Corpus(layout=core.VK_LAYOUT_CONTEXTUAL, d=args.d, n_tokens=n_tok, n_sentences=args.sentences,

@@ -1,4 +1,4 @@
-"""Generates tests/golden/*.npz from the reference's own Python similarity code.
+"""Generates tests/golden/*.npz from the reference's own Python similarity code: `python tools/make_goldens.py [cosine | vector_sims | all]`.
 
 Runs ONLY in the build container (needs /root/reference).  The reference package
 cannot be imported as a whole (gensim/h5py/spacy absent), so the
@@ -44,8 +44,41 @@ def load_reference():
 	return vectors, vector
 
 
+def vector_sims(vectors, vector):
+	"""tests/golden/vector_sims_reference.npz: inputs and outputs of PNormDistance(p) and ImprovedSqrtCosineSim (a generator of its
+	own: cosine_reference.npz keeps its bytes)"""
+	rng = np.random.default_rng(20261020)
+	cases = {}
+	for name, (n, m, d) in {"small": (7, 5, 300), "wide": (33, 10, 768), "tiny": (3, 2, 8)}.items():
+		a = rng.standard_normal((n, d)).astype(np.float32)
+		b = rng.standard_normal((m, d)).astype(np.float32)
+		if name == "small":
+			b = (a[:m] + 0.6 * rng.standard_normal((m, d))).astype(np.float32)
+			b[0] = a[0]   # equal rows: distance 0
+		if name == "tiny":
+			a[1] = 0.0    # a zero row: the sqrt-cosine's 0 / 0 -> NaN -> 0
+		va, vb = vectors.Vectors(a), vectors.Vectors(b)
+		cases[name + "_a"], cases[name + "_b"] = a, b
+		for p in (0.5, 1, 2, 3):
+			out = np.zeros((n, m), dtype=np.float32)
+			vector.PNormDistance(p)(va, vb, out)
+			cases[f"{name}_pnorm_{p}"] = out
+		out = np.zeros((n, m), dtype=np.float32)
+		vector.ImprovedSqrtCosineSim()(va, vb, out)
+		cases[name + "_sqrt_cosine"] = out
+	path = os.path.join(OUT, "vector_sims_reference.npz")
+	np.savez_compressed(path, **cases)
+	print("wrote", path, {k: v.shape for k, v in cases.items()})
+
+
 def main():
 	vectors, vector = load_reference()
+	os.makedirs(OUT, exist_ok=True)
+	which = sys.argv[1] if len(sys.argv) > 1 else "all"   # "cosine", "vector_sims" or "all" (an .npz carries its time of writing)
+	if which in ("vector_sims", "all"):
+		vector_sims(vectors, vector)
+	if which == "vector_sims":
+		return
 	rng = np.random.default_rng(20261003)
 	os.makedirs(OUT, exist_ok=True)
 

@@ -35,6 +35,8 @@ VK_ERR_ABORTED = 6
 # the operators of a chain on the cosine (vk_corpus_set_sim_ops; vectorian_amd/kernel.py states each one)
 VK_MAX_SIM_OPS = 8
 VK_SIMOP_BIAS, VK_SIMOP_SCALE, VK_SIMOP_THRESHOLD, VK_SIMOP_ONE_MINUS, VK_SIMOP_POWER, VK_SIMOP_RADIAL_BASIS = 0, 1, 2, 3, 4, 5
+# the VectorSim a chain runs on (vk_corpus_set_sim_source; vectorian_amd/sim.py states each one)
+VK_SIMSRC_COSINE, VK_SIMSRC_PNORM, VK_SIMSRC_SQRT_COSINE = 0, 1, 2
 
 
 class Locality(enum.IntEnum):
@@ -96,7 +98,7 @@ class _Timings(C.Structure):
 
 EXPORTS = [
 	"vk_abi_version", "vk_last_error", "vk_init", "vk_device_count", "vk_corpus_view",
-	"vk_corpus_create", "vk_corpus_append_vectors", "vk_corpus_set_token_ids", "vk_corpus_set_token_pos", "vk_corpus_set_token_tags", "vk_corpus_filter", "vk_corpus_set_sim_ops",
+	"vk_corpus_create", "vk_corpus_append_vectors", "vk_corpus_set_token_ids", "vk_corpus_set_token_pos", "vk_corpus_set_token_tags", "vk_corpus_filter", "vk_corpus_set_sim_ops", "vk_corpus_set_sim_source",
 	"vk_corpus_set_sentences", "vk_corpus_set_slices", "vk_corpus_finalize", "vk_corpus_free", "vk_corpus_device_bytes",
 	"vk_query", "vk_query_batch", "vk_last_scores", "vk_last_timings", "vk_merge_topk",
 	"vk_record_words", "vk_pack_records", "vk_merge_records", "vk_rwmd_from_rows"]
@@ -149,6 +151,7 @@ def lib():
 		L.vk_corpus_view.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
 		L.vk_corpus_filter.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p)]
 		L.vk_corpus_set_sim_ops.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+		L.vk_corpus_set_sim_source.argtypes = [C.c_void_p, C.c_int32, C.c_float]
 		L.vk_corpus_device_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
 		L.vk_query.argtypes = [C.c_void_p, C.POINTER(_QueryDesc), C.POINTER(_TopkOut)]
 		L.vk_query_batch.argtypes = [C.c_void_p, C.POINTER(_QueryDesc), C.c_int32, C.POINTER(_TopkOut)]

@@ -439,8 +439,11 @@ static int query_batch_body(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_q
 			q.rwmd_normalize_bow == qs[0].rwmd_normalize_bow && q.max_matches == qs[0].max_matches &&
 			q.min_score == qs[0].min_score && q.boost == qs[0].boost && !q.tag_weights;
 	}
+	// a source that is not the cosine (vk_corpus_set_sim_source): the batch's 16-bit table is the cosine's -- query by query
+	const bool sourced = c->sim_src.kind != VK_SIMSRC_COSINE;
+	if (sourced) gemm = false;
 	if (!gemm) {
-		const int rcb = query_batch_shared_pass(c, qs, n_queries, outs, keep);
+		const int rcb = sourced ? VK_ERR_UNSUPPORTED : query_batch_shared_pass(c, qs, n_queries, outs, keep);
 		if (rcb != VK_ERR_UNSUPPORTED) return rcb;
 		c->batch_state[VK_BS_ROUTE] = 1;
 		for (int i = 0; i < n_queries; i++) {

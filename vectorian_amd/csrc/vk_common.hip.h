@@ -702,10 +702,30 @@ __device__ __forceinline__ float static_cell(float cosine, bool own, bool in_que
 	return own ? 1.0f : clip01(cosine);
 }
 
+// Under a source that is not the cosine (vk_corpus_set_sim_source; vk_sim_src_host.h) there is one arithmetic, not two: the cell of
+// the per-query table -- source, chain, sim[id(t_j)][j] = 1, clip, zeros past the query (vk_source_table_kernel) -- IS the canonical
+// cell, and every site that restates a cell of the static layout takes it from there: table j >> 4 (table_stride floats apart), row
+// `id`, column j & 15.  The kind is a kernel argument beside the chain: the branch is wave-uniform.
+__device__ __forceinline__ float static_table_cell(const float *__restrict__ table, int64_t table_stride, int id, int j) {
+	return table[(int64_t)(j >> 4) * table_stride + (int64_t)id * 16 + (j & 15)];
+}
+// ... the cell of vocabulary entry `id` and query column j at such a site: the table's under a source, else from its unclipped cosine
+__device__ __forceinline__ float static_cell(float cosine, bool own, bool in_query, const vk_host::sim_ops &ops, int sim_src,
+	const float *__restrict__ table, int64_t table_stride, int id, int j) {
+	if (sim_src != VK_SIMSRC_COSINE) return static_table_cell(table, table_stride, id, j);
+	return static_cell(cosine, own, in_query, ops);
+}
+
 // ... for vocabulary entry `id` and query columns c0 .. c0 + NC - 1 (of len_t) in the canonical arithmetic
 template <int NC>
 __device__ __forceinline__ void static_sim_canon(const uint8_t *__restrict__ etiles, int tile_bytes, int id, const uint8_t *__restrict__ qtiles,
-	int c0, int d, int prec, const int32_t *__restrict__ q_ids, int len_t, const vk_host::sim_ops &ops, float (&out)[NC]) {
+	int c0, int d, int prec, const int32_t *__restrict__ q_ids, int len_t, const vk_host::sim_ops &ops, int sim_src,
+	const float *__restrict__ table, int64_t table_stride, float (&out)[NC]) {
+	if (sim_src != VK_SIMSRC_COSINE) {
+#pragma unroll
+		for (int c = 0; c < NC; c++) out[c] = static_table_cell(table, table_stride, id, c0 + c);
+		return;
+	}
 	sim_canon<NC>(etiles + (int64_t)(id >> 4) * tile_bytes, id & 15, qtiles + (int64_t)(c0 >> 4) * tile_bytes, c0 & 15, d, prec, out);
 #pragma unroll
 	for (int c = 0; c < NC; c++) out[c] = static_cell(out[c], q_ids && q_ids[c0 + c] == id, c0 + c < len_t, ops);
@@ -754,7 +774,7 @@ __device__ __forceinline__ void static_vocab_fixup(float *__restrict__ S, int st
 	const float *__restrict__ table, int64_t table_stride, const uint32_t *__restrict__ bits, const int32_t *qkey,
 	const float *tw, const int32_t *tpos, float keep, float thr, int l,
 	const uint8_t *__restrict__ etiles = nullptr, int tile_bytes = 0, const uint8_t *__restrict__ qtiles = nullptr, int d = 0, int prec = 0,
-	const int32_t *__restrict__ q_ids = nullptr, const vk_host::sim_ops &ops = vk_host::sim_ops{}) {
+	const int32_t *__restrict__ q_ids = nullptr, const vk_host::sim_ops &ops = vk_host::sim_ops{}, int sim_src = VK_SIMSRC_COSINE) {
 	const unsigned long long mask = static_vocab_shared(len_s, len_t, tok, tag, bits, qkey);
 	if (!mask) return;
 	for (int u = l; u < len_s; u += NL) {
@@ -769,7 +789,7 @@ __device__ __forceinline__ void static_vocab_fixup(float *__restrict__ S, int st
 				float raw;
 				if constexpr (CANON) {
 					float v1[1];
-					static_sim_canon<1>(etiles, tile_bytes, id, qtiles, j, d, prec, q_ids, len_t, ops, v1);
+					static_sim_canon<1>(etiles, tile_bytes, id, qtiles, j, d, prec, q_ids, len_t, ops, sim_src, table, table_stride, v1);
 					raw = v1[0];
 				} else raw = table[(int64_t)(j >> 4) * table_stride + (int64_t)id * 16 + (j & 15)];
 				S[u * stride + j] = tag_weighted(raw, tw[RESTORE ? j : ft], pos[u], tpos[j], keep, thr);

@@ -216,6 +216,8 @@ int vk_corpus_append_vectors(vk_corpus_t *c, const void *rows, int64_t n_rows, i
 	if (mem == VK_MEM_DEVICE) {
 		VK_HIP(vk_launch_pack(rows, dtype == VK_BF16, n_rows, c->desc.d, c->d_pad, c->rows_appended, c->d_tiles, c->d_mag,
 			normalize, c->prec, c->stream));
+		if (c->raw_rows)   // a source that is not the cosine: the rows once more, unmodified, as fp32 tiles
+			VK_HIP(vk_launch_pack(rows, dtype == VK_BF16, n_rows, c->desc.d, c->raw_tile_bytes / 64, c->rows_appended, *c->raw_rows, nullptr, 0, 1, c->stream));
 		VK_HIP(hipStreamSynchronize(c->stream));
 		c->rows_appended += n_rows;
 		return VK_OK;
@@ -228,6 +230,8 @@ int vk_corpus_append_vectors(vk_corpus_t *c, const void *rows, int64_t n_rows, i
 		VK_HIP(hipMemcpyAsync(c->d_stage, (const uint8_t *)rows + (size_t)r * row_bytes, (size_t)nr * row_bytes, hipMemcpyHostToDevice, c->stream));
 		VK_HIP(vk_launch_pack(c->d_stage, dtype == VK_BF16, nr, c->desc.d, c->d_pad, c->rows_appended + r, c->d_tiles, c->d_mag,
 			normalize, c->prec, c->stream));
+		if (c->raw_rows)
+			VK_HIP(vk_launch_pack(c->d_stage, dtype == VK_BF16, nr, c->desc.d, c->raw_tile_bytes / 64, c->rows_appended + r, *c->raw_rows, nullptr, 0, 1, c->stream));
 		VK_HIP(hipStreamSynchronize(c->stream));
 	}
 	c->rows_appended += n_rows;
@@ -487,6 +491,35 @@ int vk_corpus_set_sim_ops(vk_corpus_t *c, const int32_t *kinds, const float *arg
 	return VK_OK;
 }
 
+// The source the chain runs on (vk_sim_src_host.h).  A source that is not the cosine reads the UNMODIFIED rows: the handle allocates a
+// second, fp32 copy of them here (fp32 tile layout, zero tile included), which vk_corpus_append_vectors then fills beside the unit
+// tiles -- hence before the first append.  Contextual corpora refuse: their similarities come out of the matrix pipe.
+int vk_corpus_set_sim_source(vk_corpus_t *c, int32_t kind, float arg) {
+	if (!c) return fail(VK_ERR_INVALID, "null argument");
+	if (vk_host::sim_src_check(kind, arg) != VK_OK)
+		return fail(VK_ERR_INVALID, kind == VK_SIMSRC_PNORM ? "VK_SIMSRC_PNORM: p must be finite and > 0" : "unknown similarity source " + std::to_string(kind));
+	if (kind == VK_SIMSRC_COSINE) { c->sim_src = vk_host::sim_src{VK_SIMSRC_COSINE, 0.0f}; return VK_OK; }
+	if (c->desc.layout != VK_LAYOUT_STATIC)
+		return fail(VK_ERR_UNSUPPORTED, "similarity sources beside the cosine run over VK_LAYOUT_STATIC only: this corpus is VK_LAYOUT_CONTEXTUAL");
+	if (c->desc.d > vk_host::kSimSrcMaxD)
+		return fail(VK_ERR_UNSUPPORTED, "similarity sources beside the cosine: rows of at most " + std::to_string(vk_host::kSimSrcMaxD) + " features (the table kernel keeps a query tile in LDS)");
+	if (!c->raw_rows) {
+		if (c->rows_appended > 0 || c->finalized || c->is_view || c->shares_vectors)
+			return fail(VK_ERR_STATE, "a similarity source beside the cosine is set before the first vk_corpus_append_vectors: it reads the unmodified rows, and they are gone");
+		VK_HIP(hipSetDevice(c->device));
+		const int raw_tile_bytes = (c->desc.d + 15) / 16 * 1024;
+		const size_t bytes = (size_t)c->n_tiles * (size_t)raw_tile_bytes;
+		auto rows = std::make_shared<vk_devbuf<uint8_t>>();
+		if (int rc = rows->reserve(bytes, nullptr)) return rc;
+		VK_HIP(hipMemsetAsync(*rows, 0, bytes, c->stream));   // (an error leaves the handle without the copy: `rows` frees it)
+		VK_HIP(hipStreamSynchronize(c->stream));
+		c->raw_rows = rows; c->raw_tile_bytes = raw_tile_bytes;
+		c->device_bytes += (int64_t)bytes;
+	}
+	c->sim_src = vk_host::sim_src{kind, kind == VK_SIMSRC_PNORM ? arg : 0.0f};
+	return VK_OK;
+}
+
 // The filtered corpus: keep flags and their scan on the device, slice table re-indexed, token rows / ids / codes /
 // magnitudes gathered.  A handle of its own (stream, workspaces); the static layout shares the vocabulary arrays.
 int vk_corpus_filter(vk_corpus_t *src, uint64_t pos_mask, uint64_t tag_mask, vk_corpus_t **out) {
@@ -544,6 +577,7 @@ int vk_corpus_filter(vk_corpus_t *src, uint64_t pos_mask, uint64_t tag_mask, vk_
 			c->d_tiles = src->d_tiles; c->d_mag = src->d_mag; c->shares_vectors = true;
 			c->vectors_of = src->shares_vectors ? src->vectors_of : src->shared;   // the vocabulary stays alive with this handle
 			c->sim_ops = src->sim_ops;   // the source's similarity (a contextual corpus has no chain)
+			c->sim_src = src->sim_src; c->raw_rows = src->raw_rows; c->raw_tile_bytes = src->raw_tile_bytes;   // ... and the unmodified rows it may read
 			if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return fail(VK_ERR_HIP, "hipStreamCreate failed");
 			for (auto &e : c->ev) if (hipEventCreate(&e) != hipSuccess) return fail(VK_ERR_HIP, "hipEventCreate failed");
 			int r;

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "vk_sim_ops_host.h"   // vk_host::sim_ops: the operator chain on the cosine of the static layout, by value in the structs below
+#include "vk_sim_src_host.h"   // vk_host::sim_src: the source the chain runs on (the cosine, a p-norm distance, the sqrt-cosine)
 
 #define VK_DEV_LOCAL 0
 #define VK_DEV_GLOBAL 1
@@ -190,6 +191,7 @@ struct VkWrdParams {
 	int64_t scratch_stride;
 	int32_t n_cand;
 	vk_host::sim_ops sim_ops;  // static layout: the operator chain between the cosine and sim[id(t_j)][j] = 1 / the clip (static_cell, vk_common.hip.h); n = 0: none
+	int32_t sim_src;           // static layout: the handle's source (VK_SIMSRC_*); not the cosine: the table's cell is the canonical cell (static_table_cell)
 };
 
 struct VkFlowParams {
@@ -220,6 +222,7 @@ struct VkFlowParams {
 	int16_t *mapping;          // [k x 16]
 	float *edge_sim;           // [k x 16]
 	vk_host::sim_ops sim_ops;  // static layout: the operator chain between the cosine and sim[id(t_j)][j] = 1 / the clip (static_cell, vk_common.hip.h); n = 0: none
+	int32_t sim_src;           // static layout: the handle's source (VK_SIMSRC_*); not the cosine: the table's cell is the canonical cell (static_table_cell)
 };
 
 // a batch of at most 4 queries with common options over one pass of a contextual corpus (vk_score_batch_kernel)
@@ -306,6 +309,7 @@ struct VkWideParams {
 	int32_t h_ring;            // vk_wide_kernel, global-state form with ws_tail: rows of the LDS ring of the column history (vk_wide_ring_rows; 0: history in the scratch)
 	int32_t ws_tail;           // vk_wide_kernel, general gaps: w_s[k] == w_s[ws_tail] for every k >= ws_tail up to max_len (0: no such tail)
 	vk_host::sim_ops sim_ops;  // static layout: the operator chain between the cosine and sim[id(t_j)][j] = 1 / the clip (static_cell, vk_common.hip.h); n = 0: none
+	int32_t sim_src;           // static layout: the handle's source (VK_SIMSRC_*); not the cosine: the table's cell is the canonical cell (static_table_cell)
 };
 
 // queries of 65 .. VK_MAX_QUERY_LEN tokens (vk_longq_kernel): one wave per slice, lane = slice token, anti-diagonal sweep
@@ -353,6 +357,19 @@ struct VkLongqParams {
 	int32_t n_order;
 	int64_t dm_off, su_off;
 	vk_host::sim_ops sim_ops;  // static layout: the operator chain between the cosine and sim[id(t_j)][j] = 1 / the clip (static_cell, vk_common.hip.h); n = 0: none
+	int32_t sim_src;           // static layout: the handle's source (VK_SIMSRC_*); not the cosine: the table's cell is the canonical cell (static_table_cell)
+};
+
+// vk_launch_table under a source that is not the cosine (null / kind VK_SIMSRC_COSINE: the cosine's kernels): the fp32 copy of the
+// unmodified vocabulary rows in the fp32 tile layout (n_tiles tiles of raw_tile_bytes = 64 x d rounded up to 16), the query tile's 16
+// unmodified rows [16 x d] row-major (rows past the query: anything finite), and sum_k |q_k| of each (sqrt-cosine; vk_sim_src_host.h)
+struct VkSimSrcArgs {
+	vk_host::sim_src src;
+	const uint8_t *raw_tiles;
+	int32_t raw_tile_bytes;
+	int32_t d;
+	const float *q_rows;
+	const float *q_abs_sums;
 };
 
 #ifdef __cplusplus
@@ -423,7 +440,8 @@ hipError_t vk_launch_filter_rows(const uint8_t *src, uint8_t *dst, const int32_t
 hipError_t vk_launch_filter_gather(const void *src, void *dst, int32_t elem_bytes, const int32_t *src_of, int64_t n_kept,
 	hipStream_t stream);
 hipError_t vk_launch_table(const uint8_t *etiles, const uint8_t *qtile, int32_t n_tiles, int32_t nk32, int32_t tail,
-	int32_t tile_bytes, float *table, const int32_t *q_ids, int32_t len_t, int32_t V, int32_t prec, const vk_host::sim_ops *ops, hipStream_t stream);
+	int32_t tile_bytes, float *table, const int32_t *q_ids, int32_t len_t, int32_t V, int32_t prec, const vk_host::sim_ops *ops,
+	const VkSimSrcArgs *src, hipStream_t stream);
 hipError_t vk_launch_score(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
 int32_t vk_score_m8t_tail_k(void);   // K of the flat-tailed bound kernels over the 6-bit shadow (vk_score_m8t.hip) ...
 int32_t vk_score_m7t_tail_k(void);   // ... and over the 8-bit shadow (vk_score_m7t.hip)

@@ -63,10 +63,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6))) void vk
 		const int id = is_static ? p.tok_id[tok] : 0;
 		const uint8_t *xrow = is_static ? canon_row_ptr_static(p.tiles, p.tile_bytes, id) : canon_row_ptr(p.tiles + (int64_t)(tile0 + ti) * p.tile_bytes, lane);
 		const int cb = (lane >> 4) * 4;
-		float val[4];
-		sim_canon16(xrow, p.qtile, p.nk32, p.tail, p.d, PREC, canon, lane, val);
+		float val[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+		if (!(is_static && p.sim_src))   // (not the cosine: static_cell takes the table's cell)
+			sim_canon16(xrow, p.qtile, p.nk32, p.tail, p.d, PREC, canon, lane, val);
 #pragma unroll
-		for (int r = 0; r < 4; r++) val[r] = is_static ? static_cell(val[r], p.q_ids && p.q_ids[cb + r] == id, cb + r < len_t, p.sim_ops) : clip01(val[r]);   // chain, sim[id(t_j)][j] = 1 (metric/static.cpp:46-67), clip
+		for (int r = 0; r < 4; r++) val[r] = is_static ? static_cell(val[r], p.q_ids && p.q_ids[cb + r] == id, cb + r < len_t, p.sim_ops, p.sim_src, p.table, 0, id, cb + r) : clip01(val[r]);   // chain, sim[id(t_j)][j] = 1 (metric/static.cpp:46-67), clip
 		*reinterpret_cast<float4 *>(S + (ti * 16 + (lane & 15)) * 16 + cb) = make_float4(val[0], val[1], val[2], val[3]);
 		if (p.pos_s) {
 			const int ps = p.pos_s[tok];
@@ -387,12 +388,13 @@ __global__ __launch_bounds__(64) void vk_wide_kernel(VkWideParams p) {
 				const uint8_t *xrow = is_static ? canon_row_ptr_static(p.tiles, p.tile_bytes, id) : canon_row_ptr(p.tiles + (int64_t)(base >> 4) * p.tile_bytes, lane);
 				const int ps = p.pos_s ? p.pos_s[tok] : 0;
 				for (int qt = 0; qt < p.nq; qt++) {
-					float val[4];
-					sim_canon16(xrow, p.qtile + (int64_t)qt * p.tile_bytes, p.nk32, p.tail, p.d, p.prec, canon, lane, val);
+					float val[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+					if (!(is_static && p.sim_src))   // (not the cosine: static_cell takes the table's cell)
+						sim_canon16(xrow, p.qtile + (int64_t)qt * p.tile_bytes, p.nk32, p.tail, p.d, p.prec, canon, lane, val);
 					const int c0 = qt * 16 + (lane >> 4) * 4;
 #pragma unroll
 					for (int r = 0; r < 4; r++) {
-						val[r] = is_static ? static_cell(val[r], p.q_ids && p.q_ids[c0 + r] == id, c0 + r < len_t, p.sim_ops) : clip01(val[r]);
+						val[r] = is_static ? static_cell(val[r], p.q_ids && p.q_ids[c0 + r] == id, c0 + r < len_t, p.sim_ops, p.sim_src, p.table, p.table_stride, id, c0 + r) : clip01(val[r]);
 						Sx[(lane & 15) * LQ + c0 + r] = val[r];
 						if (p.pos_s) SWx[(lane & 15) * LQ + c0 + r] = tag_weighted(val[r], twl[c0 + r], ps, tposl[c0 + r], p.tw_keep, p.tw_threshold);
 					}

@@ -156,6 +156,13 @@ struct vk_corpus_shape {
 	// the operator chain on the cosine (vk_corpus_set_sim_ops; static layout only): a view and a filtered corpus start with their
 	// source's, after that each handle is set on its own
 	vk_host::sim_ops sim_ops{};
+	// the source the chain runs on (vk_corpus_set_sim_source; vk_sim_src_host.h), inherited the same way, and -- under a source that
+	// is not the cosine -- the second, fp32 copy of the UNMODIFIED rows in the fp32 tile layout: n_tiles tiles of raw_tile_bytes.  An
+	// owning buffer that the handles of one vocabulary hold together (views and filtered corpora copy the pointer): it goes with the
+	// last of them.  Counted in the device_bytes of the handle that made it, by hand (a buffer's own count would outlive that handle)
+	vk_host::sim_src sim_src{};
+	std::shared_ptr<vk_devbuf<uint8_t>> raw_rows;
+	int raw_tile_bytes = 0;
 };
 
 // vk_corpus::batch_state by index (the internal export vk_batch_state hands the array out in this order; the tests name the
@@ -193,6 +200,7 @@ struct vk_corpus : vk_corpus_shape {
 	vk_devbuf<float> d_ws, d_wt;   // d_ws: at least kGapTable floats (grown by a query over a corpus with longer slices)
 	vk_devbuf<int32_t> d_qids;
 	vk_devbuf<float> d_table;
+	vk_devbuf<float> d_qraw;      // under a source that is not the cosine: the query's unmodified rows, per tile [16 x d] and 16 sums of |q_k|
 	vk_devbuf<float> d_scores, d_raw, d_boost;
 	vk_devbuf<uint64_t> d_keys[2];
 	vk_devbuf<float> d_out_raw, d_out_sim;   // the winners' outputs: at least VK_MAX_MATCHES of them (grown by a query that asks for more matches)
@@ -288,7 +296,8 @@ template <typename P> void corpus_fields(P &p, const vk_corpus *c) {
 	p.nk32 = c->nk32; p.tail = c->tail; p.tile_bytes = c->tile_bytes;
 }
 // the handle's operator chain into the structs of the kernels that restate cells of the static layout (the others have no such field)
-template <typename P> auto sim_ops_field(P &p, const vk_corpus *c, int) -> decltype((void)p.sim_ops) { p.sim_ops = c->sim_ops; }
+// (beside it the kind of the handle's source: not the cosine, and those kernels read the table's cells instead)
+template <typename P> auto sim_ops_field(P &p, const vk_corpus *c, int) -> decltype((void)p.sim_ops) { p.sim_ops = c->sim_ops; p.sim_src = c->sim_src.kind; }
 template <typename P> void sim_ops_field(P &, const vk_corpus *, long) {}
 // ... and those of the structs that serve both layouts and both precisions (d_tok_id is null unless the layout is static)
 template <typename P> void corpus_fields_ids(P &p, const vk_corpus *c) {
@@ -381,6 +390,33 @@ int upload_boost(vk_corpus *c, const float *boost, vk_host_keep &keep, hipStream
 	}
 	VK_HIP(hipMemcpyAsync(c->d_boost, boost, (size_t)n * 4, hipMemcpyHostToDevice, st));
 	return VK_OK;
+}
+
+// Under a source that is not the cosine: the query's rows as the caller gives them (bf16 widened exactly; q_normalize is the cosine
+// tile's alone) for the table kernel -- per 16 query tokens [16 x d] floats and the 16 sums of |q_k| (vk_host::sim_src_abs_sum) -- into
+// d_qraw, and the arguments of vk_launch_table for tile t
+constexpr size_t vk_source_tile_floats(int d) { return 16 * (size_t)d + 16; }
+int upload_source_query(vk_corpus *c, const vk_query_desc *q, vk_host_keep &keep, hipStream_t st) {
+	const int d = c->desc.d, nq = (q->len_t + 15) / 16;
+	const size_t per = vk_source_tile_floats(d);
+	std::vector<float> &rows = keep.vec<float>(per * (size_t)nq);
+	std::fill(rows.begin(), rows.end(), 0.0f);
+	for (int i = 0; i < q->len_t; i++) {
+		float *row = rows.data() + (size_t)(i >> 4) * per + (size_t)(i & 15) * d;
+		for (int k = 0; k < d; k++)
+			row[k] = q->q_dtype == VK_F32 ? ((const float *)q->q_vectors)[(size_t)i * d + k] : bf16_to_f32(((const uint16_t *)q->q_vectors)[(size_t)i * d + k]);
+		rows[(size_t)(i >> 4) * per + 16 * (size_t)d + (size_t)(i & 15)] = vk_host::sim_src_abs_sum(row, d);
+	}
+	if (int rc = c->d_qraw.reserve(rows.size(), &c->device_bytes)) return rc;
+	VK_HIP(hipMemcpyAsync(c->d_qraw, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, st));
+	return VK_OK;
+}
+VkSimSrcArgs source_table_args(const vk_corpus *c, int t) {
+	VkSimSrcArgs a{};
+	a.src = c->sim_src; a.raw_tiles = c->raw_rows ? (const uint8_t *)*c->raw_rows : nullptr; a.raw_tile_bytes = c->raw_tile_bytes; a.d = c->desc.d;
+	a.q_rows = (const float *)c->d_qraw + (size_t)t * vk_source_tile_floats(c->desc.d);
+	a.q_abs_sums = a.q_rows + 16 * (size_t)c->desc.d;
+	return a;
 }
 
 // row of the slice table of a slice (long slices sit in padded groups); the inverse of entry_sent is built when first needed

@@ -84,12 +84,13 @@ __global__ __launch_bounds__(64) void vk_longq_kernel(VkLongqParams p) {
 				const int ps = p.pos_s ? p.pos_s[tok] : 0;
 #pragma unroll 1
 				for (int b = 0; b < p.nq; b++) {
-					float val[4];
-					sim_canon16(xrow, p.qtile + (int64_t)b * p.tile_bytes, p.nk32, p.tail, p.d, p.prec, canon, lane, val);
+					float val[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+					if (!(is_static && p.sim_src))   // (not the cosine: static_cell takes the table's cell)
+						sim_canon16(xrow, p.qtile + (int64_t)b * p.tile_bytes, p.nk32, p.tail, p.d, p.prec, canon, lane, val);
 					const int c0 = 16 * b + (lane >> 4) * 4;
 #pragma unroll
 					for (int r = 0; r < 4; r++) {
-						float x = is_static ? static_cell(val[r], p.q_ids && p.q_ids[c0 + r] == id, c0 + r < p.len_t, p.sim_ops) : clip01(val[r]);   // chain, sim[id(t_j)][j] = 1 (metric/static.cpp:46-67), clip
+						float x = is_static ? static_cell(val[r], p.q_ids && p.q_ids[c0 + r] == id, c0 + r < p.len_t, p.sim_ops, p.sim_src, p.table, p.table_stride, id, c0 + r) : clip01(val[r]);   // chain, sim[id(t_j)][j] = 1 (metric/static.cpp:46-67), clip
 						if (p.pos_s) {
 							if (rel < len_s && c0 + r < LT) Su[(c0 + r) * 64 + rel] = x;
 							x = tag_weighted(x, p.tw[c0 + r], ps, p.tpos[c0 + r], p.tw_keep, p.tw_threshold);

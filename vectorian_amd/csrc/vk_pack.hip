@@ -1,6 +1,7 @@
 // vk_pack.hip -- corpus upload (normalise, round, tile order) and the per-query table of the static layout.
 #include "vk_common.hip.h"
 #include "vk_bound_host.h"   // the format of a shadow and the quantizer of a row (host and device)
+#include "vk_sim_src_host.h" // the cell of a source that is not the cosine (host and device)
 
 // ---------------------------------------------------------------------------
 // corpus upload: L2-normalise rows (Vectors.normalized, vectorian/embedding/vectors.py:71-86),
@@ -261,6 +262,85 @@ __global__ __launch_bounds__(256) void vk_table_kernel(const uint8_t *__restrict
 	*reinterpret_cast<f32x4 *>(table + ((int64_t)tile * 16 + (lane & 15)) * 16 + (lane >> 4) * 4) = acc;
 }
 
+// The same table under a source that is not the cosine (vk_corpus_set_sim_source; the cell: vk_sim_src_host.h), from the fp32 copy of
+// the UNMODIFIED vocabulary rows (fp32 tile layout: a block of 16 features is 1 KiB, lane 16 g + i owns row i, features
+// 16 b + 4 s + g for s = 0..3) and the query tile's unmodified rows.  A workgroup stages the query rows in LDS in the same order --
+// qlds[(4 b + g) * 16 + j]: features 16 b + 4 s + g of query row j, one 16-byte read per column, the same address for the 16 lanes
+// of a quarter -- and each of its four waves takes one vocabulary tile: one coalesced 1 KiB load per block, the terms of the lane's
+// row against the len_t live columns into double partial sums (the lane's are those of the features k mod 4 = g, ascending: the
+// header's order), two exchanges across the four lanes of a row, the finish, the handle's chain, the clip.  Lane 16 g + i then
+// holds row i x columns 4 g .. 4 g + 3, as vk_table_kernel's lanes do.  Vocabulary rows past V and columns past len_t stay ZERO: a
+// distance to a row of padding is not zero, 1 - x of it can be positive, and the epilogues' maxima count on zeros there.
+// FORM: vk_host::SIM_SRC_*.  No array is indexed by a run-time value: nothing goes to scratch.
+template <int FORM>
+__global__ __launch_bounds__(256) void vk_source_table_kernel(const uint8_t *__restrict__ raw_tiles, int32_t n_tiles, int32_t raw_tile_bytes, int32_t d,
+	const float *__restrict__ q_rows, const float *__restrict__ q_abs_sums, float *__restrict__ table, int32_t len_t, int32_t V,
+	const float p_arg, const vk_host::sim_ops ops) {
+	extern __shared__ float4 vk_src_qlds[];
+	const int nb = raw_tile_bytes >> 10;
+	for (int idx = threadIdx.x; idx < nb * 64; idx += 256) {
+		const int b = idx >> 6, g = (idx >> 4) & 3, j = idx & 15;
+		float v[4];
+#pragma unroll
+		for (int e = 0; e < 4; e++) {
+			const int k = 16 * b + 4 * e + g;
+			v[e] = (j < len_t && k < d) ? q_rows[(int64_t)j * d + k] : 0.0f;
+		}
+		vk_src_qlds[idx] = make_float4(v[0], v[1], v[2], v[3]);
+	}
+	__syncthreads();
+	const int lane = threadIdx.x & 63;
+	const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (tile >= n_tiles) return;
+	const int i = lane & 15, g = lane >> 4;
+	const uint8_t *__restrict__ tp = raw_tiles + (int64_t)tile * raw_tile_bytes;
+	double acc[16];
+#pragma unroll
+	for (int j = 0; j < 16; j++) acc[j] = 0.0;
+	double abs_a = 0.0;
+#pragma unroll 1
+	for (int b = 0; b < nb; b++) {
+		const float4 x4 = *reinterpret_cast<const float4 *>(tp + (int64_t)b * 1024 + lane * 16);
+		const float x[4] = {x4.x, x4.y, x4.z, x4.w};
+		if constexpr (FORM == vk_host::SIM_SRC_SQRT_COS) {
+#pragma unroll
+			for (int e = 0; e < 4; e++) abs_a += (double)fabsf(x[e]);
+		}
+#pragma unroll
+		for (int j = 0; j < 16; j++) {
+			if (j < len_t) {   // (uniform)
+				const float4 q4 = vk_src_qlds[(4 * b + g) * 16 + j];
+				const float q[4] = {q4.x, q4.y, q4.z, q4.w};
+#pragma unroll
+				for (int e = 0; e < 4; e++) acc[j] += (double)vk_host::sim_src_term<FORM>(x[e], q[e], p_arg);
+			}
+		}
+	}
+	// (s0 + s1) + (s2 + s3) across the lanes i, 16 + i, 32 + i, 48 + i: an IEEE sum does not depend on the order of its two operands
+	float sum_a = 0.0f;
+	if constexpr (FORM == vk_host::SIM_SRC_SQRT_COS) {
+		abs_a += __shfl_xor(abs_a, 16, 64);
+		abs_a += __shfl_xor(abs_a, 32, 64);
+		sum_a = (float)abs_a;
+	}
+	const bool word = tile * 16 + i < V;
+	float cell[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+	for (int j = 0; j < 16; j++) {
+		if (j < len_t) {
+			double s = acc[j];
+			s += __shfl_xor(s, 16, 64);
+			s += __shfl_xor(s, 32, 64);
+			if ((j >> 2) == g) {   // this lane's four columns: the finish, the chain, the clip
+				float v = vk_host::sim_src_finish<FORM>((float)s, p_arg, sum_a, FORM == vk_host::SIM_SRC_SQRT_COS ? q_abs_sums[j] : 0.0f);
+				if (ops.n > 0) v = vk_host::sim_ops_apply(v, ops);
+				cell[j & 3] = word ? clip01(v) : 0.0f;
+			}
+		}
+	}
+	*reinterpret_cast<float4 *>(table + ((int64_t)tile * 16 + i) * 16 + g * 4) = make_float4(cell[0], cell[1], cell[2], cell[3]);
+}
+
 // sim[id(t_j)][j] = 1 (metric/static.cpp:58-67); runs after vk_table_kernel
 __global__ void vk_table_fix_kernel(float *__restrict__ table, const int32_t *__restrict__ q_ids, int32_t len_t, int32_t V) {
 	const int j = threadIdx.x;
@@ -282,8 +362,26 @@ extern "C" hipError_t vk_launch_pack(const void *in, int32_t dtype_bf16, int64_t
 }
 
 extern "C" hipError_t vk_launch_table(const uint8_t *etiles, const uint8_t *qtile, int32_t n_tiles, int32_t nk32, int32_t tail,
-	int32_t tile_bytes, float *table, const int32_t *q_ids, int32_t len_t, int32_t V, int32_t prec, const vk_host::sim_ops *ops, hipStream_t stream) {
-	if (ops && ops->n > 0) vk_table_kernel<true><<<(n_tiles + 3) / 4, 256, 0, stream>>>(etiles, qtile, n_tiles, nk32, tail, tile_bytes, table, prec, len_t, V, *ops);
+	int32_t tile_bytes, float *table, const int32_t *q_ids, int32_t len_t, int32_t V, int32_t prec, const vk_host::sim_ops *ops,
+	const VkSimSrcArgs *src, hipStream_t stream) {
+	const vk_host::sim_ops chain = ops ? *ops : vk_host::sim_ops{};
+	if (src && src->src.kind != VK_SIMSRC_COSINE) {
+		// the query tile's rows in LDS: 64 bytes per feature (d rounded up to 16), at most 64 KiB (vk_host::kSimSrcMaxD)
+		if (!src->raw_tiles || !src->q_rows || !src->q_abs_sums || src->d < 1 || src->d > vk_host::kSimSrcMaxD || src->raw_tile_bytes != (src->d + 15) / 16 * 1024 ||
+			len_t < 1 || len_t > 16) return hipErrorInvalidValue;
+		const unsigned grid = (unsigned)((n_tiles + 3) / 4);
+		const size_t lds = (size_t)src->raw_tile_bytes;
+#define VK_SRC_TABLE(FORM) vk_source_table_kernel<FORM><<<grid, 256, lds, stream>>>(src->raw_tiles, n_tiles, src->raw_tile_bytes, src->d, src->q_rows, \
+	src->q_abs_sums, table, len_t, V, src->src.arg, chain)
+		switch (vk_host::sim_src_form(src->src)) {
+		case vk_host::SIM_SRC_P1: VK_SRC_TABLE(vk_host::SIM_SRC_P1); break;
+		case vk_host::SIM_SRC_P2: VK_SRC_TABLE(vk_host::SIM_SRC_P2); break;
+		case vk_host::SIM_SRC_PGEN: VK_SRC_TABLE(vk_host::SIM_SRC_PGEN); break;
+		default: VK_SRC_TABLE(vk_host::SIM_SRC_SQRT_COS); break;
+		}
+#undef VK_SRC_TABLE
+	}
+	else if (chain.n > 0) vk_table_kernel<true><<<(n_tiles + 3) / 4, 256, 0, stream>>>(etiles, qtile, n_tiles, nk32, tail, tile_bytes, table, prec, len_t, V, chain);
 	else vk_table_kernel<false><<<(n_tiles + 3) / 4, 256, 0, stream>>>(etiles, qtile, n_tiles, nk32, tail, tile_bytes, table, prec, len_t, V, vk_host::sim_ops{});
 	if (q_ids) vk_table_fix_kernel<<<1, 64, 0, stream>>>(table, q_ids, len_t, V);
 	return hipGetLastError();

@@ -443,9 +443,16 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		int32_t *ids = keep.array<int32_t>(80);
 		for (int j = 0; j < 80; j++) ids[j] = (q->q_token_ids && j < q->len_t) ? q->q_token_ids[j] : -1;
 		VK_HIP(hipMemcpyAsync(c->d_qids, ids, 80 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-		for (int t = 0; t < nq && !only; t++)   // one [V_pad x 16] table per 16 query tokens (the traceback kernels restate their cells themselves)
+		// one [V_pad x 16] table per 16 query tokens (the traceback kernels restate their cells themselves -- or, under a source that is
+		// not the cosine, read them from these tables: then a query that only states listed slices needs them too)
+		const bool sourced = c->sim_src.kind != VK_SIMSRC_COSINE;
+		if (sourced && (rc = upload_source_query(c, q, keep, st))) return rc;
+		for (int t = 0; t < nq && (!only || sourced); t++) {
+			const VkSimSrcArgs sa = source_table_args(c, t);
 			VK_HIP(vk_launch_table(c->d_tiles, c->d_qtile + (size_t)t * c->tile_bytes, (int32_t)c->n_tiles, c->nk32, c->tail, c->tile_bytes,
-				c->d_table + t * table_stride, q->q_token_ids ? c->d_qids + t * 16 : nullptr, std::min(16, q->len_t - t * 16), c->desc.vocab_size, c->prec, &c->sim_ops, st));
+				c->d_table + t * table_stride, q->q_token_ids ? c->d_qids + t * 16 : nullptr, std::min(16, q->len_t - t * 16), c->desc.vocab_size, c->prec, &c->sim_ops,
+				sourced ? &sa : nullptr, st));
+		}
 	}
 
 	// ---- the size of the selection (known before the scoring pass: the bound pass prunes against it)
@@ -1077,7 +1084,9 @@ int vk_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out) {
 	std::vector<int16_t> own_map;
 	std::vector<float> own_sim;
 	bool restate = false;
-	if (c->sim_ops.n > 0 && q->algorithm == VK_ALG_ALIGN && !q->want_flow && !q->only_slices && q->submatch_weight == 0.0f) {
+	// (A source that is not the cosine, chain or none: likewise.  The table's cell is the canonical cell there, but the scoring
+	// kernels' sums over a slice are not stated to be the tracebacks' sums.)
+	if ((c->sim_ops.n > 0 || c->sim_src.kind != VK_SIMSRC_COSINE) && q->algorithm == VK_ALG_ALIGN && !q->want_flow && !q->only_slices && q->submatch_weight == 0.0f) {
 		q_flow = *q; q_flow.want_flow = 1;
 		out_flow = *out;
 		own_map.assign((size_t)out->capacity * (size_t)q->len_t, (int16_t)-1);

@@ -78,12 +78,13 @@ __device__ __forceinline__ int transport_sim_rows(const VkWrdParams &p, float *S
 			const int ps = p.pos_s ? p.pos_s[tok] : 0;
 #pragma unroll 1
 			for (int b = 0; b < NQ; b++) {
-				float val[4];
-				sim_canon16(xrow, p.qtile + (int64_t)b * p.tile_bytes, p.nk32, p.tail, p.d, p.prec, canon, lane, val);
+				float val[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+				if (!(is_static && p.sim_src))   // (not the cosine: static_cell takes the table's cell)
+					sim_canon16(xrow, p.qtile + (int64_t)b * p.tile_bytes, p.nk32, p.tail, p.d, p.prec, canon, lane, val);
 				const int c0 = 16 * b + (lane >> 4) * 4;
 #pragma unroll
 				for (int r = 0; r < 4; r++) {
-					val[r] = is_static ? static_cell(val[r], p.q_ids && p.q_ids[c0 + r] == id, c0 + r < p.len_t, p.sim_ops) : clip01(val[r]);   // chain, sim[id(t_j)][j] = 1 (metric/static.cpp:46-67), clip
+					val[r] = is_static ? static_cell(val[r], p.q_ids && p.q_ids[c0 + r] == id, c0 + r < p.len_t, p.sim_ops, p.sim_src, p.table, p.table_stride, id, c0 + r) : clip01(val[r]);   // chain, sim[id(t_j)][j] = 1 (metric/static.cpp:46-67), clip
 					if (p.pos_s) val[r] = tag_weighted(val[r], p.tw[c0 + r], ps, p.tpos[c0 + r], p.tw_keep, p.tw_threshold);
 				}
 				*reinterpret_cast<float4 *>(S + (ti * 16 + (lane & 15)) * N + c0) = make_float4(val[0], val[1], val[2], val[3]);
@@ -92,7 +93,7 @@ __device__ __forceinline__ int transport_sim_rows(const VkWrdParams &p, float *S
 		if (is_static && p.qid_bits && p.pos_s) {   // tag-weighted vocabulary transport: cells upstream writes twice (static_vocab_fixup, vk_common.hip.h)
 			wave_lds_fence();
 			static_vocab_fixup<64, true>(S, N, m, p.len_t, p.tok_id + t_a, p.tag_s + t_a, p.pos_s + t_a, p.table, p.table_stride,
-				p.qid_bits, p.qkey, p.tw, p.tpos, p.tw_keep, p.tw_threshold, lane, p.tiles, p.tile_bytes, p.qtile, p.d, p.prec, p.q_ids, p.sim_ops);
+				p.qid_bits, p.qkey, p.tw, p.tpos, p.tw_keep, p.tw_threshold, lane, p.tiles, p.tile_bytes, p.qtile, p.d, p.prec, p.q_ids, p.sim_ops, p.sim_src);
 		}
 		return is_static ? 0 : t_a - tile0 * 16;
 	}
@@ -737,12 +738,13 @@ __global__ __launch_bounds__(64) void vk_canon_rows_kernel(VkWrdParams p) {
 	float *out = p.rows_out + ((int64_t)w * R + (live ? rel : 0)) * N;
 #pragma unroll 1
 	for (int b = 0; b < NQ; b++) {
-		float val[4];
-		sim_canon16(xrow, p.qtile + (int64_t)b * p.tile_bytes, p.nk32, p.tail, p.d, p.prec, canon, lane, val);
+		float val[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+		if (!(is_static && p.sim_src))   // (not the cosine: static_cell takes the table's cell)
+			sim_canon16(xrow, p.qtile + (int64_t)b * p.tile_bytes, p.nk32, p.tail, p.d, p.prec, canon, lane, val);
 		const int c0 = 16 * b + (lane >> 4) * 4;
 #pragma unroll
 		for (int r = 0; r < 4; r++) {
-			val[r] = is_static ? static_cell(val[r], p.q_ids && p.q_ids[c0 + r] == id, c0 + r < p.len_t, p.sim_ops) : clip01(val[r]);
+			val[r] = is_static ? static_cell(val[r], p.q_ids && p.q_ids[c0 + r] == id, c0 + r < p.len_t, p.sim_ops, p.sim_src, p.table, p.table_stride, id, c0 + r) : clip01(val[r]);
 			if (p.pos_s) val[r] = tag_weighted(val[r], p.tw[c0 + r], ps, p.tpos[c0 + r], p.tw_keep, p.tw_threshold);
 		}
 		if (live) *reinterpret_cast<float4 *>(out + c0) = make_float4(val[0], val[1], val[2], val[3]);

@@ -109,6 +109,11 @@ class Corpus:
 		args = np.ascontiguousarray([a for _, a in pairs], dtype=np.float32)
 		_core._check(_core.lib().vk_corpus_set_sim_ops(self._h, _core._np_ptr(kinds), _core._np_ptr(args), len(pairs)))
 
+	def set_sim_source(self, kind, arg=0.0):
+		"""the VectorSim the chain runs on (vk_corpus_set_sim_source): core.VK_SIMSRC_* and its argument (p of the p-norm).  A source
+		beside the cosine reads the unmodified rows, so it is set BEFORE append_vectors; static layout only."""
+		_core._check(_core.lib().vk_corpus_set_sim_source(self._h, int(kind), float(arg)))
+
 	def finalize(self):
 		_core._check(_core.lib().vk_corpus_finalize(self._h))
 

@@ -26,7 +26,8 @@ from vectorian_amd.lanes import LanesMixin
 from vectorian_amd.match import HipMatch, Match, PyMatch, Region, TokenMatch, TokenMatchEdge, TokenMatchT, _Winners
 from vectorian_amd.options import _QUERY_OPTION_WHITELIST, _split_gap, backend_args
 from vectorian_amd.query import PreparedQuery, Query, default_tokenizer
-from vectorian_amd.sim import CosineSim, EmbeddingTokenSim, ModifiedVectorSim, OptimizedSpanSim
+from vectorian_amd.sim import (CosineSim, EmbeddingTokenSim, EuclideanDistance, ImprovedSqrtCosineSim, ModifiedVectorSim, OptimizedSpanSim,
+	PNormDistance)
 
 PartitionData = collections.namedtuple("PartitionData", ["level", "window_size", "window_step"])
 _NO_LOCK = contextlib.nullcontext()   # backends without a per-handle lock (the test double)
@@ -107,7 +108,7 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 			raise NotImplementedError("token similarity modifiers are outside the HIP path (SURVEY 2.1): they combine clipped "
 				"similarity matrices and leave values outside [0, 1]; shape ONE cosine with ModifiedVectorSim instead")
 		self._embedding = token_sim.embedding
-		self._sim_ops = self._operator_chain(token_sim.similarity, self._embedding)
+		self._sim_source, self._sim_ops = self._operator_chain(token_sim.similarity, self._embedding)
 		self._metric_name = token_sim.to_args(self)["name"]
 		session = self.session
 		level, size = partition.level, partition.window_size
@@ -172,6 +173,9 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 			self._corpus = make(layout=core.VK_LAYOUT_STATIC, d=emb.dimension, n_tokens=n_tokens_dev, n_sentences=n_slices_dev,
 				vocab_size=max(1, session.vocab.size), keep_magnitudes=True, device=device, precision=precision)
 			E = vocab_vectors.unmodified if session.vocab.size else np.zeros((1, emb.dimension), np.float32)
+			if self._sim_source is not None:
+				# a source beside the cosine reads the unmodified rows: the handle keeps a second copy of what is appended next
+				self._corpus.set_sim_source(*self._sim_source)
 			self._corpus.append_vectors(E, normalize=True)
 			if self._sim_ops:
 				# state of the handle: the views (find_many) and filtered corpora made later inherit it through the library
@@ -213,17 +217,21 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 
 	@staticmethod
 	def _operator_chain(similarity, embedding):
-		"""the (kind, float32 arg) pairs of the vector similarity's operator chain -- empty for the plain CosineSim -- or the
-		reason this similarity does not run here"""
+		"""(source, chain) of the vector similarity: the source's (kind, float32 arg) of vk_corpus_set_sim_source -- None for
+		CosineSim -- and the (kind, float32 arg) pairs of the operator chain, empty without one; or the reason this similarity does
+		not run here"""
 		if isinstance(similarity, CosineSim):
-			return []
+			return None, []
+		computes = "the HIP path computes CosineSim, PNormDistance and ImprovedSqrtCosineSim (over contextual embeddings CosineSim only), not other VectorSims"
 		if not isinstance(similarity, ModifiedVectorSim):
-			raise NotImplementedError(f"{similarity.name}: the HIP path computes CosineSim")
+			return HipBruteForceIndex._source_of(similarity, similarity, embedding, f"{similarity.name}: {computes}"), []
 		source, operators = similarity.source, similarity.operators
 		if isinstance(source, ModifiedVectorSim):
 			raise NotImplementedError(f"{similarity.name}: nested ModifiedVectorSim; give ONE ModifiedVectorSim all the operators, in order")
+		src = None
 		if not isinstance(source, CosineSim):
-			raise NotImplementedError(f"{similarity.name}: the HIP path modifies CosineSim only, not {source.name}")
+			src = HipBruteForceIndex._source_of(source, similarity, embedding,
+				f"{similarity.name}: the HIP path modifies CosineSim, PNormDistance and ImprovedSqrtCosineSim (over contextual embeddings CosineSim only), not {source.name}")
 		if len(operators) > core.VK_MAX_SIM_OPS:
 			raise NotImplementedError(f"{similarity.name}: {len(operators)} operators; the HIP path takes at most {core.VK_MAX_SIM_OPS}")
 		if not embedding.is_static:
@@ -236,7 +244,19 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 			except (AttributeError, NotImplementedError):
 				raise NotImplementedError(f"{type(op).__name__}: not an operator of vectorian_amd.kernel (the device runs those six)") from None
 			ops.append((int(kind), np.float32(arg)))
-		return ops
+		return src, ops
+
+	@staticmethod
+	def _source_of(source, similarity, embedding, refusal):
+		"""(kind, float32 arg) of a source that is not the cosine, or why it does not run here"""
+		if type(source) not in (PNormDistance, EuclideanDistance, ImprovedSqrtCosineSim):   # (a subclass may compute anything)
+			raise NotImplementedError(refusal)
+		if not embedding.is_static:
+			raise NotImplementedError(f"{similarity.name}: {source.name} runs over static embeddings only; {embedding.name} is contextual")
+		kind, arg = source.sim_source
+		if kind == core.VK_SIMSRC_PNORM and not (np.isfinite(arg) and arg > 0):
+			raise NotImplementedError(f"{similarity.name}: the p of a p-norm must be finite and > 0")
+		return int(kind), np.float32(arg)
 
 	@property
 	def metric_name(self):

@@ -4,10 +4,14 @@ VectorSim / CosineSim   vectorian/sim/vector.py:17-78
 ModifiedVectorSim       vectorian/sim/vector.py:179-200 (its operators: vectorian_amd/kernel.py, re-exported here)
 TokenSim / EmbeddingTokenSim   vectorian/sim/token.py:4-44
 SpanSim / OptimizedSpanSim     vectorian/sim/span.py:9-71
-A ModifiedVectorSim over CosineSim -- a chain of up to 8 operators on the unclipped cosine -- runs on the device over static
-embeddings: `EmbeddingTokenSim(emb, ModifiedVectorSim(CosineSim(), Bias(1), Scale(0.5)))`.  The other VectorSims,
-chains over contextual embeddings and the token-similarity modifier combinators of the reference are out of scope
-and are rejected explicitly rather than ignored; the tag-weighted variant is a "next" row.
+PNormDistance / EuclideanDistance / ImprovedSqrtCosineSim   vectorian/sim/vector.py:98-167
+A ModifiedVectorSim -- a chain of up to 8 operators on the unclipped output of its source -- runs on the device over static
+embeddings: `EmbeddingTokenSim(emb, ModifiedVectorSim(CosineSim(), Bias(1), Scale(0.5)))`.  Its source, or the
+similarity itself, is CosineSim, PNormDistance or ImprovedSqrtCosineSim (the latter two over static embeddings only, on
+the unmodified vectors): `ModifiedVectorSim(PNormDistance(2), Scale(1 / 12), DistanceToSimilarity())`.  FuzzyJaccardSim,
+DirectionalDistance, user-defined VectorSims, chains over contextual embeddings and the token-similarity modifier combinators of
+the reference are out of scope and are rejected explicitly rather than ignored; the tag-weighted variant is a "next"
+row.
 """
 
 import numpy as np
@@ -42,6 +46,72 @@ class CosineSim(VectorSim):
 	@property
 	def name(self):
 		return "cosine"
+
+
+class ImprovedSqrtCosineSim(VectorSim):
+	"""Sohangir & Wang's improved sqrt-cosine on vectors made non-negative by doubling every feature into max(0, x), max(0, -x)
+	(vectorian/sim/vector.py:98-132); a pair with a zero vector scores 0"""
+
+	@staticmethod
+	def _to_non_negative(x):
+		t = np.repeat(x, 2, axis=-1)
+		t[:, 1::2] = -t[:, 1::2]
+		return np.maximum(0, t)
+
+	def compute(self, a, b, out):
+		a_pos = self._to_non_negative(a.unmodified)
+		b_pos = self._to_non_negative(b.unmodified)
+		num = np.sum(np.sqrt(a_pos[:, np.newaxis] * b_pos[np.newaxis, :]), axis=-1)
+		x = np.sqrt(np.sum(a_pos, axis=-1))
+		y = np.sqrt(np.sum(b_pos, axis=-1))
+		denom = x[:, np.newaxis] * y[np.newaxis, :]
+		with np.errstate(divide="ignore", invalid="ignore"):
+			out[:, :] = num / denom
+		np.nan_to_num(out, copy=False, nan=0)
+
+	@property
+	def name(self):
+		return "improved-sqrt-cosine"
+
+	@property
+	def sim_source(self):
+		"""(kind, float32 argument) of vk_corpus_set_sim_source"""
+		return 2, np.float32(0)   # core.VK_SIMSRC_SQRT_COSINE
+
+
+class PNormDistance(VectorSim):
+	"""the p-norm of the difference of the unmodified vectors (vectorian/sim/vector.py:135-160).  A DISTANCE: combine it with
+	DistanceToSimilarity (or RadialBasis) in a ModifiedVectorSim"""
+
+	def __init__(self, p: float = 2):
+		self._p = p
+
+	@property
+	def p(self):
+		return self._p
+
+	def compute(self, a, b, out):
+		d = a.unmodified[:, np.newaxis] - b.unmodified[np.newaxis, :]
+		d = np.sum(np.power(np.abs(d), self._p), axis=-1)
+		d = np.power(d, 1 / self._p)
+		out[:, :] = d  # distance, not a similarity
+
+	@property
+	def name(self):
+		return f"p-norm({self._p})"
+
+	@property
+	def sim_source(self):
+		"""(kind, float32 argument) of vk_corpus_set_sim_source"""
+		return 1, np.float32(self._p)   # core.VK_SIMSRC_PNORM
+
+
+class EuclideanDistance(PNormDistance):
+	"""PNormDistance(2).  (The reference's class passes a `scale` its base class does not take and cannot be constructed,
+	vectorian/sim/vector.py:163-167; this one takes no argument.)"""
+
+	def __init__(self):
+		super().__init__(p=2)
 
 
 class ModifiedVectorSim(VectorSim):
