@@ -2,13 +2,13 @@
 """Register / scratch / LDS use of every kernel of one translation unit, from hipcc's resource remarks.
   python tools/kernel_regs.py vectorian_amd/csrc/vk_score_m0.hip [substring-filter] [-- extra hipcc flags]
   python tools/kernel_regs.py --bound    every unit of the bound pass: vk_score_m7 / m7w / m7t (8-bit), m8 / m8w / m8t (6-bit), m9 / m9w / m9t
-                                         (6-bit, compact tiles: DESIGN 11.11), compiled side by side"""
+                                         (6-bit, compact tiles: DESIGN 11.11), m9f (its local-alignment form: DESIGN 11.12), compiled side by side"""
 import os
 import re
 import subprocess
 import sys
 
-BOUND_UNITS = ["vk_score_m%s%s.hip" % (m, w) for m in (7, 8, 9) for w in ("", "w", "t")]
+BOUND_UNITS = ["vk_score_m%s%s.hip" % (m, w) for m in (7, 8, 9) for w in ("", "w", "t")] + ["vk_score_m9f.hip"]
 
 
 def main():

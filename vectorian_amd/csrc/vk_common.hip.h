@@ -1084,15 +1084,26 @@ __device__ __forceinline__ float dp_general_reg(const float *__restrict__ S, int
 // in x and non-increasing in c; fl(x + s) is non-decreasing in x; max is exact and monotone.  By induction over the cells in the
 // order they are computed, every hreg[u] here is >= the same cell there, hence every h, best and the result.  The history needs
 // KT + 1 live rows and R instead of MAXLEN + 1, the table KT + 2 scalars instead of MAXLEN + 1.
-template <int LT, int MAXLEN, int KT, bool FRESH = true>
+// LOC, LQ (the defaults are the function as it was, instruction for instruction):
+//   LOC = VK_DEV_LOCAL: the locality at compile time.  is_local is true and is_global false in every select below, so bprev = bcur =
+//     0, floor0 = 0, best is taken on every row, and the border candidate bcur - wt_border is the per-lane constant 0.0f - wt_border:
+//     the same subtraction of the same operands, made once.  No float operation changes.
+//   LQ < LT: the in-row candidates k >= LQ are left out.  Candidate k of column v comes from column v - k; for v < LQ <= k there is no
+//     such column (wtv[k] = +inf: the candidate is -inf and never the maximum), so the columns v < LQ lose nothing.  The columns
+//     v >= LQ do change -- but a column feeds only columns to its right (the diagonal and the in-row sources are lower lanes) and its
+//     own later rows, so no column v < LQ ever reads them, and with len_t <= LQ the final `v < a.len_t` select drops them: exact.
+#define VK_DP_LOC_RUNTIME (-1)
+template <int LT, int MAXLEN, int KT, bool FRESH = true, int LOC = VK_DP_LOC_RUNTIME, int LQ = LT>
 __device__ __forceinline__ float dp_general_tail_reg(const float *__restrict__ S, int rowbase, int len, int maxlen, int v,
 	const DpArgs &a, const float (&wsr)[KT + 2], const float (&wtr)[LT]) {
 	static_assert(KT >= 1 && KT < MAXLEN, "the tail begins inside the table");
-	int loc = a.locality, vsel = v;
+	static_assert(LQ >= 1 && LQ <= LT, "the in-row columns are columns of the strip");
+	static_assert(LOC == VK_DP_LOC_RUNTIME || LOC == VK_DEV_LOCAL, "the one compile-time locality is local");
+	int loc = LOC == VK_DP_LOC_RUNTIME ? a.locality : LOC, vsel = v;
 	if constexpr (FRESH) {
-		asm volatile("" : "+v"(loc));
+		if constexpr (LOC == VK_DP_LOC_RUNTIME) asm volatile("" : "+v"(loc));
 		asm volatile("" : "+v"(vsel));
-		loc = __builtin_amdgcn_readfirstlane(loc);
+		if constexpr (LOC == VK_DP_LOC_RUNTIME) loc = __builtin_amdgcn_readfirstlane(loc);
 	}
 	const bool is_local = loc == VK_DEV_LOCAL;
 	const bool is_global = loc == VK_DEV_GLOBAL;
@@ -1104,7 +1115,7 @@ __device__ __forceinline__ float dp_general_tail_reg(const float *__restrict__ S
 
 	float wtv[16];
 #pragma unroll
-	for (int k = 1; k < LT; k++) wtv[k] = vsel >= k ? wtr[k] : __builtin_inff();
+	for (int k = 1; k < LQ; k++) wtv[k] = vsel >= k ? wtr[k] : __builtin_inff();
 
 	float hreg[MAXLEN + 1];   // (fully unrolled: a row is dead once R has taken it, KT + 1 rows after it was made)
 	float h = is_global ? -wt_border0 : 0.0f;
@@ -1127,21 +1138,21 @@ __device__ __forceinline__ float dp_general_tail_reg(const float *__restrict__ S
 				c = fmaxf(c, R - c_tail);
 			}
 			float hc = fmaxf(c, bcur - wt_border);
-			if (LT > 1) hc = fmaxf(hc, dpp_zero<0x111>(c) - wtv[1]);
-			if (LT > 2) hc = fmaxf(hc, dpp_zero<0x112>(c) - wtv[2]);
-			if (LT > 3) hc = fmaxf(hc, dpp_zero<0x113>(c) - wtv[3]);
-			if (LT > 4) hc = fmaxf(hc, dpp_zero<0x114>(c) - wtv[4]);
-			if (LT > 5) hc = fmaxf(hc, dpp_zero<0x115>(c) - wtv[5]);
-			if (LT > 6) hc = fmaxf(hc, dpp_zero<0x116>(c) - wtv[6]);
-			if (LT > 7) hc = fmaxf(hc, dpp_zero<0x117>(c) - wtv[7]);
-			if (LT > 8) hc = fmaxf(hc, dpp_zero<0x118>(c) - wtv[8]);
-			if (LT > 9) hc = fmaxf(hc, dpp_zero<0x119>(c) - wtv[9]);
-			if (LT > 10) hc = fmaxf(hc, dpp_zero<0x11a>(c) - wtv[10]);
-			if (LT > 11) hc = fmaxf(hc, dpp_zero<0x11b>(c) - wtv[11]);
-			if (LT > 12) hc = fmaxf(hc, dpp_zero<0x11c>(c) - wtv[12]);
-			if (LT > 13) hc = fmaxf(hc, dpp_zero<0x11d>(c) - wtv[13]);
-			if (LT > 14) hc = fmaxf(hc, dpp_zero<0x11e>(c) - wtv[14]);
-			if (LT > 15) hc = fmaxf(hc, dpp_zero<0x11f>(c) - wtv[15]);
+			if (LQ > 1) hc = fmaxf(hc, dpp_zero<0x111>(c) - wtv[1]);
+			if (LQ > 2) hc = fmaxf(hc, dpp_zero<0x112>(c) - wtv[2]);
+			if (LQ > 3) hc = fmaxf(hc, dpp_zero<0x113>(c) - wtv[3]);
+			if (LQ > 4) hc = fmaxf(hc, dpp_zero<0x114>(c) - wtv[4]);
+			if (LQ > 5) hc = fmaxf(hc, dpp_zero<0x115>(c) - wtv[5]);
+			if (LQ > 6) hc = fmaxf(hc, dpp_zero<0x116>(c) - wtv[6]);
+			if (LQ > 7) hc = fmaxf(hc, dpp_zero<0x117>(c) - wtv[7]);
+			if (LQ > 8) hc = fmaxf(hc, dpp_zero<0x118>(c) - wtv[8]);
+			if (LQ > 9) hc = fmaxf(hc, dpp_zero<0x119>(c) - wtv[9]);
+			if (LQ > 10) hc = fmaxf(hc, dpp_zero<0x11a>(c) - wtv[10]);
+			if (LQ > 11) hc = fmaxf(hc, dpp_zero<0x11b>(c) - wtv[11]);
+			if (LQ > 12) hc = fmaxf(hc, dpp_zero<0x11c>(c) - wtv[12]);
+			if (LQ > 13) hc = fmaxf(hc, dpp_zero<0x11d>(c) - wtv[13]);
+			if (LQ > 14) hc = fmaxf(hc, dpp_zero<0x11e>(c) - wtv[14]);
+			if (LQ > 15) hc = fmaxf(hc, dpp_zero<0x11f>(c) - wtv[15]);
 			hreg[u] = hc;
 			h = act ? hc : h;
 			if (is_local || last_col) best = fmaxf(best, h);
@@ -1153,6 +1164,82 @@ __device__ __forceinline__ float dp_general_tail_reg(const float *__restrict__ S
 	else m = v < a.len_t ? fmaxf(h, last_col ? best : 0.0f) : 0.0f;
 	m = row_max_to_lane15(m);
 	return (is_global) ? m : fmaxf(m, 0.0f);
+}
+
+// dp_general_tail_reg<LT, 32, KT, true, VK_DEV_LOCAL, LQ> for a slice of exactly 32 tokens in a group whose longest slice has 32, as
+// straight-line code: the bound pass over full groups (the caller tests the group, vk_score_body.hip.inc).  Line by line against
+// that function with len = maxlen = 32:
+//   `if (u <= maxlen)` holds for every u <= 32: no branch.  act = (u <= len) is true on every row:
+//     s     the strip cell S[(rowbase + u - 1) * LT + v]: the same address, here the row pointer plus the constant (u - 1) * LT;
+//     h     `h = act ? hc : h` is h = hc, so `best = max(best, h)` is max(best, hc): the same operands;
+//   diag    dpp_f<SHR1>(bprev, hreg[u - 1]) with bprev = 0 keeps 0 in the lane without a source; dpp_zero<SHR1> reads 0 there: the same
+//           value in every lane, and diag + s the same addition (the move folds into it);
+//   c       max(diag + s, floor0 = 0), then the candidates k <= KT, then R - c_tail: the same operations in the same order;
+//   hc      max(c, border) with border = 0.0f - wt_border, what `bcur - wt_border` is with bcur = 0; then the in-row candidates
+//           k < LQ in the same order with the same wtv;
+//   the end `v < a.len_t ? best : 0`, row_max_to_lane15, max(m, 0): the local branch of the other's end.
+// Every float operation on a column v < LQ is the other function's, on the same operands, in the same order.  vsel gets the same asm
+// treatment: the in-row costs live inside the call only.
+// The strip is read in batches of eight rows behind scheduling barriers: unhindered, the compiler hoists all 32 reads over the DP
+// and the kernel leaves its register budget.
+template <int LT, int LQ, int KT>
+__device__ __forceinline__ float dp_tail_local_full(const float *__restrict__ S, int rowbase, int v, const DpArgs &a,
+	const float (&wsr)[KT + 2], const float (&wtr)[LT]) {
+	static_assert(KT >= 1 && KT < 32, "the tail begins inside the table");
+	static_assert(LQ >= 1 && LQ <= LT, "the in-row columns are columns of the strip");
+	constexpr int BATCH = 8;
+	int vsel = v;
+	asm volatile("" : "+v"(vsel));
+	const float border = 0.0f - a.wt[v + 1];
+	const float c_tail = wsr[KT + 1];
+
+	float wtv[16];
+#pragma unroll
+	for (int k = 1; k < LQ; k++) wtv[k] = vsel >= k ? wtr[k] : __builtin_inff();
+
+	const float *row = S + rowbase * LT + v;
+	float hreg[33];
+	float sv[BATCH];
+	hreg[0] = 0.0f;
+	float R = 0.0f;
+	float best = 0.0f;
+#pragma unroll
+	for (int u = 1; u <= 32; u++) {
+		if ((u - 1) % BATCH == 0) {
+			__builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+			for (int i = 0; i < BATCH; i++) sv[i] = row[(u - 1 + i) * LT];
+			__builtin_amdgcn_sched_barrier(0);
+		}
+		float c = fmaxf(dpp_zero<0x111>(hreg[u - 1]) + sv[(u - 1) % BATCH], 0.0f);
+#pragma unroll
+		for (int k = 1; k <= (u < KT ? u : KT); k++) c = fmaxf(c, hreg[u - k] - wsr[k]);
+		if (u > KT) {
+			if (u > KT + 1) R = fmaxf(R, hreg[u - KT - 1]);
+			c = fmaxf(c, R - c_tail);
+		}
+		float hc = fmaxf(c, border);
+		if (LQ > 1) hc = fmaxf(hc, dpp_zero<0x111>(c) - wtv[1]);
+		if (LQ > 2) hc = fmaxf(hc, dpp_zero<0x112>(c) - wtv[2]);
+		if (LQ > 3) hc = fmaxf(hc, dpp_zero<0x113>(c) - wtv[3]);
+		if (LQ > 4) hc = fmaxf(hc, dpp_zero<0x114>(c) - wtv[4]);
+		if (LQ > 5) hc = fmaxf(hc, dpp_zero<0x115>(c) - wtv[5]);
+		if (LQ > 6) hc = fmaxf(hc, dpp_zero<0x116>(c) - wtv[6]);
+		if (LQ > 7) hc = fmaxf(hc, dpp_zero<0x117>(c) - wtv[7]);
+		if (LQ > 8) hc = fmaxf(hc, dpp_zero<0x118>(c) - wtv[8]);
+		if (LQ > 9) hc = fmaxf(hc, dpp_zero<0x119>(c) - wtv[9]);
+		if (LQ > 10) hc = fmaxf(hc, dpp_zero<0x11a>(c) - wtv[10]);
+		if (LQ > 11) hc = fmaxf(hc, dpp_zero<0x11b>(c) - wtv[11]);
+		if (LQ > 12) hc = fmaxf(hc, dpp_zero<0x11c>(c) - wtv[12]);
+		if (LQ > 13) hc = fmaxf(hc, dpp_zero<0x11d>(c) - wtv[13]);
+		if (LQ > 14) hc = fmaxf(hc, dpp_zero<0x11e>(c) - wtv[14]);
+		if (LQ > 15) hc = fmaxf(hc, dpp_zero<0x11f>(c) - wtv[15]);
+		hreg[u] = hc;
+		best = fmaxf(best, hc);
+	}
+	float m = v < a.len_t ? best : 0.0f;
+	m = row_max_to_lane15(m);
+	return fmaxf(m, 0.0f);
 }
 
 // Relaxed Word Mover's Distance, injective form (vectorian/core/cpp/alignment/wmd.h:287-416 with

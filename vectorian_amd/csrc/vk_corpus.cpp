@@ -684,6 +684,14 @@ int vk_bound_pass_tail(vk_corpus_t *c, int32_t *k) {
 	return VK_OK;
 }
 
+// Internal (tests; not part of the ABI): 1 where the last query's bound pass ran vk_score_local_kernel (the compact 6-bit shadow, general
+// gaps under the flat tail, local alignment, VK_BOUND_DP not `generic`: DESIGN 11.12), else 0
+int vk_bound_pass_dp(vk_corpus_t *c, int32_t *out) {
+	if (!c || !out) return fail(VK_ERR_INVALID, "null argument");
+	*out = c->bp.ran ? (int32_t)c->bp.fast_dp : 0;
+	return VK_OK;
+}
+
 // Internal (tests; not part of the ABI): the handle's shadow as the device holds it.  format[5]: bits (0: no shadow, the rest zero
 // then), K-steps per tile, live quarters of the last K-step, bytes per tile, tiles (the zero tile behind the corpus included);
 // nx[2]: the corpus-wide constants N and X.  out (null: none wanted): the bytes of tiles tile0 .. tile0 + n - 1.

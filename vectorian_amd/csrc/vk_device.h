@@ -445,6 +445,10 @@ hipError_t vk_launch_table(const uint8_t *etiles, const uint8_t *qtile, int32_t 
 hipError_t vk_launch_score(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
 int32_t vk_score_m8t_tail_k(void);   // K of the flat-tailed bound kernels over the 6-bit shadow (vk_score_m8t.hip) ...
 int32_t vk_score_m7t_tail_k(void);   // ... and over the 8-bit shadow (vk_score_m7t.hip)
+// the bound pass over the compact 6-bit shadow, GAP 8 under local alignment (vk_score_m9f.hip): whether vk_launch_score_m9t
+// hands a launch to vk_score_local_kernel (gap mode, locality, query length, VK_BOUND_DP), and that launch
+int32_t vk_score_m9f_takes(const VkScoreParams *p);
+hipError_t vk_launch_score_m9f(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
 hipError_t vk_launch_span(const VkScoreParams *p, hipStream_t stream);
 hipError_t vk_launch_score_batch(const VkScoreBatchParams *p, int32_t lt, size_t smem, hipStream_t stream);
 hipError_t vk_launch_topk_scores(const float *scores, int64_t n, float min_score, int32_t k, uint64_t *out,

@@ -232,6 +232,7 @@ struct vk_corpus : vk_corpus_shape {
 		VkScoreParams full{}; int full_grid = 0; size_t full_smem = 0;   // the exact pass of the last query (its workspaces stay until the next)
 		int64_t ran = 0, round1 = 0, round2 = 0, fell_back = 0;           // the last query: bound pass ran, candidates of the rounds, full pass after all
 		int64_t tail_k = 0;                                                // ... under a slice-gap table flat beyond this many entries (0: the caller's table)
+		int64_t fast_dp = 0;                                               // ... on vk_score_local_kernel (vk_score_m9f.hip)
 		int64_t queries = 0, fallbacks = 0, survivors = 0;                // since the handle was made
 		vk_host::bound_backoff backoff;                                    // default mode: when the handle stops trying (vk_bound_host.h)
 	} bp;

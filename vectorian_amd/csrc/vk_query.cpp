@@ -229,6 +229,8 @@ static int score_bounded(vk_corpus *c, const VkScoreParams &p, int grid, size_t 
 		pb.bound_tail_cost = vk_host::bound_tail_cost(w, K, rows);
 		b.tail_k = K;
 	}
+	// the launch vk_launch_score_m9t hands to vk_score_local_kernel: asked here as it is asked there (vk_bound_pass_dp reports it)
+	b.fast_dp = sf.bits == 6 && sf.compact && vk_score_m9f_takes(&pb) ? 1 : 0;
 	VK_HIP(vk_launch_score(&pb, grid, smem_bound, st));
 	VK_HIP(hipEventRecord(c->ev[2], st));
 	c->ev2_recorded = true;
@@ -286,7 +288,7 @@ static int score_bounded(vk_corpus *c, const VkScoreParams &p, int grid, size_t 
 static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_host_keep &keep) {
 	int rc = VK_OK;
 	VK_HIP(hipSetDevice(c->device));
-	c->bp.pruned = false; c->bp.ran = c->bp.round1 = c->bp.round2 = c->bp.fell_back = c->bp.tail_k = 0;
+	c->bp.pruned = false; c->bp.ran = c->bp.round1 = c->bp.round2 = c->bp.fell_back = c->bp.tail_k = c->bp.fast_dp = 0;
 	for (int64_t &x : c->query_route) x = -1;
 	if (q->len_t > VK_MAX_QUERY_LEN) return vk_longq_query(c, q, out, keep);   // 65 .. 512 tokens (vk_longq_host.cpp)
 	hipStream_t st = c->stream;

@@ -1,5 +1,5 @@
 // vk_score_m9.hip -- vk_score_kernel, MODE 9: the bound pass over the compact 6-bit (E2M3) shadow (see vk_score.hip.h);
-// the 64-row register history of general gaps is in vk_score_m9w.hip, the flat-tailed forms in vk_score_m9t.hip.
+// the 64-row register history of general gaps is in vk_score_m9w.hip, the flat-tailed forms in vk_score_m9t.hip (and, under local alignment, vk_score_m9f.hip).
 // MODE 8's kernels with another load side (load_tile_fp6<., true>, vk_common.hip.h): 3,712-byte tiles, seven loads per tile.  The budget
 // is vk_score_m8.hip's: every form here allocates 104 VGPRs without scratch at two tiles per trip (tools/kernel_regs.py
 // --bound); tests/test_bound_compact_registers.py holds them to it.

@@ -5,7 +5,10 @@
 #define VK_SCORE_VGPRS 104
 #include "vk_score.hip.h"
 
+// GAP 8 under local alignment for a query of 1 .. 16 tokens has a kernel of its own (vk_score_m9f.hip) unless
+// VK_BOUND_DP=generic; everything else -- global and semiglobal, GAP 9 -- keeps vk_score_kernel
 extern "C" hipError_t vk_launch_score_m9t(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream) {
+	if (vk_score_m9f_takes(p)) return vk_launch_score_m9f(p, grid, smem_bytes, stream);
 	switch (p->gap_mode) {
 	case 8: return launch_score_lt<9, VK_DEV_FP6_STEPS, false, 8>(*p, grid, smem_bytes, stream);
 	case 9: return launch_score_lt<9, VK_DEV_FP6_STEPS, false, 9>(*p, grid, smem_bytes, stream);
