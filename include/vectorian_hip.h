@@ -283,6 +283,42 @@ int vk_corpus_set_sim_ops(vk_corpus_t *c, const int32_t *kinds, const float *arg
  * of the rows (they are gone by then).  VK_SIMSRC_COSINE is accepted at any time. */
 enum { VK_SIMSRC_COSINE = 0, VK_SIMSRC_PNORM = 1, VK_SIMSRC_SQRT_COSINE = 2 };
 int vk_corpus_set_sim_source(vk_corpus_t *c, int32_t kind, float arg);
+/* Token similarity combinators over several static embeddings (MixedTokenSimilarity, MaximumTokenSimilarity and -- see below --
+ * MinimumTokenSimilarity of vectorian/sim/modifier.py), VK_LAYOUT_STATIC only.  The reference builds every operand's matrix completely
+ * -- VectorSim, chain, sim[id(t_j)][j] = 1, clip -- and combines the CLIPPED matrices cell by cell, without another clip
+ * (metric/modifier.cpp:18-74).  Here every operand fills a per-query table of its own and vk_table_mix_kernel combines them into the
+ * handle's table, whose cell is then the canonical cell of every route (as under vk_corpus_set_sim_source).
+ *   VK_SIMMIX_AVERAGE: np.average(operands, axis=0, weights=w) in float64 -- sum_m double(S_m) * w_m in operand order over the sum of
+ *     the weights in the same order, rounded to float once;
+ *   VK_SIMMIX_MAXIMUM: the cell-wise maximum (weights NULL).  Upstream's MinimumTokenSimilarity computes the maximum too
+ *     (ExtremumTokenSimilarity.__call__ uses np.argmax for both), so there is no minimum here.
+ * The arithmetic is stated in csrc/vk_sim_mix_host.h.  Operand 0 is the handle itself: its d, its rows (vk_corpus_append_vectors), its
+ * vk_corpus_set_sim_source / vk_corpus_set_sim_ops.  A cosine operand of a mixed handle fills its table in the canonical arithmetic
+ * (four double sums), not the matrix pipe's.  Call before the first vk_corpus_append_vectors.  Views and filtered corpora share the
+ * operands' rows and copy the combinator.  Batches (vk_query_batch) on such a handle run query by query.
+ * VK_ERR_INVALID: unknown kind; n_operands outside 2 .. VK_MAX_SIM_OPERANDS; AVERAGE with NULL weights, a weight that is not finite
+ * or < 0, weights that do not sum to more than 0.  VK_ERR_UNSUPPORTED: VK_LAYOUT_CONTEXTUAL.  VK_ERR_STATE: after an append.
+ * VK_ALG_WRD on a mixed handle: VK_ERR_UNSUPPORTED (the reference leaves a combinator's magnitudes unwritten). */
+#define VK_MAX_SIM_OPERANDS 4
+enum { VK_SIMMIX_NONE = 0, VK_SIMMIX_AVERAGE = 1, VK_SIMMIX_MAXIMUM = 2 };
+int vk_corpus_set_sim_mix(vk_corpus_t *c, int32_t kind, int32_t n_operands, const double *weights);
+/* Operand i (1 .. n_operands - 1) of a mixed handle: the width of its embedding, its source with its argument (VK_SIMSRC_*, validated
+ * as by vk_corpus_set_sim_source: d_i <= 1024 under a source that is not the cosine) and its chain (as vk_corpus_set_sim_ops).  The
+ * first call, before the operand's first rows, allocates its tiles (and the fp32 copy of the unmodified rows under such a source).
+ * Later calls with the same d_i change source and chain of THIS handle at any time, as the two setters do for operand 0 -- a source
+ * beside the cosine only where the operand keeps that copy.  VK_ERR_STATE: no combinator set; another width, or a source that needs
+ * the unmodified rows on an operand that did not keep them, after the operand's first rows. */
+int vk_corpus_set_sim_operand(vk_corpus_t *c, int32_t i, int32_t d_i, int32_t src_kind, float src_arg,
+	const int32_t *kinds, const float *args, int32_t n_ops);
+/* The vocabulary rows of operand i, host memory [n_rows x d_i], in order; vocab_size rows in total before vk_corpus_finalize (else
+ * VK_ERR_STATE there).  Packed as the handle's own rows: unit tiles in the handle's precision, and the fp32 copy of the unmodified
+ * rows beside them when the operand's source needs it (both counted by vk_corpus_device_bytes). */
+int vk_corpus_append_operand_vectors(vk_corpus_t *c, int32_t i, const void *rows, int64_t n_rows, int32_t dtype, int32_t normalize);
+/* Operand i's rows of the NEXT vk_query on this handle, [len_t x d_i], copied at the call and consumed by that query (whether it
+ * succeeds or not).  Called k times for one operand before a vk_query_batch, the k-th call belongs to the batch's k-th query.  A query
+ * on a mixed handle that lacks an operand's rows, or whose len_t differs from theirs, ends with VK_ERR_STATE before anything is
+ * enqueued.  Calls on one handle are the caller's to serialise: set the operands and run the query under one lock. */
+int vk_corpus_set_query_operand(vk_corpus_t *c, int32_t i, const void *q_vectors, int32_t len_t, int32_t q_dtype, int32_t q_normalize);
 int vk_corpus_free(vk_corpus_t *c);
 int vk_corpus_device_bytes(const vk_corpus_t *c, int64_t *bytes);
 

@@ -42,6 +42,9 @@ def main():
 	ap.add_argument("--sim-source", action="append", default=[], metavar="KIND[:ARG]", help="static layout, may be repeated: after the plain run, the same "
 		"queries under this source (vk_corpus_set_sim_source) -- pnorm:P under Scale(s), DistanceToSimilarity with the median cell at one half, "
 		"sqrt-cosine bare -- reported beside the cosine as sim_sources: prepare_ms and the whole query's wall time, each query's")
+	ap.add_argument("--sim-mix", action="store_true", help="static layout: after the plain run, the same queries on a second, mixed handle "
+		"(vk_corpus_set_sim_mix): a two-operand AVERAGE, weights 2 : 1, of the cosine over this vocabulary and the cosine over a second one of "
+		"the same width -- reported beside the cosine as sim_mix: prepare_ms and the whole query's wall time, each query's")
 	args = ap.parse_args()
 
 	import torch
@@ -123,6 +126,34 @@ def main():
 				by_source[text] = each()
 				corpus.set_sim_ops([])
 			corpus.set_sim_source(core.VK_SIMSRC_COSINE)
+		by_mix = {}
+		if args.sim_mix:
+			def each_on(handle, operands):
+				"""prepare_ms and wall time of every query after the warm-up"""
+				out = []
+				for i in range(args.warmup + args.steps):
+					q = qs[i]
+					more = dict(q_operand_vectors=[np.ascontiguousarray(E2[q[1]], dtype=np.float32)]) if operands else {}
+					torch.cuda.synchronize()
+					t0 = time.perf_counter()
+					handle.query(q[0], q_token_ids=q[1], algorithm=alg, locality=loc, gap_s=gap, gap_t=gap, max_matches=args.k, want_flow=args.alg == "align", **more)
+					ms = (time.perf_counter() - t0) * 1e3
+					if i >= args.warmup:
+						out.append((handle.last_timings()["prepare_ms"], ms))
+				return {"prepare_ms_each": [a for a, _ in out], "query_ms_each": [b for _, b in out]}
+			E2 = np.random.default_rng(2).standard_normal((V, args.d)).astype(np.float32)
+			mixed = core.Corpus(layout=core.VK_LAYOUT_STATIC, d=args.d, n_tokens=n_tok, n_sentences=args.sentences, vocab_size=V)
+			mixed.set_sim_mix(core.VK_SIMMIX_AVERAGE, 2, [2, 1])
+			mixed.set_sim_operand(1, args.d)
+			mixed.append_operand_vectors(1, E2, normalize=True)
+			mixed.append_vectors(E, normalize=True)
+			mixed.set_token_ids(ids)
+			mixed.set_sentences(off)
+			mixed.finalize()
+			by_mix["cosine"] = each_on(corpus, False)
+			by_mix["average of two cosines"] = each_on(mixed, True)
+			by_mix["cosine again"] = each_on(corpus, False)
+			mixed.close()
 		score_ms = float(np.mean([p["score_ms"] for p in ph]))
 		cells = float(n_tok) * args.len_t
 		print(json.dumps({"layout": "static", "alg": args.alg, "gap": args.gap, "d": args.d, "len_t": args.len_t, "len_s": [args.min_len, args.max_len],
@@ -132,7 +163,7 @@ def main():
 			"phases_ms_mean": {k: float(np.mean([p[k] for p in ph])) for k in ph[0]},
 			**({"sim_ops": args.sim_ops, "phases_ms_mean_sim_ops": {k: float(np.mean([p[k] for p in ph_ops])) for k in ph_ops[0]},
 				"prepare_ms_each": [p["prepare_ms"] for p in ph], "prepare_ms_each_sim_ops": [p["prepare_ms"] for p in ph_ops]} if ph_ops else {}),
-			**({"sim_sources": by_source} if by_source else {})}))
+			**({"sim_sources": by_source} if by_source else {}), **({"sim_mix": by_mix} if by_mix else {})}))
 		corpus.close()
 		return
 	corpus = core.Corpus(layout=core.VK_LAYOUT_CONTEXTUAL, d=args.d, n_tokens=n_tok, n_sentences=args.sentences,

@@ -37,6 +37,9 @@ VK_MAX_SIM_OPS = 8
 VK_SIMOP_BIAS, VK_SIMOP_SCALE, VK_SIMOP_THRESHOLD, VK_SIMOP_ONE_MINUS, VK_SIMOP_POWER, VK_SIMOP_RADIAL_BASIS = 0, 1, 2, 3, 4, 5
 # the VectorSim a chain runs on (vk_corpus_set_sim_source; vectorian_amd/sim.py states each one)
 VK_SIMSRC_COSINE, VK_SIMSRC_PNORM, VK_SIMSRC_SQRT_COSINE = 0, 1, 2
+# token similarity combinators over several static embeddings (vk_corpus_set_sim_mix; vectorian_amd/modifier.py states each one)
+VK_MAX_SIM_OPERANDS = 4
+VK_SIMMIX_NONE, VK_SIMMIX_AVERAGE, VK_SIMMIX_MAXIMUM = 0, 1, 2
 
 
 class Locality(enum.IntEnum):
@@ -99,6 +102,7 @@ class _Timings(C.Structure):
 EXPORTS = [
 	"vk_abi_version", "vk_last_error", "vk_init", "vk_device_count", "vk_corpus_view",
 	"vk_corpus_create", "vk_corpus_append_vectors", "vk_corpus_set_token_ids", "vk_corpus_set_token_pos", "vk_corpus_set_token_tags", "vk_corpus_filter", "vk_corpus_set_sim_ops", "vk_corpus_set_sim_source",
+	"vk_corpus_set_sim_mix", "vk_corpus_set_sim_operand", "vk_corpus_append_operand_vectors", "vk_corpus_set_query_operand",
 	"vk_corpus_set_sentences", "vk_corpus_set_slices", "vk_corpus_finalize", "vk_corpus_free", "vk_corpus_device_bytes",
 	"vk_query", "vk_query_batch", "vk_last_scores", "vk_last_timings", "vk_merge_topk",
 	"vk_record_words", "vk_pack_records", "vk_merge_records", "vk_rwmd_from_rows"]
@@ -152,6 +156,10 @@ def lib():
 		L.vk_corpus_filter.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p)]
 		L.vk_corpus_set_sim_ops.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
 		L.vk_corpus_set_sim_source.argtypes = [C.c_void_p, C.c_int32, C.c_float]
+		L.vk_corpus_set_sim_mix.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+		L.vk_corpus_set_sim_operand.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_int32]
+		L.vk_corpus_append_operand_vectors.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32]
+		L.vk_corpus_set_query_operand.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
 		L.vk_corpus_device_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
 		L.vk_query.argtypes = [C.c_void_p, C.POINTER(_QueryDesc), C.POINTER(_TopkOut)]
 		L.vk_query_batch.argtypes = [C.c_void_p, C.POINTER(_QueryDesc), C.c_int32, C.POINTER(_TopkOut)]

@@ -439,14 +439,16 @@ static int query_batch_body(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_q
 			q.rwmd_normalize_bow == qs[0].rwmd_normalize_bow && q.max_matches == qs[0].max_matches &&
 			q.min_score == qs[0].min_score && q.boost == qs[0].boost && !q.tag_weights;
 	}
-	// a source that is not the cosine (vk_corpus_set_sim_source): the batch's 16-bit table is the cosine's -- query by query
-	const bool sourced = c->sim_src.kind != VK_SIMSRC_COSINE;
+	// a source that is not the cosine (vk_corpus_set_sim_source) or a combinator (vk_corpus_set_sim_mix): the batch's 16-bit table is
+	// the cosine's -- query by query
+	const bool sourced = c->table_is_canonical();
 	if (sourced) gemm = false;
 	if (!gemm) {
 		const int rcb = sourced ? VK_ERR_UNSUPPORTED : query_batch_shared_pass(c, qs, n_queries, outs, keep);
 		if (rcb != VK_ERR_UNSUPPORTED) return rcb;
 		c->batch_state[VK_BS_ROUTE] = 1;
 		for (int i = 0; i < n_queries; i++) {
+			c->q_operand_at = i;   // (a mixed handle: the i-th rows vk_corpus_set_query_operand left for each operand)
 			const int rc = vk_query(c, &qs[i], &outs[i]);   // polls the query's abort flag
 			if (rc) {
 				for (int r = i; r < n_queries; r++) outs[r].n_out = 0;
@@ -747,6 +749,9 @@ extern "C" {
 
 int vk_query_batch(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_queries, vk_topk_out *outs) {
 	if (!c || !qs || !outs || n_queries < 0) return fail(VK_ERR_INVALID, "null argument");
+	// the rows vk_corpus_set_query_operand left belong to this batch, however it ends
+	struct consume { vk_corpus_t *c; ~consume() { c->in_batch = false; c->drop_query_operands(); } } consumed{c};
+	c->in_batch = true;
 	if (n_queries == 0) return VK_OK;
 	if (qs[0].abort && *qs[0].abort) {
 		for (int i = 0; i < n_queries; i++) outs[i].n_out = 0;

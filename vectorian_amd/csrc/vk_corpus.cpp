@@ -465,6 +465,9 @@ int vk_corpus_finalize(vk_corpus_t *c) {
 	if (c->rows_appended != c->rows_total) return fail(VK_ERR_STATE, "not all vectors were appended");
 	if (!c->have_sent) return fail(VK_ERR_STATE, "sentence spans were not set");
 	if (c->desc.layout == VK_LAYOUT_STATIC && !c->have_ids) return fail(VK_ERR_STATE, "token ids were not set");
+	for (int m = 1; c->mixed() && m < c->sim_mix.n; m++)
+		if (c->operands[m - 1].rows_appended != c->rows_total)
+			return fail(VK_ERR_STATE, "mixed handle: operand " + std::to_string(m) + " has " + std::to_string(c->operands[m - 1].rows_appended) + " of " + std::to_string(c->rows_total) + " vocabulary rows (vk_corpus_append_operand_vectors)");
 	VK_HIP(hipSetDevice(c->device));
 	c->d_stage.reset();
 	VK_HIP(hipStreamSynchronize(c->stream));
@@ -517,6 +520,127 @@ int vk_corpus_set_sim_source(vk_corpus_t *c, int32_t kind, float arg) {
 		c->device_bytes += (int64_t)bytes;
 	}
 	c->sim_src = vk_host::sim_src{kind, kind == VK_SIMSRC_PNORM ? arg : 0.0f};
+	return VK_OK;
+}
+
+// The combinator of a mixed handle (vk_sim_mix_host.h): host state, read when a query fills its tables.  Before the first
+// append, as a source is: the operands' rows arrive beside the handle's own.
+int vk_corpus_set_sim_mix(vk_corpus_t *c, int32_t kind, int32_t n_operands, const double *weights) {
+	if (!c) return fail(VK_ERR_INVALID, "null argument");
+	const char *why = "";
+	if (vk_host::sim_mix_check(kind, n_operands, weights, &why) != VK_OK) return fail(VK_ERR_INVALID, std::string("vk_corpus_set_sim_mix: ") + why);
+	if (c->desc.layout != VK_LAYOUT_STATIC)
+		return fail(VK_ERR_UNSUPPORTED, "token similarity combinators run over VK_LAYOUT_STATIC only: this corpus is VK_LAYOUT_CONTEXTUAL");
+	if (c->rows_appended > 0 || c->finalized || c->is_view || c->shares_vectors)
+		return fail(VK_ERR_STATE, "a token similarity combinator is set before the first vk_corpus_append_vectors");
+	for (const auto &op : c->operands)
+		if (op.rows_appended > 0) return fail(VK_ERR_STATE, "a token similarity combinator is set before the first vk_corpus_append_operand_vectors");
+	vk_host::sim_mix mix{};
+	mix.kind = kind; mix.n = n_operands;
+	for (int m = 0; m < n_operands; m++) mix.w[m] = kind == VK_SIMMIX_AVERAGE ? weights[m] : 0.0;
+	c->sim_mix = mix;
+	return VK_OK;
+}
+
+static int mix_operand_of(vk_corpus_t *c, int32_t i, const char *who) {
+	if (!c) return fail(VK_ERR_INVALID, "null argument");
+	if (!c->mixed()) return fail(VK_ERR_STATE, std::string(who) + ": the handle has no combinator (vk_corpus_set_sim_mix)");
+	if (i < 1 || i >= c->sim_mix.n) return fail(VK_ERR_INVALID, std::string(who) + ": operand index must be 1 .. n_operands - 1 (operand 0 is the handle itself)");
+	return VK_OK;
+}
+
+// An operand's width, source and chain; allocates its tiles as vk_corpus_create allocates the handle's, and -- under a source that is
+// not the cosine -- the fp32 copy of the unmodified rows as vk_corpus_set_sim_source does
+int vk_corpus_set_sim_operand(vk_corpus_t *c, int32_t i, int32_t d_i, int32_t src_kind, float src_arg, const int32_t *kinds, const float *args, int32_t n_ops) {
+	if (int rc = mix_operand_of(c, i, "vk_corpus_set_sim_operand")) return rc;
+	if (n_ops > 0 && (!kinds || !args)) return fail(VK_ERR_INVALID, "null argument");
+	if (d_i < 1 || d_i > 8192) return fail(VK_ERR_INVALID, "embedding dimension out of range");
+	if (vk_host::sim_src_check(src_kind, src_arg) != VK_OK)
+		return fail(VK_ERR_INVALID, src_kind == VK_SIMSRC_PNORM ? "VK_SIMSRC_PNORM: p must be finite and > 0" : "unknown similarity source " + std::to_string(src_kind));
+	int bad = -1;
+	if (vk_host::sim_ops_check(kinds, args, n_ops, &bad) != VK_OK) {
+		if (bad < 0) return fail(VK_ERR_INVALID, "n_ops must be 0 .. VK_MAX_SIM_OPS (8), got " + std::to_string(n_ops));
+		return fail(VK_ERR_INVALID, "similarity operator " + std::to_string(bad) + ": unknown kind or an argument that is not finite");
+	}
+	if (src_kind != VK_SIMSRC_COSINE && d_i > vk_host::kSimSrcMaxD)
+		return fail(VK_ERR_UNSUPPORTED, "similarity sources beside the cosine: rows of at most " + std::to_string(vk_host::kSimSrcMaxD) + " features (the table kernel keeps a query tile in LDS)");
+	vk_corpus::sim_operand &op = c->operands[i - 1];
+	vk_host::sim_ops chain{};
+	chain.n = n_ops;
+	for (int k = 0; k < n_ops; k++) { chain.kind[k] = kinds[k]; chain.arg[k] = args[k]; }
+	// an operand that has its buffers: source and chain are host state, as vk_corpus_set_sim_source / vk_corpus_set_sim_ops are on a
+	// handle that keeps the rows they read -- at any time, on this handle alone
+	if (op.tiles && op.d == d_i && (src_kind == VK_SIMSRC_COSINE || op.raw_rows)) {
+		op.src = vk_host::sim_src{src_kind, src_kind == VK_SIMSRC_PNORM ? src_arg : 0.0f};
+		op.ops = chain;
+		return VK_OK;
+	}
+	if (op.rows_appended > 0 || c->finalized || c->is_view || c->shares_vectors)
+		return fail(VK_ERR_STATE, "an operand's width, and a source beside the cosine, are set before its first vk_corpus_append_operand_vectors: the unmodified rows are gone");
+	VK_HIP(hipSetDevice(c->device));
+	vk_corpus::sim_operand fresh;
+	fresh.d = d_i; fresh.d_pad = (d_i + 15) / 16 * 16;
+	if (c->prec) { fresh.nk32 = fresh.d_pad / 16; fresh.tail = 0; fresh.tile_bytes = fresh.d_pad * 64; }
+	else { fresh.nk32 = (fresh.d_pad + 31) / 32; fresh.tail = (fresh.d_pad % 32) ? 1 : 0; fresh.tile_bytes = fresh.d_pad * 32; }
+	fresh.src = vk_host::sim_src{src_kind, src_kind == VK_SIMSRC_PNORM ? src_arg : 0.0f};
+	fresh.ops = chain;
+	int64_t bytes_before = 0;
+	if (op.tiles) bytes_before += (int64_t)op.tiles->capacity();
+	if (op.raw_rows) bytes_before += (int64_t)op.raw_rows->capacity();
+	const size_t tile_bytes_all = (size_t)c->n_tiles * (size_t)fresh.tile_bytes;
+	fresh.tiles = std::make_shared<vk_devbuf<uint8_t>>();
+	if (int rc = fresh.tiles->reserve(tile_bytes_all, nullptr)) return rc;
+	VK_HIP(hipMemsetAsync(*fresh.tiles, 0, tile_bytes_all, c->stream));
+	size_t raw_all = 0;
+	if (src_kind != VK_SIMSRC_COSINE) {
+		fresh.raw_tile_bytes = (d_i + 15) / 16 * 1024;
+		raw_all = (size_t)c->n_tiles * (size_t)fresh.raw_tile_bytes;
+		fresh.raw_rows = std::make_shared<vk_devbuf<uint8_t>>();
+		if (int rc = fresh.raw_rows->reserve(raw_all, nullptr)) return rc;
+		VK_HIP(hipMemsetAsync(*fresh.raw_rows, 0, raw_all, c->stream));
+	}
+	VK_HIP(hipStreamSynchronize(c->stream));   // (an error above leaves the operand as it was: `fresh` frees what it allocated)
+	op = fresh;
+	c->device_bytes += (int64_t)(tile_bytes_all + raw_all) - bytes_before;   // counted by hand, as raw_rows: the buffers may outlive this handle
+	return VK_OK;
+}
+
+int vk_corpus_append_operand_vectors(vk_corpus_t *c, int32_t i, const void *rows, int64_t n_rows, int32_t dtype, int32_t normalize) {
+	if (int rc = mix_operand_of(c, i, "vk_corpus_append_operand_vectors")) return rc;
+	if (!rows && n_rows > 0) return fail(VK_ERR_INVALID, "null argument");
+	if (c->finalized) return fail(VK_ERR_STATE, "corpus already finalized");
+	if (dtype != VK_F32 && dtype != VK_BF16) return fail(VK_ERR_INVALID, "bad dtype");
+	vk_corpus::sim_operand &op = c->operands[i - 1];
+	if (!op.tiles) return fail(VK_ERR_STATE, "vk_corpus_append_operand_vectors before vk_corpus_set_sim_operand");
+	if (n_rows < 0 || op.rows_appended + n_rows > c->rows_total) return fail(VK_ERR_INVALID, "more rows appended than declared");
+	VK_HIP(hipSetDevice(c->device));
+	const size_t row_bytes = (dtype == VK_F32 ? 4 : 2) * (size_t)op.d;
+	if (int rc = c->d_stage.reserve((size_t)kStageBytes, &c->device_bytes)) return rc;
+	const int64_t rows_per_chunk = std::max<int64_t>(1, kStageBytes / (int64_t)row_bytes);
+	for (int64_t r = 0; r < n_rows; r += rows_per_chunk) {
+		const int64_t nr = std::min(rows_per_chunk, n_rows - r);
+		VK_HIP(hipMemcpyAsync(c->d_stage, (const uint8_t *)rows + (size_t)r * row_bytes, (size_t)nr * row_bytes, hipMemcpyHostToDevice, c->stream));
+		VK_HIP(vk_launch_pack(c->d_stage, dtype == VK_BF16, nr, op.d, op.d_pad, op.rows_appended + r, *op.tiles, nullptr, normalize, c->prec, c->stream));
+		if (op.raw_rows)
+			VK_HIP(vk_launch_pack(c->d_stage, dtype == VK_BF16, nr, op.d, op.raw_tile_bytes / 64, op.rows_appended + r, *op.raw_rows, nullptr, 0, 1, c->stream));
+		VK_HIP(hipStreamSynchronize(c->stream));
+	}
+	op.rows_appended += n_rows;
+	return VK_OK;
+}
+
+int vk_corpus_set_query_operand(vk_corpus_t *c, int32_t i, const void *q_vectors, int32_t len_t, int32_t q_dtype, int32_t q_normalize) {
+	if (int rc = mix_operand_of(c, i, "vk_corpus_set_query_operand")) return rc;
+	if (!q_vectors) return fail(VK_ERR_INVALID, "q_vectors is null");
+	if (q_dtype != VK_F32 && q_dtype != VK_BF16) return fail(VK_ERR_INVALID, "bad q_dtype");
+	if (len_t < 1 || len_t > VK_MAX_LONG_QUERY_LEN) return fail(VK_ERR_INVALID, "len_t must be 1 .. VK_MAX_LONG_QUERY_LEN (512)");
+	const vk_corpus::sim_operand &op = c->operands[i - 1];
+	if (op.d < 1) return fail(VK_ERR_STATE, "vk_corpus_set_query_operand before vk_corpus_set_sim_operand");
+	vk_corpus::mix_operand_bufs::rows rows;
+	rows.len_t = len_t; rows.dtype = q_dtype; rows.normalize = q_normalize;
+	const size_t bytes = (size_t)len_t * (size_t)op.d * (q_dtype == VK_F32 ? 4 : 2);
+	rows.bytes.assign((const uint8_t *)q_vectors, (const uint8_t *)q_vectors + bytes);
+	c->mixop[i - 1].pending.push_back(std::move(rows));
 	return VK_OK;
 }
 
@@ -578,6 +702,8 @@ int vk_corpus_filter(vk_corpus_t *src, uint64_t pos_mask, uint64_t tag_mask, vk_
 			c->vectors_of = src->shares_vectors ? src->vectors_of : src->shared;   // the vocabulary stays alive with this handle
 			c->sim_ops = src->sim_ops;   // the source's similarity (a contextual corpus has no chain)
 			c->sim_src = src->sim_src; c->raw_rows = src->raw_rows; c->raw_tile_bytes = src->raw_tile_bytes;   // ... and the unmodified rows it may read
+			c->sim_mix = src->sim_mix;   // ... and its combinator with the operands' rows
+			for (int m = 0; m < VK_MAX_SIM_OPERANDS - 1; m++) c->operands[m] = src->operands[m];
 			if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return fail(VK_ERR_HIP, "hipStreamCreate failed");
 			for (auto &e : c->ev) if (hipEventCreate(&e) != hipSuccess) return fail(VK_ERR_HIP, "hipEventCreate failed");
 			int r;

@@ -9,6 +9,7 @@
 
 #include "vk_sim_ops_host.h"   // vk_host::sim_ops: the operator chain on the cosine of the static layout, by value in the structs below
 #include "vk_sim_src_host.h"   // vk_host::sim_src: the source the chain runs on (the cosine, a p-norm distance, the sqrt-cosine)
+#include "vk_sim_mix_host.h"   // vk_host::sim_mix: the combinator of a mixed handle's operand tables
 
 #define VK_DEV_LOCAL 0
 #define VK_DEV_GLOBAL 1
@@ -16,6 +17,9 @@
 
 #define VK_DEV_LAYOUT_CONTEXTUAL 0
 #define VK_DEV_LAYOUT_STATIC 1
+// the sim_src of the parameter structs below on a mixed handle (vk_corpus_set_sim_mix), whatever operand 0's source is: not
+// VK_SIMSRC_COSINE, so every restatement site reads the table's cell (static_table_cell)
+#define VK_DEV_SIMSRC_MIXED 3
 
 #define VK_DEV_MAX_SENT_LEN 64        // fused fast path: 4 slices per wave
 #define VK_DEV_MAX_LONG_LEN 512       // longer slices: one per wave, second launch
@@ -372,6 +376,15 @@ struct VkSimSrcArgs {
 	const float *q_abs_sums;
 };
 
+// vk_launch_table_mix: the n operand tables of one query tile (in[0] may be `out`: every cell is read before it is written, by the
+// thread that writes it) into the handle's table, n_cells floats each (a multiple of 4)
+struct VkMixArgs {
+	const float *in[VK_MAX_SIM_OPERANDS];
+	float *out;
+	int64_t n_cells;
+	vk_host::sim_mix mix;
+};
+
 #ifdef __cplusplus
 namespace vk_host { struct shadow_format; }   // vk_bound_host.h
 
@@ -442,6 +455,12 @@ hipError_t vk_launch_filter_gather(const void *src, void *dst, int32_t elem_byte
 hipError_t vk_launch_table(const uint8_t *etiles, const uint8_t *qtile, int32_t n_tiles, int32_t nk32, int32_t tail,
 	int32_t tile_bytes, float *table, const int32_t *q_ids, int32_t len_t, int32_t V, int32_t prec, const vk_host::sim_ops *ops,
 	const VkSimSrcArgs *src, hipStream_t stream);
+// a cosine operand's table of a mixed handle in the canonical arithmetic (vk_canon_table_kernel, vk_mix.hip); then the fix as above
+hipError_t vk_launch_canon_table(const uint8_t *etiles, const uint8_t *qtile, int32_t n_tiles, int32_t nk32, int32_t tail,
+	int32_t tile_bytes, int32_t d, float *table, const int32_t *q_ids, int32_t len_t, int32_t V, int32_t prec, const vk_host::sim_ops *ops,
+	hipStream_t stream);
+hipError_t vk_launch_table_fix(float *table, const int32_t *q_ids, int32_t len_t, int32_t V, hipStream_t stream);
+hipError_t vk_launch_table_mix(const VkMixArgs *a, hipStream_t stream);
 hipError_t vk_launch_score(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
 int32_t vk_score_m8t_tail_k(void);   // K of the flat-tailed bound kernels over the 6-bit shadow (vk_score_m8t.hip) ...
 int32_t vk_score_m7t_tail_k(void);   // ... and over the 8-bit shadow (vk_score_m7t.hip)

@@ -163,6 +163,23 @@ struct vk_corpus_shape {
 	vk_host::sim_src sim_src{};
 	std::shared_ptr<vk_devbuf<uint8_t>> raw_rows;
 	int raw_tile_bytes = 0;
+	// the combinator of a mixed handle (vk_corpus_set_sim_mix; vk_sim_mix_host.h; kind VK_SIMMIX_NONE: none) and its operands 1 ..
+	// sim_mix.n - 1 at operands[0 ..] -- operand 0 is the handle itself.  Inherited like source and chain; the rows are owning buffers
+	// held together like raw_rows
+	vk_host::sim_mix sim_mix{};
+	struct sim_operand {
+		int d = 0, d_pad = 0, nk32 = 0, tail = 0, tile_bytes = 0;   // the operand's own width in the handle's precision (as the fields above)
+		int64_t rows_appended = 0;
+		vk_host::sim_src src{};
+		vk_host::sim_ops ops{};
+		std::shared_ptr<vk_devbuf<uint8_t>> tiles;      // unit rows as tiles, n_tiles of tile_bytes (the zero tile included)
+		std::shared_ptr<vk_devbuf<uint8_t>> raw_rows;   // under a source that is not the cosine: the unmodified rows, fp32 tiles of raw_tile_bytes
+		int raw_tile_bytes = 0;
+	} operands[VK_MAX_SIM_OPERANDS - 1];
+	bool mixed() const { return sim_mix.kind != VK_SIMMIX_NONE; }
+	// what the kernels' sim_src says: not the cosine -- read the table's cell -- under a source of the handle's or a combinator
+	int dev_sim_src() const { return mixed() ? VK_DEV_SIMSRC_MIXED : sim_src.kind; }
+	bool table_is_canonical() const { return dev_sim_src() != VK_SIMSRC_COSINE; }
 };
 
 // vk_corpus::batch_state by index (the internal export vk_batch_state hands the array out in this order; the tests name the
@@ -201,6 +218,18 @@ struct vk_corpus : vk_corpus_shape {
 	vk_devbuf<int32_t> d_qids;
 	vk_devbuf<float> d_table;
 	vk_devbuf<float> d_qraw;      // under a source that is not the cosine: the query's unmodified rows, per tile [16 x d] and 16 sums of |q_k|
+	// a mixed handle (vk_corpus_set_sim_mix), per operand 1 ..: its tables of the running query (sized as d_table is), its query
+	// tiles and -- under a source -- its query's unmodified rows; and the rows vk_corpus_set_query_operand has left for the next
+	// queries, in the order of the calls (vk_query reads entry q_operand_at: 0, or the query's place in a batch run query by query)
+	struct mix_operand_bufs {
+		vk_devbuf<float> table, qraw;
+		vk_devbuf<uint8_t> qtile;
+		struct rows { std::vector<uint8_t> bytes; int32_t len_t = 0, dtype = 0, normalize = 0; };
+		std::vector<rows> pending;
+	} mixop[VK_MAX_SIM_OPERANDS - 1];
+	int q_operand_at = 0;
+	bool in_batch = false;        // vk_query_batch is running its queries one by one: it clears the pending rows, not vk_query
+	void drop_query_operands() { for (auto &m : mixop) m.pending.clear(); q_operand_at = 0; }
 	vk_devbuf<float> d_scores, d_raw, d_boost;
 	vk_devbuf<uint64_t> d_keys[2];
 	vk_devbuf<float> d_out_raw, d_out_sim;   // the winners' outputs: at least VK_MAX_MATCHES of them (grown by a query that asks for more matches)
@@ -287,6 +316,8 @@ int vk_validate_query(const vk_corpus *c, const vk_query_desc *q, const vk_topk_
 int vk_longq_query(vk_corpus *c, const vk_query_desc *q, vk_topk_out *out, vk_host_keep &keep);   // vk_longq_host.cpp
 // bound_tile: with a shadow, the query's tile in the shadow's format and the cells' constants behind it (left empty when a row is not finite)
 void vk_pack_query(const vk_corpus *c, const vk_query_desc *q, std::vector<uint8_t> &tile, float *mags, std::vector<uint8_t> *bound_tile = nullptr);
+// ... the query tiles alone, for rows of any width (an operand of a mixed handle has its own): tile_bytes per tile of d features
+void vk_pack_query_rows(int d, int tile_bytes, int prec, const void *q_vectors, int q_dtype, int q_normalize, int len_t, std::vector<uint8_t> &tile, float *mags);
 
 // ---- steps the query paths share (vk_query.cpp, vk_longq_host.cpp, vk_batch.cpp); the rules without a device are in vk_result_host.h
 namespace {
@@ -298,7 +329,7 @@ template <typename P> void corpus_fields(P &p, const vk_corpus *c) {
 }
 // the handle's operator chain into the structs of the kernels that restate cells of the static layout (the others have no such field)
 // (beside it the kind of the handle's source: not the cosine, and those kernels read the table's cells instead)
-template <typename P> auto sim_ops_field(P &p, const vk_corpus *c, int) -> decltype((void)p.sim_ops) { p.sim_ops = c->sim_ops; p.sim_src = c->sim_src.kind; }
+template <typename P> auto sim_ops_field(P &p, const vk_corpus *c, int) -> decltype((void)p.sim_ops) { p.sim_ops = c->sim_ops; p.sim_src = c->dev_sim_src(); }
 template <typename P> void sim_ops_field(P &, const vk_corpus *, long) {}
 // ... and those of the structs that serve both layouts and both precisions (d_tok_id is null unless the layout is static)
 template <typename P> void corpus_fields_ids(P &p, const vk_corpus *c) {
@@ -397,27 +428,89 @@ int upload_boost(vk_corpus *c, const float *boost, vk_host_keep &keep, hipStream
 // tile's alone) for the table kernel -- per 16 query tokens [16 x d] floats and the 16 sums of |q_k| (vk_host::sim_src_abs_sum) -- into
 // d_qraw, and the arguments of vk_launch_table for tile t
 constexpr size_t vk_source_tile_floats(int d) { return 16 * (size_t)d + 16; }
-int upload_source_query(vk_corpus *c, const vk_query_desc *q, vk_host_keep &keep, hipStream_t st) {
-	const int d = c->desc.d, nq = (q->len_t + 15) / 16;
+int upload_source_rows(vk_corpus *c, int d, const void *q_vectors, int q_dtype, int len_t, vk_devbuf<float> &dst, vk_host_keep &keep, hipStream_t st) {
+	const int nq = (len_t + 15) / 16;
 	const size_t per = vk_source_tile_floats(d);
 	std::vector<float> &rows = keep.vec<float>(per * (size_t)nq);
 	std::fill(rows.begin(), rows.end(), 0.0f);
-	for (int i = 0; i < q->len_t; i++) {
+	for (int i = 0; i < len_t; i++) {
 		float *row = rows.data() + (size_t)(i >> 4) * per + (size_t)(i & 15) * d;
 		for (int k = 0; k < d; k++)
-			row[k] = q->q_dtype == VK_F32 ? ((const float *)q->q_vectors)[(size_t)i * d + k] : bf16_to_f32(((const uint16_t *)q->q_vectors)[(size_t)i * d + k]);
+			row[k] = q_dtype == VK_F32 ? ((const float *)q_vectors)[(size_t)i * d + k] : bf16_to_f32(((const uint16_t *)q_vectors)[(size_t)i * d + k]);
 		rows[(size_t)(i >> 4) * per + 16 * (size_t)d + (size_t)(i & 15)] = vk_host::sim_src_abs_sum(row, d);
 	}
-	if (int rc = c->d_qraw.reserve(rows.size(), &c->device_bytes)) return rc;
-	VK_HIP(hipMemcpyAsync(c->d_qraw, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, st));
+	if (int rc = dst.reserve(rows.size(), &c->device_bytes)) return rc;
+	VK_HIP(hipMemcpyAsync(dst, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, st));
 	return VK_OK;
 }
-VkSimSrcArgs source_table_args(const vk_corpus *c, int t) {
+int upload_source_query(vk_corpus *c, const vk_query_desc *q, vk_host_keep &keep, hipStream_t st) {
+	return upload_source_rows(c, c->desc.d, q->q_vectors, q->q_dtype, q->len_t, c->d_qraw, keep, st);
+}
+VkSimSrcArgs source_table_args_of(const vk_host::sim_src &src, const vk_devbuf<uint8_t> *raw_rows, int raw_tile_bytes, int d, const float *qraw, int t) {
 	VkSimSrcArgs a{};
-	a.src = c->sim_src; a.raw_tiles = c->raw_rows ? (const uint8_t *)*c->raw_rows : nullptr; a.raw_tile_bytes = c->raw_tile_bytes; a.d = c->desc.d;
-	a.q_rows = (const float *)c->d_qraw + (size_t)t * vk_source_tile_floats(c->desc.d);
-	a.q_abs_sums = a.q_rows + 16 * (size_t)c->desc.d;
+	a.src = src; a.raw_tiles = raw_rows ? (const uint8_t *)*raw_rows : nullptr; a.raw_tile_bytes = raw_tile_bytes; a.d = d;
+	a.q_rows = qraw + (size_t)t * vk_source_tile_floats(d);
+	a.q_abs_sums = a.q_rows + 16 * (size_t)d;
 	return a;
+}
+VkSimSrcArgs source_table_args(const vk_corpus *c, int t) {
+	return source_table_args_of(c->sim_src, c->raw_rows.get(), c->raw_tile_bytes, c->desc.d, (const float *)c->d_qraw, t);
+}
+
+// The per-query tables of the static layout, one [V_pad x 16] table per 16 query tokens at `table` (table_stride floats apart), from
+// the query tiles at d_qtile and the 16 token ids per tile at d_qids (null: none): the cosine (or the handle's source), the chain,
+// sim[id(t_j)][j] = 1, the clip (metric/static.cpp:9-78).  The traceback kernels restate their cells themselves -- or, where the
+// table's cell is the canonical cell (a source that is not the cosine, a combinator), read them from these tables: then a query that
+// only states listed slices (`only`) needs them too.
+// A mixed handle: every operand's table -- a cosine operand's in the canonical arithmetic, operand 0's in place -- from
+// the rows vk_corpus_set_query_operand left (vk_validate_query has seen them), then their combination into `table`.
+int fill_query_tables(vk_corpus *c, const vk_query_desc *q, const uint8_t *d_qtile, const int32_t *d_qids, float *table, int64_t table_stride,
+	bool only, vk_host_keep &keep, hipStream_t st) {
+	const bool sourced = c->sim_src.kind != VK_SIMSRC_COSINE, mixed = c->mixed();
+	if (only && !sourced && !mixed) return VK_OK;
+	const int nq = (q->len_t + 15) / 16, V = c->desc.vocab_size, n_tiles = (int32_t)c->n_tiles;
+	int rc;
+	if (sourced && (rc = upload_source_query(c, q, keep, st))) return rc;
+	for (int m = 1; mixed && m < c->sim_mix.n; m++) {
+		const vk_corpus::sim_operand &op = c->operands[m - 1];
+		vk_corpus::mix_operand_bufs &b = c->mixop[m - 1];
+		const vk_corpus::mix_operand_bufs::rows &rows = b.pending[(size_t)c->q_operand_at];
+		if ((rc = b.table.reserve((size_t)nq * (size_t)table_stride, &c->device_bytes))) return rc;
+		std::vector<uint8_t> &tile = keep.vec<uint8_t>();
+		float mags[VK_MAX_LONG_QUERY_LEN];
+		vk_pack_query_rows(op.d, op.tile_bytes, c->prec, rows.bytes.data(), rows.dtype, rows.normalize, q->len_t, tile, mags);
+		if ((rc = b.qtile.reserve(tile.size(), &c->device_bytes))) return rc;
+		VK_HIP(hipMemcpyAsync(b.qtile, tile.data(), tile.size(), hipMemcpyHostToDevice, st));
+		if (op.src.kind != VK_SIMSRC_COSINE && (rc = upload_source_rows(c, op.d, rows.bytes.data(), rows.dtype, q->len_t, b.qraw, keep, st))) return rc;
+	}
+	for (int t = 0; t < nq; t++) {
+		const int cols = std::min(16, q->len_t - t * 16);
+		const int32_t *ids = d_qids ? d_qids + t * 16 : nullptr;
+		float *tab = table + (size_t)t * table_stride;
+		const VkSimSrcArgs sa = source_table_args(c, t);
+		if (mixed && !sourced)
+			VK_HIP(vk_launch_canon_table(c->d_tiles, d_qtile + (size_t)t * c->tile_bytes, n_tiles, c->nk32, c->tail, c->tile_bytes, c->desc.d, tab, ids, cols, V, c->prec, &c->sim_ops, st));
+		else
+			VK_HIP(vk_launch_table(c->d_tiles, d_qtile + (size_t)t * c->tile_bytes, n_tiles, c->nk32, c->tail, c->tile_bytes, tab, ids, cols, V, c->prec, &c->sim_ops,
+				sourced ? &sa : nullptr, st));
+		if (!mixed) continue;
+		VkMixArgs mix{};
+		mix.in[0] = tab; mix.out = tab; mix.n_cells = table_stride; mix.mix = c->sim_mix;
+		for (int m = 1; m < c->sim_mix.n; m++) {
+			const vk_corpus::sim_operand &op = c->operands[m - 1];
+			vk_corpus::mix_operand_bufs &b = c->mixop[m - 1];
+			float *otab = b.table + (size_t)t * table_stride;
+			const uint8_t *oq = b.qtile + (size_t)t * op.tile_bytes;
+			if (op.src.kind != VK_SIMSRC_COSINE) {
+				const VkSimSrcArgs osa = source_table_args_of(op.src, op.raw_rows.get(), op.raw_tile_bytes, op.d, (const float *)b.qraw, t);
+				VK_HIP(vk_launch_table(*op.tiles, oq, n_tiles, op.nk32, op.tail, op.tile_bytes, otab, ids, cols, V, c->prec, &op.ops, &osa, st));
+			} else
+				VK_HIP(vk_launch_canon_table(*op.tiles, oq, n_tiles, op.nk32, op.tail, op.tile_bytes, op.d, otab, ids, cols, V, c->prec, &op.ops, st));
+			mix.in[m] = otab;
+		}
+		VK_HIP(vk_launch_table_mix(&mix, st));
+	}
+	return VK_OK;
 }
 
 // row of the slice table of a slice (long slices sit in padded groups); the inverse of entry_sent is built when first needed

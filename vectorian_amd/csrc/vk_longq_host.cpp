@@ -61,16 +61,10 @@ int vk_longq_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_
 
 	if (q->boost && (rc = upload_boost(c, q->boost, keep, st))) return rc;
 	const int64_t table_stride = (int64_t)c->n_tiles * 16 * 16;
-	const bool sourced = is_static && c->sim_src.kind != VK_SIMSRC_COSINE;   // (the tracebacks then read the tables: listed slices need them too)
-	if (is_static && (!only || sourced)) {
-		if ((rc = lq.table.reserve((size_t)nq * (size_t)table_stride, &c->device_bytes))) return rc;
-		if (sourced && (rc = upload_source_query(c, q, keep, st))) return rc;
-		for (int t = 0; t < nq; t++) {   // one [V_pad x 16] table per 16 query tokens: cosine (or the handle's source), sim[id(t_j)][j] = 1, clip (metric/static.cpp:9-78)
-			const VkSimSrcArgs sa = source_table_args(c, t);
-			VK_HIP(vk_launch_table(c->d_tiles, lq.qt + (size_t)t * c->tile_bytes, (int32_t)c->n_tiles, c->nk32, c->tail, c->tile_bytes,
-				lq.table + (size_t)t * table_stride, q->q_token_ids ? lq.il + LTP + t * 16 : nullptr, std::min(16, LT - t * 16), c->desc.vocab_size, c->prec, &c->sim_ops,
-				sourced ? &sa : nullptr, st));
-		}
+	if (is_static) {   // (where the table's cell is the canonical cell the tracebacks read the tables: listed slices need them too)
+		if (!only || c->table_is_canonical())
+			if ((rc = lq.table.reserve((size_t)nq * (size_t)table_stride, &c->device_bytes))) return rc;
+		if ((rc = fill_query_tables(c, q, lq.qt, q->q_token_ids ? (const int32_t *)lq.il + LTP : nullptr, lq.table, table_stride, only, keep, st))) return rc;
 	}
 
 	corpus_fields_ids(p, c);

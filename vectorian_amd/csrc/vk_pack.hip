@@ -361,6 +361,11 @@ extern "C" hipError_t vk_launch_pack(const void *in, int32_t dtype_bf16, int64_t
 	return hipGetLastError();
 }
 
+extern "C" hipError_t vk_launch_table_fix(float *table, const int32_t *q_ids, int32_t len_t, int32_t V, hipStream_t stream) {
+	vk_table_fix_kernel<<<1, 64, 0, stream>>>(table, q_ids, len_t, V);
+	return hipGetLastError();
+}
+
 extern "C" hipError_t vk_launch_table(const uint8_t *etiles, const uint8_t *qtile, int32_t n_tiles, int32_t nk32, int32_t tail,
 	int32_t tile_bytes, float *table, const int32_t *q_ids, int32_t len_t, int32_t V, int32_t prec, const vk_host::sim_ops *ops,
 	const VkSimSrcArgs *src, hipStream_t stream) {

@@ -69,6 +69,18 @@ int vk_validate_query(const vk_corpus *c, const vk_query_desc *q, const vk_topk_
 			return fail(VK_ERR_UNSUPPORTED, "slices of more than VK_MAX_SENT_LEN (512) tokens: tag-weighted vocabulary transports keyed by (id, tag) rewrite cells of a slice's rows in LDS");
 	}
 	if (!q->q_vectors) return fail(VK_ERR_INVALID, "q_vectors is null");
+	if (c->mixed()) {   // a combinator (vk_corpus_set_sim_mix): every operand's rows of this query, and no magnitudes
+		if (q->algorithm == VK_ALG_WRD)
+			return fail(VK_ERR_UNSUPPORTED, "VK_ALG_WRD on a mixed handle: the reference leaves the magnitudes of a token similarity combinator unwritten");
+		for (int m = 1; m < c->sim_mix.n; m++) {
+			const auto &pending = c->mixop[m - 1].pending;
+			if ((size_t)c->q_operand_at >= pending.size())
+				return fail(VK_ERR_STATE, "mixed handle: no rows of operand " + std::to_string(m) + " for this query (vk_corpus_set_query_operand)");
+			if (pending[(size_t)c->q_operand_at].len_t != q->len_t)
+				return fail(VK_ERR_STATE, "mixed handle: operand " + std::to_string(m) + " was given " + std::to_string(pending[(size_t)c->q_operand_at].len_t) +
+					" rows for a query of " + std::to_string(q->len_t) + " tokens");
+		}
+	}
 	if (q->q_dtype != VK_F32 && q->q_dtype != VK_BF16) return fail(VK_ERR_INVALID, "bad q_dtype");
 	if (q->max_matches < 1 || q->max_matches > VK_MAX_MATCHES_SORTED) return fail(VK_ERR_INVALID, "max_matches out of range");
 	// beyond VK_MAX_MATCHES: every score sorted on the device -- alignments (with or without their tracebacks), no submatch weight;
@@ -149,20 +161,19 @@ int vk_validate_query(const vk_corpus *c, const vk_query_desc *q, const vk_topk_
 
 // Vectors.normalized for the query rows, then bf16 (RNE), then tile order (16 rows,
 // rows >= len_t zero).  Same arithmetic as oracle/vk_oracle.c vko_normalize_rows_bf16.
-void vk_pack_query(const vk_corpus *c, const vk_query_desc *q, std::vector<uint8_t> &tile, float *mags, std::vector<uint8_t> *bound_tile) {
-	const int d = c->desc.d;
-	tile.assign((size_t)c->tile_bytes * (size_t)((q->len_t + 15) / 16), 0);   // tile i / 16 holds row i % 16
+void vk_pack_query_rows(int d, int tile_bytes, int prec, const void *q_vectors, int q_dtype, int q_normalize, int len_t, std::vector<uint8_t> &tile, float *mags) {
+	tile.assign((size_t)tile_bytes * (size_t)((len_t + 15) / 16), 0);   // tile i / 16 holds row i % 16
 	std::vector<float> row((size_t)d);
-	for (int i = 0; i < q->len_t; i++) {
+	for (int i = 0; i < len_t; i++) {
 		for (int k = 0; k < d; k++)
-			row[(size_t)k] = q->q_dtype == VK_F32 ? ((const float *)q->q_vectors)[(size_t)i * d + k]
-			                                       : bf16_to_f32(((const uint16_t *)q->q_vectors)[(size_t)i * d + k]);
+			row[(size_t)k] = q_dtype == VK_F32 ? ((const float *)q_vectors)[(size_t)i * d + k]
+			                                    : bf16_to_f32(((const uint16_t *)q_vectors)[(size_t)i * d + k]);
 		double acc = 0.0;
 		for (int k = 0; k < d; k++) acc += (double)row[(size_t)k] * (double)row[(size_t)k];
 		float m = (float)std::sqrt(acc);
 		if (m != m) m = 0.0f;
 		mags[i] = m;
-		if (q->q_normalize) {
+		if (q_normalize) {
 			for (int k = 0; k < d; k++) {
 				float v = row[(size_t)k] / m;
 				if (v != v) v = 0.0f;
@@ -170,17 +181,22 @@ void vk_pack_query(const vk_corpus *c, const vk_query_desc *q, std::vector<uint8
 			}
 		}
 		for (int k = 0; k < d; k++) {
-			if (c->prec) {   // fp32 tile: block k >> 4, lane 16 (k & 3) + row, element (k & 15) >> 2
-				const size_t off = (size_t)(i >> 4) * c->tile_bytes + (size_t)(k >> 4) * 1024 + (size_t)((k & 3) * 16 + (i & 15)) * 16 + (size_t)((k & 15) >> 2) * 4;
+			if (prec) {   // fp32 tile: block k >> 4, lane 16 (k & 3) + row, element (k & 15) >> 2
+				const size_t off = (size_t)(i >> 4) * tile_bytes + (size_t)(k >> 4) * 1024 + (size_t)((k & 3) * 16 + (i & 15)) * 16 + (size_t)((k & 15) >> 2) * 4;
 				memcpy(&tile[off], &row[(size_t)k], 4);
 				continue;
 			}
 			const uint16_t b = f32_to_bf16(row[(size_t)k]);
 			const int t = k >> 5, g = (k & 31) >> 3, j = k & 7;
-			const size_t off = (size_t)(i >> 4) * c->tile_bytes + (size_t)t * 1024 + (size_t)(g * 16 + (i & 15)) * 16 + (size_t)j * 2;
+			const size_t off = (size_t)(i >> 4) * tile_bytes + (size_t)t * 1024 + (size_t)(g * 16 + (i & 15)) * 16 + (size_t)j * 2;
 			memcpy(&tile[off], &b, 2);
 		}
 	}
+}
+
+void vk_pack_query(const vk_corpus *c, const vk_query_desc *q, std::vector<uint8_t> &tile, float *mags, std::vector<uint8_t> *bound_tile) {
+	const int d = c->desc.d;
+	vk_pack_query_rows(d, c->tile_bytes, c->prec, q->q_vectors, q->q_dtype, q->q_normalize, q->len_t, tile, mags);
 	// The bound pass: the rows as stored (bf16), read back from the tile, in the format of the corpus's shadow with the
 	// cells' constants behind them (vk_host::pack_bound_query)
 	if (!bound_tile || !c->shadow || c->prec || q->len_t > VK_FAST_QUERY_LEN) return;
@@ -445,16 +461,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		int32_t *ids = keep.array<int32_t>(80);
 		for (int j = 0; j < 80; j++) ids[j] = (q->q_token_ids && j < q->len_t) ? q->q_token_ids[j] : -1;
 		VK_HIP(hipMemcpyAsync(c->d_qids, ids, 80 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-		// one [V_pad x 16] table per 16 query tokens (the traceback kernels restate their cells themselves -- or, under a source that is
-		// not the cosine, read them from these tables: then a query that only states listed slices needs them too)
-		const bool sourced = c->sim_src.kind != VK_SIMSRC_COSINE;
-		if (sourced && (rc = upload_source_query(c, q, keep, st))) return rc;
-		for (int t = 0; t < nq && (!only || sourced); t++) {
-			const VkSimSrcArgs sa = source_table_args(c, t);
-			VK_HIP(vk_launch_table(c->d_tiles, c->d_qtile + (size_t)t * c->tile_bytes, (int32_t)c->n_tiles, c->nk32, c->tail, c->tile_bytes,
-				c->d_table + t * table_stride, q->q_token_ids ? c->d_qids + t * 16 : nullptr, std::min(16, q->len_t - t * 16), c->desc.vocab_size, c->prec, &c->sim_ops,
-				sourced ? &sa : nullptr, st));
-		}
+		if ((rc = fill_query_tables(c, q, c->d_qtile, q->q_token_ids ? (const int32_t *)c->d_qids : nullptr, c->d_table, table_stride, only, keep, st))) return rc;
 	}
 
 	// ---- the size of the selection (known before the scoring pass: the bound pass prunes against it)
@@ -1074,6 +1081,8 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 extern "C" {
 
 int vk_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out) {
+	// the rows vk_corpus_set_query_operand left belong to this query, however it ends (a batch run query by query drops its own)
+	struct consume { vk_corpus_t *c; ~consume() { if (c && !c->in_batch) c->drop_query_operands(); } } consumed{c};
 	const int rc = vk_validate_query(c, q, out);
 	if (rc) return rc;
 	if (q->abort && *q->abort) { out->n_out = 0; return fail(VK_ERR_ABORTED, "query aborted by the caller"); }
@@ -1086,9 +1095,9 @@ int vk_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out) {
 	std::vector<int16_t> own_map;
 	std::vector<float> own_sim;
 	bool restate = false;
-	// (A source that is not the cosine, chain or none: likewise.  The table's cell is the canonical cell there, but the scoring
+	// (A source that is not the cosine or a combinator, chain or none: likewise.  The table's cell is the canonical cell there, but the scoring
 	// kernels' sums over a slice are not stated to be the tracebacks' sums.)
-	if ((c->sim_ops.n > 0 || c->sim_src.kind != VK_SIMSRC_COSINE) && q->algorithm == VK_ALG_ALIGN && !q->want_flow && !q->only_slices && q->submatch_weight == 0.0f) {
+	if ((c->sim_ops.n > 0 || c->table_is_canonical()) && q->algorithm == VK_ALG_ALIGN && !q->want_flow && !q->only_slices && q->submatch_weight == 0.0f) {
 		q_flow = *q; q_flow.want_flow = 1;
 		out_flow = *out;
 		own_map.assign((size_t)out->capacity * (size_t)q->len_t, (int16_t)-1);

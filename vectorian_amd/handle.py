@@ -114,6 +114,46 @@ class Corpus:
 		beside the cosine reads the unmodified rows, so it is set BEFORE append_vectors; static layout only."""
 		_core._check(_core.lib().vk_corpus_set_sim_source(self._h, int(kind), float(arg)))
 
+	def set_sim_mix(self, kind, n_operands, weights=None):
+		"""a token similarity combinator over n_operands static embeddings (vk_corpus_set_sim_mix): core.VK_SIMMIX_AVERAGE with one
+		weight per operand (float64), or core.VK_SIMMIX_MAXIMUM.  Operand 0 is this handle; set BEFORE append_vectors."""
+		w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+		if w is not None and w.shape != (int(n_operands),):
+			raise ValueError("one weight per operand")
+		_core._check(_core.lib().vk_corpus_set_sim_mix(self._h, int(kind), int(n_operands), _core._np_ptr(w) if w is not None else None))
+		self._operand_d = {}
+
+	def set_sim_operand(self, i, d, source=None, ops=()):
+		"""operand i >= 1 of a mixed handle (vk_corpus_set_sim_operand): the width of its embedding, its source -- None for the
+		cosine, else (kind, arg) as set_sim_source -- and its operator chain as set_sim_ops"""
+		pairs = [tuple(op.sim_op) if hasattr(op, "sim_op") else tuple(op) for op in ops]
+		kinds = np.ascontiguousarray([int(k) for k, _ in pairs], dtype=np.int32)
+		args = np.ascontiguousarray([a for _, a in pairs], dtype=np.float32)
+		kind, arg = source if source is not None else (_core.VK_SIMSRC_COSINE, 0.0)
+		_core._check(_core.lib().vk_corpus_set_sim_operand(self._h, int(i), int(d), int(kind), float(arg), _core._np_ptr(kinds), _core._np_ptr(args), len(pairs)))
+		self._operand_d[int(i)] = int(d)
+
+	@staticmethod
+	def _operand_rows(rows, d):
+		rows = np.ascontiguousarray(rows)
+		if rows.dtype != np.uint16:
+			rows = np.ascontiguousarray(rows, dtype=np.float32)
+		if rows.ndim != 2 or rows.shape[1] != d:
+			raise ValueError(f"expected [n x {d}] vectors, got {rows.shape}")
+		return rows, (_core.VK_BF16 if rows.dtype == np.uint16 else _core.VK_F32)
+
+	def append_operand_vectors(self, i, rows, normalize=True):
+		"""the vocabulary rows of operand i (vk_corpus_append_operand_vectors): float32 / uint16(bf16) [n x d_i] on the host"""
+		rows, dt = self._operand_rows(rows, self._operand_d[int(i)])
+		_core._check(_core.lib().vk_corpus_append_operand_vectors(self._h, int(i), _core._np_ptr(rows), rows.shape[0], dt, int(normalize)))
+
+	def set_query_operand(self, i, q_vectors, q_normalize=True):
+		"""operand i's rows [len_t x d_i] of the NEXT query on this handle (vk_corpus_set_query_operand; before a query_batch: call k
+		belongs to query k).  `query(q_operand_vectors=...)` does this under the same hold of the lock as the query."""
+		rows, dt = self._operand_rows(q_vectors, self._operand_d[int(i)])
+		with self.lock:
+			_core._check(_core.lib().vk_corpus_set_query_operand(self._h, int(i), _core._np_ptr(rows), rows.shape[0], dt, int(q_normalize)))
+
 	def finalize(self):
 		_core._check(_core.lib().vk_corpus_finalize(self._h))
 
@@ -195,21 +235,26 @@ class Corpus:
 		"""similarity rows / plans of the winners: room for the longest slice of the corpus (a multiple of 64 tokens)"""
 		return _core.winner_rows(getattr(self, "_max_len", 0))
 
-	def query(self, q_vectors, **options):
-		"""One query against the shard (vk_query).  Returns a _core.TopK."""
+	def query(self, q_vectors, q_operand_vectors=None, **options):
+		"""One query against the shard (vk_query).  Returns a _core.TopK.
+		q_operand_vectors: a mixed handle (set_sim_mix) -- the query's rows under operands 1 .., one [len_t x d_i] array each; set
+		and consumed under one hold of the handle's lock"""
 		keep = []
 		q, len_t = self._desc(q_vectors, keep, **options)
 		rows = self._winner_rows()
 		out = _core.TopK(max(1, q.max_matches), len_t, transport=bool(q.want_flow) and (q.algorithm != _core.VK_ALG_ALIGN or bool(options.get("want_rows"))), rows=rows)
 		so = out._struct()
 		with self.lock:
+			for i, rows_i in enumerate(q_operand_vectors or (), 1):
+				self.set_query_operand(i, rows_i, q_normalize=bool(q.q_normalize))
 			_core._check(_core.lib().vk_query(self._h, C.byref(q), C.byref(so)))
 		out.n = so.n_out
 		return out
 
-	def query_batch(self, queries, token_ids=None, **options):
+	def query_batch(self, queries, token_ids=None, q_operand_vectors=None, **options):
 		"""A batch of queries with common options (vk_query_batch).  Returns a list of _core.TopK.
-		token_ids: static layout -- the vocabulary ids of every query's tokens, a list parallel to `queries` (vk_query_desc.q_token_ids)"""
+		token_ids: static layout -- the vocabulary ids of every query's tokens, a list parallel to `queries` (vk_query_desc.q_token_ids)
+		q_operand_vectors: a mixed handle -- per query the list `query` takes, a list parallel to `queries`"""
 		keep = []
 		n = len(queries)
 		if token_ids is not None and len(token_ids) != n:
@@ -249,6 +294,9 @@ class Corpus:
 			outs.append(t)
 			sos[i] = t._struct()
 		with self.lock:
+			for per_query_rows in q_operand_vectors or ():
+				for i, rows_i in enumerate(per_query_rows, 1):
+					self.set_query_operand(i, rows_i, q_normalize=bool(options.get("q_normalize", True)))
 			_core._check(_core.lib().vk_query_batch(self._h, qs, n, sos))
 		for t, so in zip(outs, sos):
 			t.n = so.n_out

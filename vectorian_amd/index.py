@@ -26,6 +26,9 @@ from vectorian_amd.lanes import LanesMixin
 from vectorian_amd.match import HipMatch, Match, PyMatch, Region, TokenMatch, TokenMatchEdge, TokenMatchT, _Winners
 from vectorian_amd.options import _QUERY_OPTION_WHITELIST, _split_gap, backend_args
 from vectorian_amd.query import PreparedQuery, Query, default_tokenizer
+from vectorian_amd.alignment import WordRotatorsDistance
+from vectorian_amd.modifier import (ExtremumTokenSimilarity, MixedTokenSimilarity, TokenSimilarityModifier,
+	UnaryTokenSimilarityModifier)
 from vectorian_amd.sim import (CosineSim, EmbeddingTokenSim, EuclideanDistance, ImprovedSqrtCosineSim, ModifiedVectorSim, OptimizedSpanSim,
 	PNormDistance)
 
@@ -104,12 +107,21 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 		if not isinstance(sim, OptimizedSpanSim):
 			raise TypeError(f"{type(sim).__name__}: the HIP index implements OptimizedSpanSim")
 		token_sim = sim.token_sim
-		if not isinstance(token_sim, EmbeddingTokenSim):
-			raise NotImplementedError("token similarity modifiers are outside the HIP path (SURVEY 2.1): they combine clipped "
-				"similarity matrices and leave values outside [0, 1]; shape ONE cosine with ModifiedVectorSim instead")
-		self._embedding = token_sim.embedding
-		self._sim_source, self._sim_ops = self._operator_chain(token_sim.similarity, self._embedding)
-		self._metric_name = token_sim.to_args(self)["name"]
+		# a combinator of the reference's: its kind, its float64 weights, and per operand 1 .. (embedding, source, chain);
+		# operand 0 is what a plain EmbeddingTokenSim would be
+		self._mix = None
+		if isinstance(token_sim, TokenSimilarityModifier):
+			self._mix = self._token_sim_mix(token_sim, sim.optimizer)
+			first = token_sim.operands[0]
+		elif isinstance(token_sim, EmbeddingTokenSim):
+			first = token_sim
+		else:
+			raise NotImplementedError("token similarity modifiers that are none of vectorian_amd.modifier's are outside the HIP path "
+				"(SURVEY 2.1): the device combines the clipped matrices of MixedTokenSimilarity / MaximumTokenSimilarity only (DESIGN 14); "
+				"shape ONE cosine with ModifiedVectorSim instead")
+		self._embedding = first.embedding
+		self._sim_source, self._sim_ops = self._operator_chain(first.similarity, self._embedding)
+		self._metric_name = token_sim.name if self._mix is not None else token_sim.to_args(self)["name"]
 		session = self.session
 		level, size = partition.level, partition.window_size
 		# slices: Spans::iterate (vectorian/core/cpp/document.h:147-169) over every document
@@ -173,6 +185,13 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 			self._corpus = make(layout=core.VK_LAYOUT_STATIC, d=emb.dimension, n_tokens=n_tokens_dev, n_sentences=n_slices_dev,
 				vocab_size=max(1, session.vocab.size), keep_magnitudes=True, device=device, precision=precision)
 			E = vocab_vectors.unmodified if session.vocab.size else np.zeros((1, emb.dimension), np.float32)
+			if self._mix is not None:
+				# before the first append, as a source: the operands' rows arrive beside the handle's own
+				self._corpus.set_sim_mix(self._mix["kind"], 1 + len(self._mix["operands"]), self._mix["weights"])
+				for i, (o_emb, o_source, o_ops) in enumerate(self._mix["operands"], 1):
+					self._corpus.set_sim_operand(i, o_emb.dimension, o_source, o_ops)
+					rows = o_emb.encode_tokens(session.vocab.tokens).unmodified if session.vocab.size else np.zeros((1, o_emb.dimension), np.float32)
+					self._corpus.append_operand_vectors(i, rows, normalize=True)
 			if self._sim_source is not None:
 				# a source beside the cosine reads the unmodified rows: the handle keeps a second copy of what is appended next
 				self._corpus.set_sim_source(*self._sim_source)
@@ -245,6 +264,49 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 				raise NotImplementedError(f"{type(op).__name__}: not an operator of vectorian_amd.kernel (the device runs those six)") from None
 			ops.append((int(kind), np.float32(arg)))
 		return src, ops
+
+	@staticmethod
+	def _token_sim_mix(token_sim, optimizer):
+		"""kind, weights and operands 1 .. of a token similarity combinator (vk_corpus_set_sim_mix), or the reason it does not run here
+		"""
+		name = type(token_sim).__name__
+		if isinstance(token_sim, UnaryTokenSimilarityModifier):
+			raise NotImplementedError(f"{name}: operators on a CLIPPED token similarity leave [0, 1] unclipped and are outside the HIP path; "
+				"put the operators into the operand's vector similarity with ModifiedVectorSim instead")
+		if type(token_sim) is MixedTokenSimilarity:
+			kind = core.VK_SIMMIX_AVERAGE
+		elif isinstance(token_sim, ExtremumTokenSimilarity) and type(token_sim).__call__ is ExtremumTokenSimilarity.__call__:
+			kind = core.VK_SIMMIX_MAXIMUM   # MinimumTokenSimilarity too: upstream's __call__ computes the maximum for both
+		else:
+			raise NotImplementedError(f"{name}: token similarity modifiers other than MixedTokenSimilarity, MaximumTokenSimilarity and "
+				"MinimumTokenSimilarity are outside the HIP path; shape ONE cosine with ModifiedVectorSim instead")
+		if isinstance(optimizer, WordRotatorsDistance):
+			raise NotImplementedError(f"{name} under WordRotatorsDistance: the reference leaves the magnitudes of a combinator unwritten "
+				"(Extremum) or averaged (Mixed); the HIP path computes neither")
+		operands = list(token_sim.operands)
+		if not 2 <= len(operands) <= core.VK_MAX_SIM_OPERANDS:
+			raise NotImplementedError(f"{name}: {len(operands)} operands; the HIP path combines 2 to {core.VK_MAX_SIM_OPERANDS}")
+		for op in operands:
+			if isinstance(op, TokenSimilarityModifier):
+				raise NotImplementedError(f"{name}: nested modifier {type(op).__name__} as an operand; operands are EmbeddingTokenSims")
+			if not isinstance(op, EmbeddingTokenSim):
+				raise NotImplementedError(f"{name}: operand {type(op).__name__} is no EmbeddingTokenSim")
+			if not op.embedding.is_static:
+				raise NotImplementedError(f"{name}: combinators run over static embeddings only; {op.embedding.name} is contextual")
+		weights = None
+		if kind == core.VK_SIMMIX_AVERAGE:
+			weights = np.asarray(token_sim.weights, dtype=np.float64)   # what np.average makes of Python or int weights
+			if weights.shape != (len(operands),):
+				raise NotImplementedError(f"{name}: {weights.size} weights for {len(operands)} operands")
+			if not np.isfinite(weights).all() or (weights < 0).any():
+				raise NotImplementedError(f"{name}: weights must be finite and not negative, got {list(token_sim.weights)}")
+			if not weights.sum() > 0:
+				raise NotImplementedError(f"{name}: the weights sum to 0")
+		rest = []
+		for op in operands[1:]:
+			source, ops = HipBruteForceIndex._operator_chain(op.similarity, op.embedding)
+			rest.append((op.embedding, source, ops))
+		return dict(kind=kind, weights=weights, operands=rest)
 
 	@staticmethod
 	def _source_of(source, similarity, embedding, refusal):
@@ -357,6 +419,9 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 		call["abort_flag"] = query._abort
 		if emb.is_static:
 			call["q_token_ids"] = p_query.token_ids
+		if self._mix is not None:   # the query's rows under the other operands' embeddings (the debug hook's walk passes them on)
+			call["q_operand_vectors"] = [np.ascontiguousarray(o_emb.encode_tokens(p_query.tokens).unmodified, dtype=np.float32)
+				for o_emb, _, _ in self._mix["operands"]]
 		aborted = False
 		all_scores = None
 		# A handle serves one call at a time.  With find_many the hook's walk over all slices (debug = AllSlices) runs later, on the

@@ -93,6 +93,9 @@ class LanesMixin:
 				return idx, [], False
 			qvs = [emb.encode_tokens(prepared[i].tokens) for i in idx]
 			ids = dict(token_ids=[prepared[i].token_ids for i in idx]) if emb.is_static else {}   # static layout: sim[id(t_j)][j] = 1 needs the words' ids
+			if getattr(self, "_mix", None) is not None:   # a combinator: every query's rows under the other operands' embeddings
+				ids["q_operand_vectors"] = [[np.ascontiguousarray(o_emb.encode_tokens(prepared[i].tokens).unmodified, dtype=np.float32)
+					for o_emb, _, _ in self._mix["operands"]] for i in idx]
 			try:
 				tops = handles[l].query_batch([np.ascontiguousarray(qv.unmodified, dtype=np.float32) for qv in qvs], q_normalize=True,
 					boost=self._dev_boost, want_flow=True, abort_flag=queries[idx[0]]._abort, **ids, **args) if idx else []

@@ -8,10 +8,13 @@ PNormDistance / EuclideanDistance / ImprovedSqrtCosineSim   vectorian/sim/vector
 A ModifiedVectorSim -- a chain of up to 8 operators on the unclipped output of its source -- runs on the device over static
 embeddings: `EmbeddingTokenSim(emb, ModifiedVectorSim(CosineSim(), Bias(1), Scale(0.5)))`.  Its source, or the
 similarity itself, is CosineSim, PNormDistance or ImprovedSqrtCosineSim (the latter two over static embeddings only, on
-the unmodified vectors): `ModifiedVectorSim(PNormDistance(2), Scale(1 / 12), DistanceToSimilarity())`.  FuzzyJaccardSim,
-DirectionalDistance, user-defined VectorSims, chains over contextual embeddings and the token-similarity modifier combinators of
-the reference are out of scope and are rejected explicitly rather than ignored; the tag-weighted variant is a "next"
-row.
+the unmodified vectors): `ModifiedVectorSim(PNormDistance(2), Scale(1 / 12), DistanceToSimilarity())`.
+TokenSimilarityModifier / MixedTokenSimilarity / MaximumTokenSimilarity / MinimumTokenSimilarity   vectorian/sim/modifier.py
+(vectorian_amd/modifier.py, re-exported here): combinators of up to four EmbeddingTokenSims over static embeddings run on the device
+(DESIGN 14): `MixedTokenSimilarity([EmbeddingTokenSim(a, CosineSim()), EmbeddingTokenSim(b, CosineSim())], [2, 1])`.
+FuzzyJaccardSim, DirectionalDistance, user-defined VectorSims, chains and combinators over contextual embeddings, nested
+combinators, UnaryTokenSimilarityModifier and a combinator under WordRotatorsDistance are out of scope and are rejected explicitly
+rather than ignored; the tag-weighted variant is a "next" row.
 """
 
 import numpy as np
@@ -179,6 +182,19 @@ class EmbeddingTokenSim(TokenSim):
 			"embedding": self._embedding.name,
 			"metric": self._sim
 		}
+
+
+# the combinators of vectorian/sim/modifier.py live in vectorian_amd/modifier.py (which needs TokenSim above) and are re-exported
+# here on first use, so that either module may be imported first
+_MODIFIERS = ("TokenSimilarityModifier", "UnaryTokenSimilarityModifier", "MixedTokenSimilarity", "ExtremumTokenSimilarity",
+	"MaximumTokenSimilarity", "MinimumTokenSimilarity")
+
+
+def __getattr__(name):
+	if name in _MODIFIERS:
+		from vectorian_amd import modifier
+		return getattr(modifier, name)
+	raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 class SpanSim:
