@@ -330,7 +330,10 @@ int vk_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out);
  * n_queries calls of vk_query; for injective RWMD over a contextual corpus whose sentences all have
  * the same length 16 / 32 / 48 / 64 it runs as one MFMA-bound GEMM with the row / column minima as
  * epilogue (every corpus byte read once per batch).  outs: [n_queries]; with want_flow, relaxed-WMD queries get the
- * similarity rows of their winners in outs[i].sim_rows when that array is given (one launch for the whole batch). */
+ * similarity rows of their winners in outs[i].sim_rows when that array is given (one launch for the whole batch).
+ * A batch of one-token local alignment queries with a common max_matches and min_score over a contextual corpus of one-token
+ * slices (one vector per span; no booster, flows, tag or submatch weights) takes one pass over the span vectors per LDS fill of
+ * queries, 16 queries per MFMA tile; its result sets are those of vk_query bit for bit. */
 int vk_query_batch(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_queries, vk_topk_out *outs);
 
 /* every sentence's Score::value of the last query, for the debug hook

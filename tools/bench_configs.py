@@ -5,6 +5,7 @@ driver's bench: that is bench.py).  Prints one JSON line per run.
   python tools/bench_configs.py --alg rwmd --sentences 1000000
   python tools/bench_configs.py --alg wrd --d 768 --min-len 8 --max-len 64 --sentences 500000
   python tools/bench_configs.py --alg align --gap exp5 --locality global --d 768 --min-len 8 --max-len 64
+  python tools/bench_configs.py --span-batch 256 --d 768          the span index's shape: 256 one-vector queries per vk_query_batch
 """
 
 import argparse
@@ -45,7 +46,11 @@ def main():
 	ap.add_argument("--sim-mix", action="store_true", help="static layout: after the plain run, the same queries on a second, mixed handle "
 		"(vk_corpus_set_sim_mix): a two-operand AVERAGE, weights 2 : 1, of the cosine over this vocabulary and the cosine over a second one of "
 		"the same width -- reported beside the cosine as sim_mix: prepare_ms and the whole query's wall time, each query's")
+	ap.add_argument("--span-batch", type=int, default=0, metavar="B", help="the span-embedding index's shape (one vector per slice, as --len-t 1 "
+		"--min-len 1 --max-len 1 --gap linear): times query_batch of B one-vector queries with HipSpanEncoderIndex's options; prints pairs/s and the route")
 	args = ap.parse_args()
+	if args.span_batch > 0:
+		args.alg, args.layout, args.len_t, args.min_len, args.max_len = "align", "contextual", 1, 1, 1
 
 	import torch
 	from vectorian_amd import core, synth
@@ -219,6 +224,34 @@ def main():
 	def step(q):
 		return corpus.query(q, algorithm=alg, locality=loc, gap_s=gap, gap_t=gap, q_normalize=True, max_matches=args.k,
 			min_score=0.0 if loc != 1 else -1e9, want_flow=args.alg == "align")
+
+	if args.span_batch > 0:
+		import ctypes
+		bq = [np.ascontiguousarray(E[rng.integers(0, V, size=1)] + 0.05 * rng.standard_normal((1, args.d)).astype(np.float32), dtype=np.float32)
+			for _ in range(args.span_batch)]
+		def sstep():
+			return corpus.query_batch(bq, q_normalize=True, locality=0, gap_s=0.0, gap_t=0.0, max_matches=args.k, min_score=0.0, want_flow=False)
+		for i in range(args.warmup):
+			sstep()
+		torch.cuda.synchronize()
+		ph = []
+		t0 = time.perf_counter()
+		for i in range(args.steps):
+			outs = sstep()
+			ph.append(corpus.last_timings())
+		el = time.perf_counter() - t0
+		state = np.zeros(16, dtype=np.int64)   # vk_batch_state (internal export): entry 0 is the route -- 1 query by query, 2 the shared pass, 4 the span pass
+		core.lib().vk_batch_state.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+		core._check(core.lib().vk_batch_state(corpus._h, state.ctypes.data))
+		score_ms = float(np.mean([p["score_ms"] for p in ph]))
+		print(json.dumps({
+			"span_batch": args.span_batch, "d": args.d, "precision": args.precision, "spans": args.sentences, "k": args.k, "route": int(state[0]),
+			"pairs_per_s": args.sentences * args.span_batch * args.steps / el, "ms_per_batch": el / args.steps * 1e3,
+			"score_kernels_ms": score_ms, "select_ms": float(np.mean([p["topk_ms"] for p in ph])), "total_device_ms": float(np.mean([p["total_ms"] for p in ph])),
+			"matrix_GB": args.sentences * args.span_batch * 4 / 1e9, "corpus_GB": args.sentences * args.d * (4 if args.precision == "f32" else 2) / 1e9,
+			"top_score_q0": float(outs[0].score[0]) if outs[0].n else None}))
+		corpus.close()
+		return
 
 	if args.batch > 0:
 		# BASELINE config 4: a batch of queries per call

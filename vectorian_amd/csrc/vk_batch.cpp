@@ -1,5 +1,5 @@
-// vk_batch.cpp -- C-ABI: several queries per call (the RWMD GEMM pass, queries sharing a pass over the tiles,
-// or one by one).
+// vk_batch.cpp -- C-ABI: several queries per call (the RWMD GEMM pass, the span pass over one-token slices, queries sharing a pass
+// over the tiles, or one by one).
 // No CPU compute fallback exists: without a HIP device every entry point that
 // would compute returns VK_ERR_NO_DEVICE / VK_ERR_HIP.
 
@@ -369,6 +369,153 @@ static int query_batch_shared_pass(vk_corpus_t *c, const vk_query_desc *qs, int3
 	return VK_OK;
 }
 
+// One-token queries over a corpus of one-token slices (the span-embedding index): 16 queries per packed query tile, one pass of
+// vk_span_batch_kernel over the span tiles per LDS fill of queries, every query's scores a row of the handle's score matrix, then the
+// selection per query (geometry and qualification: vk_span_batch_host.h).  The cell of (query, span) is the float
+// vk_span_kernel writes for that query alone -- the same MFMA chain, clipped; raw / 1 with no booster -- and the selections order by the
+// same keys, so every result set is vk_query's bit for bit.  Returns VK_ERR_UNSUPPORTED (without setting an error) when the batch
+// does not qualify.  VK_SPAN_BATCH=off: never; VK_SPAN_BATCH_CAP=<bytes>: a smaller score matrix (tests: batches over several chunks).
+static int query_batch_span(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_queries, vk_topk_out *outs, vk_host_keep &keep) {
+	if (n_queries < 2) return VK_ERR_UNSUPPORTED;
+	if (const char *e = getenv("VK_SPAN_BATCH")) if (!strcmp(e, "off")) return VK_ERR_UNSUPPORTED;
+	size_t cap = vk_host::kSpanBatchMatrixCap;
+	if (const char *e = getenv("VK_SPAN_BATCH_CAP")) { const long long v = atoll(e); if (v > 0) cap = std::min(cap, (size_t)v); }
+	{
+		vk_host::span_batch_corpus f;
+		f.finalized = c->finalized; f.contextual = c->desc.layout == VK_LAYOUT_CONTEXTUAL; f.contiguous = c->contiguous;
+		f.has_entry_sent = !c->entry_sent.empty(); f.sourced = c->table_is_canonical(); f.chained = c->sim_ops.n > 0;
+		f.uniform_len = c->uniform_len; f.n_long_groups = c->n_long_groups; f.tile_bytes = c->tile_bytes; f.n = c->n_entries;
+		if (!vk_host::span_batch_corpus_ok(f, cap)) return VK_ERR_UNSUPPORTED;
+		const auto facts_of = [](const vk_query_desc &q) {
+			vk_host::span_batch_query s;
+			s.len_t = q.len_t; s.align = q.algorithm == VK_ALG_ALIGN; s.local = q.locality == VK_LOCAL; s.tagged = q.tag_weights != nullptr;
+			s.submatch = q.submatch_weight != 0.0f; s.boost = q.boost != nullptr; s.want_flow = q.want_flow != 0; s.only = q.only_slices != nullptr;
+			s.max_matches = q.max_matches; s.min_score = q.min_score;
+			return s;
+		};
+		const vk_host::span_batch_query s0 = facts_of(qs[0]);
+		for (int i = 0; i < n_queries; i++) if (!vk_host::span_batch_query_ok(facts_of(qs[i]), s0)) return VK_ERR_UNSUPPORTED;
+	}
+	int rc;
+	for (int i = 0; i < n_queries; i++)
+		if ((rc = vk_validate_query(c, &qs[i], &outs[i]))) return rc;
+	VK_HIP(hipSetDevice(c->device));
+	hipStream_t st = c->stream;
+	const int64_t n = c->n_entries, n_pad = vk_host::span_batch_n_pad(n);
+	const int tb = c->tile_bytes;
+	const int k = qs[0].max_matches, kk = (int)std::min<int64_t>(k, n);   // as vk_query: never more winners than rows
+	const float floor = qs[0].min_score;
+	const int fill_tiles = vk_host::span_batch_fill_tiles(tb);
+	const int64_t chunk = std::min<int64_t>(vk_host::span_batch_chunk(n, cap), ((int64_t)n_queries + 15) / 16 * 16);   // queries per score matrix
+	const int chunk_tiles = (int)(chunk / 16);
+	c->batch_state[VK_BS_ROUTE] = vk_host::kSpanBatchRoute; c->batch_state[VK_BS_N_QTILES] = (n_queries + 15) / 16; c->batch_state[VK_BS_UNIFORM_LEN] = c->uniform_len;
+
+	// ---- buffers: the chunk's query tiles, its score matrix (this route's own workspace), the keys of the selection
+	if ((rc = c->d_bq.reserve((size_t)chunk_tiles * tb, &c->device_bytes))) return rc;
+	if ((rc = c->d_bspan.reserve(vk_host::span_batch_matrix_floats(n, chunk), &c->device_bytes))) return rc;
+	const bool waves = kk <= 64;
+	const int64_t nw1 = (n + 4095) / 4096;
+	if (waves) for (auto &b : c->d_bkeys) if ((rc = b.reserve((size_t)chunk * (size_t)nw1 * (size_t)kk, &c->device_bytes))) return rc;
+	if (kk > VK_MAX_MATCHES) {
+		if ((rc = c->d_sort[0].reserve((size_t)n + 64, &c->device_bytes))) return rc;
+		if ((rc = c->d_sort[1].reserve((size_t)n + 64, &c->device_bytes))) return rc;
+	}
+	std::vector<uint8_t> &all = keep.vec<uint8_t>((size_t)chunk_tiles * tb);
+	std::vector<uint64_t> &keys = keep.vec<uint64_t>((size_t)(waves ? chunk : 1) * (size_t)kk);
+	// a query's winners from its kk selected keys, best first: score, slice, and the aligner score -- the score itself without a booster
+	const auto emit = [&](int i, const uint64_t *sel) {
+		vk_topk_out *out = &outs[i];
+		const int n_out = vk_host::count_keys(sel, kk);
+		for (int j = 0; j < n_out; j++) {
+			out->score[j] = vk_host::key_score(sel[j]);
+			out->sentence[j] = (int64_t)vk_host::key_row(sel[j]);
+			if (out->raw_score) out->raw_score[j] = out->score[j];
+		}
+		out->n_out = n_out;
+	};
+
+	VkSpanBatchParams p{};
+	p.tiles = c->d_tiles; p.n_tiles = n_pad / 16; p.tile_bytes = tb; p.nk32 = c->nk32; p.tail = c->tail; p.prec = c->prec;
+	p.qtiles = c->d_bq; p.n_pad = n_pad; p.matrix = c->d_bspan;
+	for (int base = 0; base < n_queries; base += (int)chunk) {
+		const int nq = (int)std::min<int64_t>(chunk, n_queries - base), n_qtiles = (nq + 15) / 16;
+		// Query::abort (query.h:183-189): polled between the chunks; the queries before `base` are complete
+		if (qs[base].abort && *qs[base].abort) {
+			for (int i = base; i < n_queries; i++) outs[i].n_out = 0;
+			return fail(VK_ERR_ABORTED, "batch aborted by the caller");
+		}
+		VK_HIP(hipEventRecord(c->ev[0], st));
+		// normalise, round and lay out the queries, query j of a tile in its row j: a few host threads over disjoint ranges of tiles
+		std::fill(all.begin(), all.begin() + (size_t)n_qtiles * tb, 0);
+		auto pack_range = [&](int t0, int t1) {
+			std::vector<uint8_t> one;
+			float mags[VK_MAX_QUERY_LEN];
+			for (int i = t0 * 16; i < std::min(nq, t1 * 16); i++) {
+				vk_pack_query(c, &qs[base + i], one, mags);
+				uint8_t *tile = all.data() + (size_t)(i / 16) * tb;
+				for (int u = 0; u < tb / 16; u += 16) memcpy(tile + (size_t)(u + i % 16) * 16, one.data() + (size_t)u * 16, 16);   // row 0 of `one`: every 16th piece
+			}
+		};
+		{
+			const int n_thr = nq >= 32 ? std::min<int>(8, std::max(1u, std::thread::hardware_concurrency())) : 1;
+			std::vector<std::thread> pool;
+			const int per = (n_qtiles + n_thr - 1) / n_thr;
+			for (int t = 1; t < n_thr; t++)
+				if (t * per < n_qtiles) pool.emplace_back(pack_range, t * per, std::min(n_qtiles, (t + 1) * per));
+			pack_range(0, std::min(n_qtiles, per));
+			for (auto &th : pool) th.join();
+		}
+		VK_HIP(hipMemcpyAsync(c->d_bq, all.data(), (size_t)n_qtiles * tb, hipMemcpyHostToDevice, st));
+		VK_HIP(hipEventRecord(c->ev[5], st));   // (no turn-taking with the handle's peers, as in the shared pass: nothing is waited for)
+		VK_HIP(hipEventRecord(c->ev[1], st));
+		p.n_qtiles = n_qtiles; p.fill_tiles = std::min(fill_tiles, n_qtiles); p.n_queries = nq;
+		VK_HIP(vk_launch_span_batch(&p, st));
+		VK_HIP(hipEventRecord(c->ev[2], st));
+		if (waves) {
+			// k <= 64: the wave-streaming selection of every row at once
+			int64_t nw = 0;
+			int cur = 0;
+			const int64_t stride = nw1 * kk;
+			VK_HIP(vk_launch_topk_wave_batch(c->d_bspan, nullptr, n, floor, kk, 4096, nq, n_pad, stride, c->d_bkeys[0], &nw, st));
+			while (nw > 1) {
+				const int64_t nkeys = nw * kk;
+				const int64_t per_wave = nkeys <= 16384 ? nkeys : 4096;
+				VK_HIP(vk_launch_topk_wave_batch(nullptr, c->d_bkeys[cur], nkeys, 0.0f, kk, per_wave, nq, stride, stride, c->d_bkeys[1 - cur], &nw, st));
+				cur = 1 - cur;
+			}
+			VK_HIP(hipEventRecord(c->ev[3], st));
+			VK_HIP(hipEventRecord(c->ev[4], st));
+			VK_HIP(hipMemcpy2DAsync(keys.data(), (size_t)kk * 8, c->d_bkeys[cur], (size_t)stride * 8, (size_t)kk * 8, (size_t)nq, hipMemcpyDeviceToHost, st));
+			VK_HIP(hipStreamSynchronize(st));
+			for (int i = 0; i < nq; i++) emit(base + i, keys.data() + (size_t)i * kk);
+		} else {
+			// larger result sets: vk_query's own selection, row by row of the matrix -- the block selection up to VK_MAX_MATCHES, beyond it
+			// the keys of all n cells of the row, sorted
+			for (int i = 0; i < nq; i++) {
+				const float *row = c->d_bspan + (size_t)i * (size_t)n_pad;
+				const uint64_t *d_sel = nullptr;
+				if (kk > VK_MAX_MATCHES) {
+					size_t temp_bytes = 0;
+					uint64_t *sorted = nullptr;
+					VK_HIP(vk_launch_sort_all(nullptr, n, floor, c->d_sort[0], c->d_sort[1], nullptr, &temp_bytes, &sorted, st));
+					if ((rc = c->d_sort_temp.reserve(temp_bytes, &c->device_bytes))) return rc;
+					VK_HIP(vk_launch_sort_all(row, n, floor, c->d_sort[0], c->d_sort[1], c->d_sort_temp, &temp_bytes, &sorted, st));
+					d_sel = sorted;
+				} else if ((rc = select_blocks(c, floor, kk, st, &d_sel, row))) return rc;
+				VK_HIP(hipMemcpyAsync(keys.data(), d_sel, (size_t)kk * 8, hipMemcpyDeviceToHost, st));
+				VK_HIP(hipStreamSynchronize(st));
+				emit(base + i, keys.data());
+			}
+			VK_HIP(hipEventRecord(c->ev[3], st));
+			VK_HIP(hipEventRecord(c->ev[4], st));
+			VK_HIP(hipStreamSynchronize(st));
+		}
+	}
+	c->have_scores = false;
+	state_timings(c, false);   // of the batch's last chunk (a batch within the matrix's cap: of the batch)
+	return VK_OK;
+}
+
 // The padded copy of a ragged corpus the batched GEMM runs on: sentences sorted into buckets by their length rounded up to
 // 16, 32, 48 or 64 tokens, every sentence padded with zero rows to its bucket's length (tile aligned: a wave's token tiles
 // then belong to whole sentences, as in a corpus of one sentence length), with the real length and the original index of
@@ -444,6 +591,9 @@ static int query_batch_body(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_q
 	const bool sourced = c->table_is_canonical();
 	if (sourced) gemm = false;
 	if (!gemm) {
+		// one-token queries over one-token slices: the span pass, before the shared pass would take them two at a time
+		const int rcs = query_batch_span(c, qs, n_queries, outs, keep);
+		if (rcs != VK_ERR_UNSUPPORTED) return rcs;
 		const int rcb = sourced ? VK_ERR_UNSUPPORTED : query_batch_shared_pass(c, qs, n_queries, outs, keep);
 		if (rcb != VK_ERR_UNSUPPORTED) return rcb;
 		c->batch_state[VK_BS_ROUTE] = 1;

@@ -846,6 +846,9 @@ int vk_batch_state(vk_corpus_t *c, int64_t *state) {
 	return VK_OK;
 }
 
+// Internal (tests; not part of the ABI): queries per LDS fill of the span pass over tiles of tile_bytes (vk_span_batch_host.h; 0: none)
+int32_t vk_span_batch_fill_queries(int32_t tile_bytes) { return vk_host::span_batch_fill_queries(tile_bytes); }
+
 // Internal (tests; not part of the ABI): the route of the last vk_query on this handle -- state[VK_QR_COUNT] in the order of
 // vk_query_route_index (all zero: no query yet)
 int vk_query_route(vk_corpus_t *c, int64_t *state) {

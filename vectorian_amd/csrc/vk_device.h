@@ -385,6 +385,20 @@ struct VkMixArgs {
 	vk_host::sim_mix mix;
 };
 
+// vk_span_batch_kernel (vk_span_batch.hip): one-token queries, 16 per packed query tile, against the one-token slices of a
+// span corpus; every column of the MFMA result is kept.  Geometry: vk_span_batch_host.h
+struct VkSpanBatchParams {
+	const uint8_t *tiles;      // the corpus's token tiles: 16 spans each
+	int64_t n_tiles;
+	int32_t tile_bytes, nk32, tail, prec;
+	const uint8_t *qtiles;     // packed query tiles of this launch, tile_bytes apart; rows past n_queries are zero
+	int32_t n_qtiles;          // ... how many
+	int32_t fill_tiles;        // query tiles a workgroup stages (blockIdx.y takes tiles fill_tiles * y ..)
+	int32_t n_queries;         // rows of the matrix this launch writes
+	int64_t n_pad;             // floats per row of the matrix: the spans rounded up to 16
+	float *matrix;             // [n_queries x n_pad] clipped cosines
+};
+
 #ifdef __cplusplus
 namespace vk_host { struct shadow_format; }   // vk_bound_host.h
 
@@ -469,6 +483,7 @@ int32_t vk_score_m7t_tail_k(void);   // ... and over the 8-bit shadow (vk_score_
 int32_t vk_score_m9f_takes(const VkScoreParams *p);
 hipError_t vk_launch_score_m9f(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
 hipError_t vk_launch_span(const VkScoreParams *p, hipStream_t stream);
+hipError_t vk_launch_span_batch(const VkSpanBatchParams *p, hipStream_t stream);   // a batch of one-token queries over the same tiles (vk_span_batch.hip)
 hipError_t vk_launch_score_batch(const VkScoreBatchParams *p, int32_t lt, size_t smem, hipStream_t stream);
 hipError_t vk_launch_topk_scores(const float *scores, int64_t n, float min_score, int32_t k, uint64_t *out,
 	int32_t *n_blocks_out, hipStream_t stream);

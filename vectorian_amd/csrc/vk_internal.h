@@ -10,6 +10,7 @@
 #include "vk_result_host.h"
 #include "vk_bound_host.h"
 #include "vk_route_host.h"
+#include "vk_span_batch_host.h"
 #include "vk_sim_ops_host.h"
 
 #include <algorithm>
@@ -183,7 +184,8 @@ struct vk_corpus_shape {
 };
 
 // vk_corpus::batch_state by index (the internal export vk_batch_state hands the array out in this order; the tests name the
-// entries in the same order).  Route: 1 query by query, 2 the shared pass, 3 the GEMM pass.
+// entries in the same order).  Route: 1 query by query, 2 the shared pass, 3 the GEMM pass, 4 the span pass (vk_span_batch_host.h; it
+// states n_qtiles and uniform_len).
 enum vk_batch_state_index {
 	VK_BS_ROUTE,
 	VK_BS_QB_MAX, VK_BS_LT, VK_BS_GAP_MODE,                                                     // the shared pass
@@ -211,6 +213,7 @@ struct vk_corpus : vk_corpus_shape {
 	int64_t device_bytes = 0;    // bytes of device memory this handle has allocated and not freed (declared before the buffers that count into it)
 	vk_devbuf<uint8_t> d_bq; vk_devbuf<int32_t> d_bqlen; vk_devbuf<float> d_bscores; vk_devbuf<uint64_t> d_bkeys[2];
 	vk_devbuf<float> d_braw;   // aligner scores of a batch of alignment queries
+	vk_devbuf<float> d_bspan;  // the score matrix [queries x spans] of a batch of one-token queries (vk_span_batch_kernel): this route's alone
 	// workspaces
 	vk_devbuf<uint8_t> d_stage;
 	vk_devbuf<uint8_t> d_qtile;

@@ -560,6 +560,38 @@ class HipSpanEncoderIndex(Index):
 			want_flow=False)
 		if progress:
 			progress(1.0)
+		return self._matches_from_top(query, top)
+
+	def find_many(self, texts, n=10, min_score=0.0, options: dict = dict(), in_flight=3, abort=None, batch=None, progress=None):
+		"""Several queries, with the keywords of HipBruteForceIndex.find_many: one embedding.encode and one Corpus.query_batch per
+		chunk of `batch` texts (default 256) -- a batch of one-vector queries over one-vector slices takes one pass of
+		vk_span_batch_kernel over the span vectors per LDS fill of queries, and every result set is what `find` returns
+		for that text.  in_flight is accepted and unused (one handle serves the chunks in turn); abort: an int32 array of one
+		element, polled between the chunks of a call; progress: called with done / total after every chunk.  Returns one Result
+		per text, in order."""
+		session = self.session
+		texts = list(texts)
+		queries = [self.make_query(t, n=n, min_score=min_score, options=options) for t in texts]
+		if abort is not None and not (isinstance(abort, np.ndarray) and abort.dtype == np.int32 and abort.size >= 1):
+			raise TypeError("abort must be an int32 numpy array")
+		per_call = 256 if batch is None or batch is True or batch is False else max(1, int(batch))
+		start = time.time()
+		results = []
+		for at in range(0, len(texts), per_call):
+			chunk = queries[at:at + per_call]
+			qv = np.ascontiguousarray(self._embedding.encode([q.text for q in chunk]))
+			if qv.shape[0] != len(chunk):
+				raise RuntimeError("a query produced more than one embedding")
+			tops = self._corpus.query_batch([qv[i:i + 1] for i in range(len(chunk))], q_normalize=True, locality=core.Locality.LOCAL,
+				gap_s=0.0, gap_t=0.0, max_matches=int(n), min_score=float(min_score), want_flow=False,
+				**({} if abort is None else {"abort_flag": abort}))
+			results.extend(self._matches_from_top(q, top) for q, top in zip(chunk, tops))
+			if progress:
+				progress(len(results) / len(texts))
+		duration = (time.time() - start) / max(1, len(texts))
+		return [session.make_result(self, m, duration=duration) for m in results]
+
+	def _matches_from_top(self, query, top):
 		matches = []
 		for i in range(top.n):
 			g = int(top.sentence[i])
