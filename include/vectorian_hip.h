@@ -226,6 +226,27 @@ int vk_corpus_create(const vk_corpus_desc *desc, vk_corpus_t **out);
  * rows: [n_rows x d] row-major, dtype f32/bf16, in host or device memory.
  * normalize=1 L2-normalises each row (Vectors.normalized, vectorian/embedding/vectors.py:71-80). */
 int vk_corpus_append_vectors(vk_corpus_t *c, const void *rows, int64_t n_rows, int32_t dtype, int32_t mem, int32_t normalize);
+/* Appends n_spans rows to the span corpus -- a VK_LAYOUT_CONTEXTUAL handle with one row per span, not finalized -- each the mean,
+ * minimum or maximum of a span's token vectors (AggregatedTokenImpl, vectorian/embedding/span.py:27-93), pooled on the device
+ * (vk_pool_spans_kernel) and packed as vk_corpus_append_vectors(.., VK_MEM_DEVICE, normalize) packs the same fp32 rows.
+ *   rows: [n_rows x d] row-major, f32 / bf16, host or device (mem): the token rows, or the vocabulary when ids != NULL;
+ *   ids (host, n_ids entries, or NULL): the vocabulary row of every token; span i is then rows[ids[t]] for t in [start[i], end[i]);
+ *   start, end (host, n_spans entries): span i is rows[start[i] .. end[i]) (ids == NULL) -- spans may overlap or be empty;
+ *   pooled_out (host, [n_spans x d] floats, or NULL): receives the fp32 aggregates.
+ * The arithmetic is the reference's agg(v, axis=0) over the UNMODIFIED rows (bf16 widened exactly), stated in csrc/vk_pool_host.h:
+ * MEAN is a sequential fp32 sum in token order divided once by (float)n; MIN / MAX propagate NaN; a span without tokens is a row of
+ * NaN (which packs to a zero row).  The buffers of a call are freed before it returns: the caller bounds a call's size.
+ * VK_ERR_INVALID: null arguments; unknown agg / dtype / mem; start[i] > end[i]; an index outside rows (ids == NULL) or ids; an id
+ * outside [0, n_rows); more rows than declared.  VK_ERR_STATE: a finalized handle, or a view.  VK_ERR_UNSUPPORTED: a
+ * VK_LAYOUT_STATIC handle; a handle with a similarity source or combinator; a span of more than 2^24 tokens.  Nothing is enqueued
+ * before validation passes, and a refused call leaves the handle as it was. */
+enum { VK_POOL_MEAN = 0, VK_POOL_MIN = 1, VK_POOL_MAX = 2 };
+int vk_corpus_append_pooled(vk_corpus_t *c,
+	const void *rows, int64_t n_rows, int32_t dtype, int32_t mem,
+	const int32_t *ids, int64_t n_ids,
+	const int64_t *start, const int64_t *end, int64_t n_spans,
+	int32_t agg, int32_t normalize,
+	float *pooled_out);
 /* VK_LAYOUT_STATIC: token ids of the whole shard (Token.id, common.h:34-42) */
 int vk_corpus_set_token_ids(vk_corpus_t *c, const int32_t *ids, int64_t n, int32_t mem);
 /* universal POS code per token occurrence (Token.pos, common.h:34-42); only needed by tag-weighted queries */

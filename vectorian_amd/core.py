@@ -40,6 +40,8 @@ VK_SIMSRC_COSINE, VK_SIMSRC_PNORM, VK_SIMSRC_SQRT_COSINE = 0, 1, 2
 # token similarity combinators over several static embeddings (vk_corpus_set_sim_mix; vectorian_amd/modifier.py states each one)
 VK_MAX_SIM_OPERANDS = 4
 VK_SIMMIX_NONE, VK_SIMMIX_AVERAGE, VK_SIMMIX_MAXIMUM = 0, 1, 2
+# the aggregates of pooled span vectors (vk_corpus_append_pooled; vectorian_amd/sim.py AggregatedSpanEmbedding)
+VK_POOL_MEAN, VK_POOL_MIN, VK_POOL_MAX = 0, 1, 2
 
 
 class Locality(enum.IntEnum):
@@ -101,7 +103,7 @@ class _Timings(C.Structure):
 
 EXPORTS = [
 	"vk_abi_version", "vk_last_error", "vk_init", "vk_device_count", "vk_corpus_view",
-	"vk_corpus_create", "vk_corpus_append_vectors", "vk_corpus_set_token_ids", "vk_corpus_set_token_pos", "vk_corpus_set_token_tags", "vk_corpus_filter", "vk_corpus_set_sim_ops", "vk_corpus_set_sim_source",
+	"vk_corpus_create", "vk_corpus_append_vectors", "vk_corpus_append_pooled", "vk_corpus_set_token_ids", "vk_corpus_set_token_pos", "vk_corpus_set_token_tags", "vk_corpus_filter", "vk_corpus_set_sim_ops", "vk_corpus_set_sim_source",
 	"vk_corpus_set_sim_mix", "vk_corpus_set_sim_operand", "vk_corpus_append_operand_vectors", "vk_corpus_set_query_operand",
 	"vk_corpus_set_sentences", "vk_corpus_set_slices", "vk_corpus_finalize", "vk_corpus_free", "vk_corpus_device_bytes",
 	"vk_query", "vk_query_batch", "vk_last_scores", "vk_last_timings", "vk_merge_topk",
@@ -145,6 +147,8 @@ def lib():
 		L.vk_last_error.restype = C.c_char_p
 		L.vk_corpus_create.argtypes = [C.POINTER(_CorpusDesc), C.POINTER(C.c_void_p)]
 		L.vk_corpus_append_vectors.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32]
+		L.vk_corpus_append_pooled.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+			C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
 		L.vk_corpus_set_token_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
 		L.vk_corpus_set_token_pos.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
 		L.vk_corpus_set_token_tags.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
@@ -230,6 +234,20 @@ def gap_to_struct(gap, keep, n_table):
 	else:
 		raise ValueError(gap)
 	return g
+
+
+_POOL_CODES = {np.mean: VK_POOL_MEAN, np.min: VK_POOL_MIN, np.max: VK_POOL_MAX, "mean": VK_POOL_MEAN, "min": VK_POOL_MIN, "max": VK_POOL_MAX}
+
+
+def pool_code(agg):
+	"""the VK_POOL_* code of an aggregate: np.mean / np.min / np.max, their names, or the code itself.  Nothing else is pooled on the
+	device, and there is no other place to pool (NotImplementedError)"""
+	if isinstance(agg, (int, np.integer)) and not isinstance(agg, bool):
+		return int(agg)   # (the library checks it)
+	try:
+		return _POOL_CODES[agg]
+	except (KeyError, TypeError):
+		raise NotImplementedError(f"{agg}: span vectors are pooled with np.mean, np.min or np.max") from None
 
 
 def winner_rows(longest):

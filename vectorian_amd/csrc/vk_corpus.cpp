@@ -3,6 +3,10 @@
 // would compute returns VK_ERR_NO_DEVICE / VK_ERR_HIP.
 
 #include "vk_internal.h"
+#include "vk_pool_host.h"
+
+static_assert(vk_host::POOL_MEAN == VK_POOL_MEAN && vk_host::POOL_MIN == VK_POOL_MIN && vk_host::POOL_MAX == VK_POOL_MAX, "vk_pool_host.h and the C-ABI");
+static_assert(vk_host::POOL_INVALID == VK_ERR_INVALID && vk_host::POOL_UNSUPPORTED == VK_ERR_UNSUPPORTED, "vk_pool_host.h and the C-ABI");
 
 std::string &vk_error_slot() {
 	static thread_local std::string err;
@@ -236,6 +240,67 @@ int vk_corpus_append_vectors(vk_corpus_t *c, const void *rows, int64_t n_rows, i
 	}
 	c->rows_appended += n_rows;
 	return VK_OK;
+}
+
+// Span vectors pooled from token rows on the device (vk_pool_host.h, vk_pool.hip), appended as vk_corpus_append_vectors
+// appends rows in device memory.  Everything is validated before anything is enqueued; the rows, ids, spans and aggregates live in
+// buffers of this call, which die after the stream has drained -- on every path (vk_guard.h).
+static int append_pooled_body(vk_corpus *c, const void *rows, int64_t n_rows, int32_t dtype, int32_t mem, const int32_t *ids, int64_t n_ids,
+	const int64_t *start, const int64_t *end, int64_t n_spans, int32_t agg, int32_t normalize, float *pooled_out,
+	vk_devbuf<uint8_t> &d_rows, vk_devbuf<int32_t> &d_ids, vk_devbuf<int64_t> &d_spans, vk_devbuf<float> &d_pooled) {
+	if (n_spans == 0) return VK_OK;
+	const int d = c->desc.d;
+	const size_t row_bytes = (dtype == VK_F32 ? 4 : 2) * (size_t)d;
+	VK_HIP(hipSetDevice(c->device));
+	const void *dev_rows = rows;
+	if (mem == VK_MEM_HOST) {
+		if (int rc = d_rows.reserve((size_t)n_rows * row_bytes, nullptr)) return rc;
+		if (n_rows > 0) VK_HIP(hipMemcpyAsync(d_rows, rows, (size_t)n_rows * row_bytes, hipMemcpyHostToDevice, c->stream));
+		dev_rows = d_rows;
+	}
+	if (ids) {
+		if (int rc = d_ids.reserve((size_t)n_ids, nullptr)) return rc;
+		if (n_ids > 0) VK_HIP(hipMemcpyAsync(d_ids, ids, (size_t)n_ids * 4, hipMemcpyHostToDevice, c->stream));
+	}
+	if (int rc = d_spans.reserve(2 * (size_t)n_spans, nullptr)) return rc;
+	VK_HIP(hipMemcpyAsync(d_spans, start, (size_t)n_spans * 8, hipMemcpyHostToDevice, c->stream));
+	VK_HIP(hipMemcpyAsync(d_spans + n_spans, end, (size_t)n_spans * 8, hipMemcpyHostToDevice, c->stream));
+	if (int rc = d_pooled.reserve((size_t)n_spans * (size_t)d, nullptr)) return rc;
+	VK_HIP(vk_launch_pool_spans(dev_rows, dtype == VK_BF16, ids ? (const int32_t *)d_ids : nullptr, d_spans, d_spans + n_spans, n_spans, d, agg,
+		d_pooled, c->stream));
+	VK_HIP(vk_launch_pack(d_pooled, 0, n_spans, d, c->d_pad, c->rows_appended, c->d_tiles, c->d_mag, normalize, c->prec, c->stream));
+	if (pooled_out) VK_HIP(hipMemcpyAsync(pooled_out, d_pooled, (size_t)n_spans * (size_t)d * 4, hipMemcpyDeviceToHost, c->stream));
+	VK_HIP(hipStreamSynchronize(c->stream));
+	c->rows_appended += n_spans;
+	return VK_OK;
+}
+
+int vk_corpus_append_pooled(vk_corpus_t *c, const void *rows, int64_t n_rows, int32_t dtype, int32_t mem, const int32_t *ids, int64_t n_ids,
+	const int64_t *start, const int64_t *end, int64_t n_spans, int32_t agg, int32_t normalize, float *pooled_out) {
+	if (!c || (!rows && n_rows > 0) || ((!start || !end) && n_spans > 0)) return fail(VK_ERR_INVALID, "null argument");
+	if (c->finalized) return fail(VK_ERR_STATE, "corpus already finalized");
+	if (c->is_view) return fail(VK_ERR_STATE, "rows are appended to the owning handle, before taking views");
+	if (c->desc.layout != VK_LAYOUT_CONTEXTUAL)
+		return fail(VK_ERR_UNSUPPORTED, "pooled span vectors are appended to a VK_LAYOUT_CONTEXTUAL handle (one row per span): this corpus is VK_LAYOUT_STATIC");
+	if (c->sim_src.kind != VK_SIMSRC_COSINE || c->mixed() || c->raw_rows)
+		return fail(VK_ERR_UNSUPPORTED, "pooled span vectors under a similarity source or combinator: the span corpus computes the cosine");
+	if (dtype != VK_F32 && dtype != VK_BF16) return fail(VK_ERR_INVALID, "bad dtype");
+	if (mem != VK_MEM_HOST && mem != VK_MEM_DEVICE) return fail(VK_ERR_INVALID, "bad memory kind");
+	if (!vk_host::pool_agg_ok(agg)) return fail(VK_ERR_INVALID, "unknown aggregate " + std::to_string(agg) + " (VK_POOL_MEAN, VK_POOL_MIN, VK_POOL_MAX)");
+	if (n_rows < 0 || n_spans < 0 || (ids && n_ids < 0)) return fail(VK_ERR_INVALID, "a negative count");
+	if (c->rows_appended + n_spans > c->rows_total) return fail(VK_ERR_INVALID, "more rows appended than declared");
+	const char *why = "";
+	if (const int bad = vk_host::pool_check_spans(n_rows, ids, n_ids, start, end, n_spans, &why))
+		return fail(bad == vk_host::POOL_UNSUPPORTED ? VK_ERR_UNSUPPORTED : VK_ERR_INVALID, std::string("vk_corpus_append_pooled: ") + why);
+	// (declared here: they are freed after the guard has drained the stream)
+	vk_devbuf<uint8_t> d_rows;
+	vk_devbuf<int32_t> d_ids;
+	vk_devbuf<int64_t> d_spans;
+	vk_devbuf<float> d_pooled;
+	return vk_run_guarded(
+		[&](vk_host_keep &) { return append_pooled_body(c, rows, n_rows, dtype, mem, ids, n_ids, start, end, n_spans, agg, normalize, pooled_out, d_rows, d_ids, d_spans, d_pooled); },
+		[&]() { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream); },
+		[](const char *what) { return fail(VK_ERR_INVALID, std::string("vk_corpus_append_pooled: ") + what); });
 }
 
 int vk_corpus_set_token_ids(vk_corpus_t *c, const int32_t *ids, int64_t n, int32_t mem) {

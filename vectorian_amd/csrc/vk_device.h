@@ -453,6 +453,10 @@ hipError_t vk_launch_topk_unsorted(const uint64_t *in, int32_t n, int32_t k, uin
 hipError_t vk_launch_key_groups(const uint64_t *keys, int32_t n, int32_t *groups, hipStream_t stream);
 hipError_t vk_launch_pack(const void *in, int32_t dtype_bf16, int64_t n_rows, int32_t d, int32_t d_pad, int64_t row0,
 	uint8_t *tiles, float *mag_out, int32_t normalize, int32_t prec, hipStream_t stream);
+// span vectors pooled from token rows (vk_pool.hip; vk_pool_host.h): out [n_spans x d] fp32 = agg of rows[start .. end), or of
+// rows[ids[start .. end)] when ids is given; everything on the device
+hipError_t vk_launch_pool_spans(const void *rows, int32_t dtype_bf16, const int32_t *ids, const int64_t *start, const int64_t *end,
+	int64_t n_spans, int32_t d, int32_t agg, float *out, hipStream_t stream);
 // queries of 17..32 tokens, linear / affine gaps (vk_score32.hip)
 size_t vk_score32_lds_bytes(int32_t nk32, int32_t tail, int32_t max_pair_tiles, int32_t len_t, int32_t gap_mode, int32_t waves);
 int32_t vk_score32_waves(int32_t nk32, int32_t tail, int32_t max_pair_tiles, int32_t len_t, int32_t gap_mode);   // waves per workgroup that fit the LDS: 4, 2, 1 or 0 (none)

@@ -75,6 +75,40 @@ class Corpus:
 		"""ptr: device pointer (e.g. torch.Tensor.data_ptr()) to [n_rows x d] row-major rows."""
 		_core._check(_core.lib().vk_corpus_append_vectors(self._h, C.c_void_p(ptr), n_rows, dtype, _core.VK_MEM_DEVICE, int(normalize)))
 
+	def append_pooled(self, rows, start, end, agg, ids=None, normalize=True, want_pooled=False):
+		"""one row per span, pooled from token rows on the device (vk_corpus_append_pooled): span i is rows[start[i] .. end[i]), or
+		rows[ids[start[i] .. end[i])] when `ids` names a row of the vocabulary `rows` for every token.
+		rows: numpy float32 / uint16(bf16) [n x d] on the host; agg: np.mean / np.min / np.max, "mean" / "min" / "max" or a
+		core.VK_POOL_* code; want_pooled: returns the fp32 aggregates [n_spans x d] (a span without tokens: a row of NaN)"""
+		rows = np.ascontiguousarray(rows)
+		if rows.dtype == np.float32:
+			dt = _core.VK_F32
+		elif rows.dtype == np.uint16:
+			dt = _core.VK_BF16
+		else:
+			raise TypeError(f"vectors must be float32 or uint16 (bf16 bits), got {rows.dtype}")
+		if rows.ndim != 2 or rows.shape[1] != self.d:
+			raise ValueError(f"expected [n x {self.d}] vectors, got {rows.shape}")
+		return self._append_pooled(rows.ctypes.data, rows.shape[0], dt, _core.VK_MEM_HOST, start, end, agg, ids, normalize, want_pooled)
+
+	def append_pooled_device(self, ptr, n_rows, dtype, start, end, agg, ids=None, normalize=True, want_pooled=False):
+		"""append_pooled over rows in device memory: ptr is a device pointer (e.g. torch.Tensor.data_ptr()) to [n_rows x d] row-major
+		rows; spans and ids stay host arrays"""
+		return self._append_pooled(ptr, n_rows, dtype, _core.VK_MEM_DEVICE, start, end, agg, ids, normalize, want_pooled)
+
+	def _append_pooled(self, ptr, n_rows, dtype, mem, start, end, agg, ids, normalize, want_pooled):
+		start = np.ascontiguousarray(start, dtype=np.int64)
+		end = np.ascontiguousarray(end, dtype=np.int64)
+		if start.ndim != 1 or start.shape != end.shape:
+			raise ValueError("start and end must hold one entry per span")
+		if ids is not None:
+			ids = np.ascontiguousarray(ids, dtype=np.int32)
+		pooled = np.empty((len(start), self.d), dtype=np.float32) if want_pooled else None
+		_core._check(_core.lib().vk_corpus_append_pooled(self._h, C.c_void_p(ptr), int(n_rows), int(dtype), int(mem),
+			None if ids is None else _core._np_ptr(ids), 0 if ids is None else len(ids), _core._np_ptr(start), _core._np_ptr(end), len(start),
+			_core.pool_code(agg), int(normalize), None if pooled is None else _core._np_ptr(pooled)))
+		return pooled
+
 	def set_token_ids(self, ids):
 		ids = np.ascontiguousarray(ids, dtype=np.int32)
 		_core._check(_core.lib().vk_corpus_set_token_ids(self._h, _core._np_ptr(ids), len(ids), _core.VK_MEM_HOST))

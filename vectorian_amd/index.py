@@ -29,7 +29,7 @@ from vectorian_amd.query import PreparedQuery, Query, default_tokenizer
 from vectorian_amd.alignment import WordRotatorsDistance
 from vectorian_amd.modifier import (ExtremumTokenSimilarity, MixedTokenSimilarity, TokenSimilarityModifier,
 	UnaryTokenSimilarityModifier)
-from vectorian_amd.sim import (CosineSim, EmbeddingTokenSim, EuclideanDistance, ImprovedSqrtCosineSim, ModifiedVectorSim, OptimizedSpanSim,
+from vectorian_amd.sim import (AggregatedSpanEmbedding, CosineSim, EmbeddingTokenSim, EuclideanDistance, ImprovedSqrtCosineSim, ModifiedVectorSim, OptimizedSpanSim,
 	PNormDistance)
 
 PartitionData = collections.namedtuple("PartitionData", ["level", "window_size", "window_step"])
@@ -528,6 +528,8 @@ class HipSpanEncoderIndex(Index):
 
 	def __init__(self, partition, embedding, span_sim, nlp=None, vectors=None, device=0, corpus_factory=None):
 		super().__init__(partition, span_sim)
+		if nlp is not None and isinstance(embedding, AggregatedSpanEmbedding):
+			embedding = embedding.with_nlp(nlp)   # its queries are tokenised as the index's
 		self._embedding = embedding
 		self._nlp = nlp
 		session = self.session
@@ -538,18 +540,51 @@ class HipSpanEncoderIndex(Index):
 				self._slice_doc.append(di)
 				self._slice_id.append(sid)
 		n = len(self._slice_doc)
-		if vectors is None:
-			size = partition.window_size
-			texts = [" ".join(session.documents[di].span_tokens(level, sid, size)) for di, sid in zip(self._slice_doc, self._slice_id)]
-			vectors = embedding.encode(texts)
-		vectors = np.ascontiguousarray(vectors, dtype=np.float32)
-		if vectors.shape != (n, embedding.dimension):
-			raise ValueError(f"expected {(n, embedding.dimension)} span vectors, got {vectors.shape}")
+		# an AggregatedSpanEmbedding without vectors= : pooled on the device from the token rows
+		pooled = vectors is None and isinstance(embedding, AggregatedSpanEmbedding)
+		if not pooled:
+			if vectors is None:
+				size = partition.window_size
+				texts = [" ".join(session.documents[di].span_tokens(level, sid, size)) for di, sid in zip(self._slice_doc, self._slice_id)]
+				vectors = embedding.encode(texts)
+			vectors = np.ascontiguousarray(vectors, dtype=np.float32)
+			if vectors.shape != (n, embedding.dimension):
+				raise ValueError(f"expected {(n, embedding.dimension)} span vectors, got {vectors.shape}")
 		make = corpus_factory or core.Corpus
 		self._corpus = make(layout=core.VK_LAYOUT_CONTEXTUAL, d=embedding.dimension, n_tokens=n, n_sentences=n, device=device)
-		self._corpus.append_vectors(vectors, normalize=True)
+		if pooled:
+			self._append_pooled(embedding)
+		else:
+			self._corpus.append_vectors(vectors, normalize=True)
 		self._corpus.set_sentences(np.arange(n + 1, dtype=np.int64))
 		self._corpus.finalize()
+
+	def _append_pooled(self, embedding):
+		"""the span corpus of an AggregatedSpanEmbedding: the token ranges of the slices -- Spans::iterate over every document, as
+		HipBruteForceIndex enumerates them: window i of a document starts at span i * step and covers `size` spans, fewer at the end
+		-- pooled by Corpus.append_pooled.  A static embedding: one call, the vocabulary's rows and the documents' token ids; a
+		contextual one: one call per document with its token vectors."""
+		session, partition = self.session, self.partition
+		level, size, step = partition.level, partition.window_size, partition.window_step
+		emb = embedding.token_embedding
+		ranges = []   # per document: the token ranges of its slices, in the document's tokens
+		for doc in session.documents:
+			st, en = doc.spans[level]["start"], doc.spans[level]["end"]
+			sids = np.arange(0, len(st), step)
+			last = np.minimum(sids + size - 1, len(st) - 1)
+			ranges.append((np.asarray(st, dtype=np.int64)[sids], np.asarray(en, dtype=np.int64)[last]))
+		if emb.is_static:
+			rows = emb.encode_tokens(session.vocab.tokens).unmodified if session.vocab.size else np.zeros((1, emb.dimension), np.float32)
+			bases = np.concatenate(([0], np.cumsum([doc.n_tokens for doc in session.documents]))).astype(np.int64)
+			ids = np.concatenate([session.doc_token_ids(i) for i in range(len(session.documents))] or [np.zeros(0, np.int32)])
+			start = np.concatenate([a + base for (a, _), base in zip(ranges, bases)] or [np.zeros(0, np.int64)])
+			end = np.concatenate([b + base for (_, b), base in zip(ranges, bases)] or [np.zeros(0, np.int64)])
+			self._corpus.append_pooled(rows, start, end, embedding.agg, ids=ids, normalize=True)
+		elif emb.is_contextual:
+			for doc, (start, end) in zip(session.documents, ranges):
+				self._corpus.append_pooled(doc.contextual_vectors(emb.name), start, end, embedding.agg, normalize=True)
+		else:
+			raise TypeError(emb)
 
 	def _find(self, query, progress=None):
 		qv = self._embedding.encode([query.text])

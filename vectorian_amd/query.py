@@ -9,6 +9,12 @@ def default_tokenizer(text):
 	return text.split()
 
 
+def tokenize(text, nlp=None):
+	"""the tokens of a query text: `nlp`'s (plain strings, or dicts with 'text' / 'pos' / 'tag' as spaCy's doc.to_json()["tokens"]), or
+	the default tokenizer's.  The one call every query goes through (PreparedQuery; AggregatedSpanEmbedding.encode)"""
+	return list((nlp or default_tokenizer)(text))
+
+
 class Query:
 	def __init__(self, index, vocab, text, options):
 		self._index = index
@@ -47,8 +53,7 @@ class PreparedQuery:
 
 	def __init__(self, query, vocab, nlp):
 		self._query = query
-		raw = list((nlp or default_tokenizer)(query.text))
-		# nlp may return plain strings, or dicts with 'text' / 'pos' / 'tag' (as spaCy's doc.to_json()["tokens"])
+		raw = tokenize(query.text, nlp)
 		tokens, self._pos, self._tags = [], [], []
 		for t in raw:
 			if isinstance(t, dict):

@@ -12,6 +12,9 @@ the unmodified vectors): `ModifiedVectorSim(PNormDistance(2), Scale(1 / 12), Dis
 TokenSimilarityModifier / MixedTokenSimilarity / MaximumTokenSimilarity / MinimumTokenSimilarity   vectorian/sim/modifier.py
 (vectorian_amd/modifier.py, re-exported here): combinators of up to four EmbeddingTokenSims over static embeddings run on the device
 (DESIGN 14): `MixedTokenSimilarity([EmbeddingTokenSim(a, CosineSim()), EmbeddingTokenSim(b, CosineSim())], [2, 1])`.
+SpanEmbedding / AggregatedSpanEmbedding / EmbeddedSpanSim   vectorian/embedding/span.py:27-93, vectorian/sim/span.py:74-95: one vector
+per span, from the caller or -- the mean, minimum or maximum of the span's token vectors -- pooled on the device:
+`AggregatedSpanEmbedding(emb, np.mean).to_sentence_sim()`.
 FuzzyJaccardSim, DirectionalDistance, user-defined VectorSims, chains and combinators over contextual embeddings, nested
 combinators, UnaryTokenSimilarityModifier and a combinator under WordRotatorsDistance are out of scope and are rejected explicitly
 rather than ignored; the tag-weighted variant is a "next" row.
@@ -21,6 +24,7 @@ import numpy as np
 
 from vectorian_amd.alignment import ConstantGapCost, LocalAlignment, Optimizer
 from vectorian_amd.embedding import AbstractVectors
+from vectorian_amd.query import tokenize
 from vectorian_amd.kernel import (  # noqa: F401  (the reference's users import the operators next to the similarities)
 	Bias, DistanceToSimilarity, Kernel, Power, RadialBasis, Scale, Threshold, UnaryOperator)
 
@@ -271,6 +275,60 @@ class SpanEmbedding:
 	def encode(self, texts):
 		v = np.ascontiguousarray(self._encode(texts), dtype=np.float32)
 		return v.reshape(len(texts), self._dimension)
+
+
+class AggregatedSpanEmbedding(SpanEmbedding):
+	"""the mean, minimum or maximum of a span's token vectors, static or contextual (AggregatedTokenImpl,
+	vectorian/embedding/span.py:27-93): `AggregatedSpanEmbedding(emb, np.max).to_sentence_sim()`.  The spans of an index are pooled on
+	the device from the token rows the alignment index uses (HipSpanEncoderIndex -> Corpus.append_pooled) -- np.mean,
+	np.min and np.max only: there is no other place in this package to pool.  A query is one span and is pooled here, on the host,
+	by the reference's own numpy call."""
+
+	_default_functions = {np.mean: "mean", np.min: "min", np.max: "max"}
+
+	def __init__(self, token_embedding, agg=np.mean, agg_name=None, nlp=None):
+		try:
+			known = AggregatedSpanEmbedding._default_functions.get(agg)
+		except TypeError:   # (not hashable)
+			known = None
+		if known is None:
+			raise NotImplementedError(f"{agg}: span vectors are pooled on the device with np.mean, np.min or np.max; there is no CPU path for other aggregates")
+		self._token_embedding = token_embedding
+		self._agg = agg
+		self._agg_name = known if agg_name is None else agg_name
+		self._nlp = nlp
+
+	@property
+	def name(self):
+		return f"aggregated-{self._agg_name}-{self._token_embedding.name}"
+
+	@property
+	def dimension(self):
+		return self._token_embedding.dimension
+
+	@property
+	def token_embedding(self):
+		return self._token_embedding
+
+	@property
+	def agg(self):
+		return self._agg
+
+	def with_nlp(self, nlp):
+		"""this embedding with `nlp` as the tokenizer of its queries (an index hands its own on)"""
+		return AggregatedSpanEmbedding(self._token_embedding, self._agg, self._agg_name, nlp=nlp)
+
+	def to_sentence_sim(self, vector_sim=None):
+		return EmbeddedSpanSim(self, vector_sim)
+
+	def encode(self, texts):
+		out = np.full((len(texts), self.dimension), np.nan, dtype=np.float32)   # a text without tokens: the reference's out.fill(np.nan)
+		for i, text in enumerate(texts):
+			tokens = [t["text"] if isinstance(t, dict) else t for t in tokenize(text, self._nlp)]
+			v = self._token_embedding.encode_tokens(tokens).unmodified
+			if v.shape[0] > 0:
+				out[i, :] = self._agg(v, axis=0)
+		return out
 
 
 class EmbeddedSpanSim(SpanSim):
