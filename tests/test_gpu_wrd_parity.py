@@ -101,3 +101,38 @@ def test_transport_flow_outputs(hip, oracle):
 			raw = ((1.0 - np.maximum(1.0 - S.T, 0.0)) * G).sum() / G.sum()
 			assert abs(raw - got.raw_score[i]) < 1e-5
 	c.close()
+
+
+@pytest.mark.parametrize("algorithm", ["wrd", "wmd"])
+def test_listed_slices_with_an_empty_one(hip, oracle, algorithm):
+	"""vk_query_desc.only_slices under the exact transports over a corpus that holds empty slices: every listed slice solved, in the
+	caller's order; an empty one, which no solver takes, is stated with -inf for its score and its aligner score and without a flow"""
+	rng = np.random.default_rng(61)
+	n, d, len_t = 128, 32, 4
+	lens = rng.integers(1, 17, size=n)
+	lens[[5, 40, 127]] = 0
+	off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+	X = (rng.standard_normal((int(off[-1]), d)) * rng.lognormal(0, 0.25, size=(int(off[-1]), 1))).astype(np.float32)
+	Xb, mag = oracle.normalize_rows_bf16(X)
+	c = hip.Corpus(layout=hip.VK_LAYOUT_CONTEXTUAL, d=d, n_tokens=X.shape[0], n_sentences=n, keep_magnitudes=True)
+	c.append_vectors(X, normalize=True)
+	c.set_sentences(off)
+	c.finalize()
+	qv = (X[int(off[17]):int(off[17]) + 1].repeat(len_t, axis=0) + 0.3 * rng.standard_normal((len_t, d))).astype(np.float32)
+	Qb, qmag = oracle.normalize_rows_bf16(qv)
+	if algorithm == "wrd":
+		okw, hkw = dict(algorithm=oracle.ALG_WRD, X_mag=mag, Q_mag=qmag), dict(algorithm=hip.VK_ALG_WRD)
+	else:
+		okw, hkw = dict(algorithm=oracle.ALG_RWMD, rwmd=(False, False, True), wmd_full=True), dict(algorithm=hip.VK_ALG_RWMD, rwmd=(False, False, True), wmd_full=True)
+	ref = oracle.find(layout=oracle.LAYOUT_CONTEXTUAL, d=d, sent_off=off, X=Xb, Q=Qb, max_matches=n, min_score=-10.0, **okw)
+	by_sent = {int(s): j for j, s in enumerate(ref["sentence"])}
+	ids = np.array([9, 5, 100, 127, 17, 40, 3], dtype=np.int64)
+	got = c.query(qv, q_normalize=True, only_slices=ids, **hkw)
+	assert got.n == len(ids) and list(got.sentence[:got.n]) == list(ids)
+	for i, s in enumerate(ids):
+		if lens[s] == 0:
+			assert got.score[i] == -np.inf and got.raw_score[i] == -np.inf
+		else:
+			assert abs(got.score[i] - ref["score"][by_sent[int(s)]]) < 1e-5
+		assert (got.mapping[i] == -1).all() and (got.edge_sim[i] == 0).all()
+	c.close()

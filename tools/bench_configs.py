@@ -35,6 +35,8 @@ def main():
 	ap.add_argument("--k", type=int, default=10)
 	ap.add_argument("--layout", choices=["contextual", "static"], default="contextual")
 	ap.add_argument("--batch", type=int, default=0, help="queries per vk_query_batch call (config 4: 256)")
+	ap.add_argument("--batch-flows", action="store_true", help="with --batch: flows asked for, so that every query's winners are restated from their "
+		"similarity rows on the host (batch_winner_rows) instead of written from the scores of the pass")
 	ap.add_argument("--precision", choices=["bf16", "f32"], default="bf16", help="how the unit rows are kept in HBM")
 	ap.add_argument("--handles", type=int, default=1, help="queries in flight (vk_corpus_view handles, one host thread each), as bench.py keeps them")
 	ap.add_argument("--filter", type=float, default=0.0, help="share of tokens a pos_filter drops: times vk_corpus_filter, then queries the filtered corpus")
@@ -264,7 +266,7 @@ def main():
 				bq[i] = np.ascontiguousarray(E[qi] + 0.05 * rng.standard_normal((args.len_t, args.d)).astype(np.float32), dtype=np.float32)
 		def bstep():
 			return corpus.query_batch(bq, algorithm=alg, locality=loc, gap_s=gap, gap_t=gap, q_normalize=True, max_matches=args.k,
-				min_score=0.0 if loc != 1 else -1e9, want_flow=False)
+				min_score=0.0 if loc != 1 else -1e9, want_flow=args.batch_flows)
 		for i in range(args.warmup):
 			bstep()
 		torch.cuda.synchronize()
@@ -286,7 +288,7 @@ def main():
 			padded = float(np.sum((lens + 15) // 16 * 16))
 			flops_padded = 2.0 * padded * args.batch * 16 * ((args.d + 31) // 32 * 32)
 		print(json.dumps({
-			"alg": args.alg, "batch": args.batch, "d": args.d, "len_t": args.len_t, "len_s": [args.min_len, args.max_len],
+			"alg": args.alg, "batch": args.batch, "flows": args.batch_flows, "d": args.d, "len_t": args.len_t, "len_s": [args.min_len, args.max_len],
 			"sentences": args.sentences, "pairs_per_s": args.sentences * args.batch * args.steps / el,
 			"ms_per_batch": el / args.steps * 1e3, "gemm_kernel_ms": score_ms,
 			"algorithmic_TFLOPs": flops / (score_ms * 1e-3) / 1e12, "issued_mfma_TFLOPs": flops_padded / (score_ms * 1e-3) / 1e12,

@@ -109,40 +109,30 @@ static int batch_winner_rows(vk_corpus *c, const vk_query_desc *qs, int n_querie
 	// the score of every candidate from its rows, in the reference's order of operations (vk_transport_host.h; contextual layout:
 	// every position is a vocabulary entry); the k best of a query's kk candidates, in the order of the result set
 	auto rank_range = [&](int i0, int i1) {
-		std::vector<int> order;
-		std::vector<float> val((size_t)kk), raw((size_t)kk);
+		vk_host::result_set rs;   // (one per thread, from query to query)
 		std::vector<int32_t> key_s, key_t;   // static layout: vocabulary keys (token ids) of both sides (alignment/bow.h:204-275)
 		for (int i = i0; i < i1; i++) {
 			const vk_query_desc &q = qs[i];
 			vk_topk_out *out = &outs[i];
-			order.clear();
 			const size_t at = (size_t)first[(size_t)i];
-			const auto row_at = [&](int j) { return (int64_t)key_row(keys[(size_t)i * kk + j]); };
-			for (int j = 0; j < first[(size_t)i + 1] - first[(size_t)i]; j++) {
-				const int64_t g = row_at(j);
+			vk_host::selected sel;   // the candidates that travelled; rows are slices here
+			sel.keys = keys + (size_t)i * kk; sel.cap = first[(size_t)i + 1] - first[(size_t)i];
+			vk_host::score_selected(sel, rs, q.min_score, k, false, [&](int j) -> std::pair<float, float> {
+				const int64_t g = sel.row(j);
 				const int t_a = (*c->h_start)[(size_t)g], len_s = (*c->h_end)[(size_t)g] - t_a;
 				const bool vocab = is_static && q.q_token_ids && c->h_tok;
 				if (vocab) {
 					key_t.assign(q.q_token_ids, q.q_token_ids + q.len_t);
 					key_s.assign(c->h_tok->begin() + t_a, c->h_tok->begin() + t_a + len_s);
 				}
-				raw[(size_t)j] = vk_host::rwmd_from_rows(c->h_brows + (at + j) * 64 * 16, 16, len_s, q.len_t, vocab ? key_s.data() : nullptr, vocab ? key_t.data() : nullptr,
+				const float raw = vk_host::rwmd_from_rows(c->h_brows + (at + j) * 64 * 16, 16, len_s, q.len_t, vocab ? key_s.data() : nullptr, vocab ? key_t.data() : nullptr,
 					q.rwmd_injective != 0, q.rwmd_symmetric != 0, q.rwmd_normalize_bow != 0);
-				val[(size_t)j] = (raw[(size_t)j] / (float)q.len_t) * (q.boost ? q.boost[g] : 1.0f);
-				order.push_back(j);
-			}
-			vk_host::rank_above(order, q.min_score, [&](int j) { return val[(size_t)j]; }, row_at);
-			const int n_out = std::min((int)order.size(), k);
-			for (int r = 0; r < n_out; r++) {
-				const int j = order[(size_t)r];
-				out->score[r] = val[(size_t)j];
-				out->sentence[r] = row_at(j);
-				if (out->raw_score) out->raw_score[r] = raw[(size_t)j];
-				if (out->mapping && out->edge_sim) vk_host::no_flow(out->mapping + (size_t)r * q.len_t, out->edge_sim + (size_t)r * q.len_t, q.len_t);
-				const size_t room = out->rows_per_winner > 0 ? (size_t)out->rows_per_winner : (size_t)VK_FAST_SENT_LEN;   // rows per winner of the caller's array (>= 64)
-				memcpy(out->sim_rows + (size_t)r * room * 16, c->h_brows + (at + j) * 64 * 16, (size_t)64 * 16 * 4);
-			}
-			out->n_out = n_out;
+				return {raw, (raw / (float)q.len_t) * (q.boost ? q.boost[g] : 1.0f)};
+			});
+			vk_host::write_result_set(out, sel, rs, q.len_t, true);
+			const size_t room = out->rows_per_winner > 0 ? (size_t)out->rows_per_winner : (size_t)VK_FAST_SENT_LEN;   // rows per winner of the caller's array (>= 64)
+			for (int r = 0; r < rs.n_out; r++)   // the rows of the winners, in their final order
+				memcpy(out->sim_rows + (size_t)r * room * 16, c->h_brows + (at + (size_t)rs.order[(size_t)r]) * 64 * 16, (size_t)64 * 16 * 4);
 		}
 	};
 	const int n_threads = n_queries >= 64 ? 4 : 1;
@@ -197,13 +187,13 @@ static int query_batch_shared_pass(vk_corpus_t *c, const vk_query_desc *qs, int3
 	const int k = q0.max_matches;
 	const bool is_align = q0.algorithm == VK_ALG_ALIGN;
 	// alignments with traceback: k + 8 slices are selected and restated in the canonical arithmetic, the k best of them returned
-	// (vk_query: the result set is then the oracle's, not only its members' numbers); kk slots per query below
+	// (the result set is then the oracle's, not only its members' numbers: vk_result_host.h); kk slots per query below
 	// relaxed WMD with flows: likewise, restated on the host from the candidates' canonical similarity rows (batch_winner_rows)
 	bool canon_tr = !is_align && q0.want_flow;
 	for (int i = 0; i < n_queries; i++) canon_tr = canon_tr && outs[i].sim_rows != nullptr;
 	const bool margin = (q0.want_flow && is_align) || canon_tr;
-	const int kk = margin ? k + 8 : k;   // (<= 64: checked above)
-	const float sel_floor = margin ? q0.min_score - 1e-5f * std::max(1.0f, std::fabs(q0.min_score)) : q0.min_score;
+	const int kk = margin ? k + vk_host::kCanonMargin : k;   // (<= 64: checked above)
+	const float sel_floor = margin ? vk_host::restated_floor(q0.min_score) : q0.min_score;
 
 	// ---- common options: gap tables, DP form
 	VkScoreBatchParams p{};
@@ -269,6 +259,7 @@ static int query_batch_shared_pass(vk_corpus_t *c, const vk_query_desc *qs, int3
 	std::vector<uint64_t> &keys = keep.vec<uint64_t>((size_t)qb_max * kk);
 	std::vector<float> &raw = keep.vec<float>((size_t)qb_max * kk), &sim = keep.vec<float>((size_t)qb_max * kk * 16);
 	std::vector<int16_t> &map = keep.vec<int16_t>((size_t)qb_max * kk * 16);
+	vk_host::result_set rs;
 	for (int base = 0; base < n_queries; base += qb_max) {
 		const int qb = std::min(qb_max, n_queries - base);
 		// Query::abort (query.h:183-189): polled between the passes; the queries before `base` are complete
@@ -326,36 +317,17 @@ static int query_batch_shared_pass(vk_corpus_t *c, const vk_query_desc *qs, int3
 		for (int i = 0; i < qb && !canon_tr; i++) {   // (relaxed WMD with flows: batch_winner_rows below writes the result sets)
 			const vk_query_desc &q = qs[base + i];
 			vk_topk_out *out = &outs[base + i];
-			// winners of this query: position in the selection, score.  With traceback the score is restated from the canonical
-			// aligner score of the flow kernel (the oracle's, bit for bit) and the winners are put in that order (vk_query).
-			const auto row_at = [&](int j) { return (int64_t)vk_host::key_row(keys[(size_t)i * kk + j]); };
-			std::vector<int> order((size_t)vk_host::count_keys(keys.data() + (size_t)i * kk, kk));
-			std::vector<float> val((size_t)kk, 0.0f);
-			for (int j = 0; j < (int)order.size(); j++) {
-				order[(size_t)j] = j;
-				// (no tag weights in a batch: every matched token counts 1)
-				val[(size_t)j] = !do_flow ? vk_host::key_score(keys[(size_t)i * kk + j])
-					: vk_host::reference_score(raw[(size_t)i * kk + j], &map[((size_t)i * kk + j) * 16], q.len_t, nullptr, (float)q.len_t, 0.0f, q.boost ? q.boost[row_at(j)] : 1.0f);
-			}
-			if (do_flow) vk_host::rank_above(order, q.min_score, [&](int j) { return val[(size_t)j]; }, row_at);
-			int n_out = 0;
-			for (const int j : order) {
-				if (n_out >= k) break;
-				const int64_t g = row_at(j);
-				out->score[n_out] = val[(size_t)j];
-				out->sentence[n_out] = g;
-				if (out->raw_score) {
-					if (do_flow) out->raw_score[n_out] = raw[(size_t)i * kk + j];
-					else VK_HIP(hipMemcpy(&out->raw_score[n_out], c->d_braw + (size_t)i * n + g, 4, hipMemcpyDeviceToHost));
-				}
-				if (q.want_flow && out->mapping && out->edge_sim)
-					for (int t = 0; t < q.len_t; t++) {
-						out->mapping[(size_t)n_out * q.len_t + t] = do_flow ? map[((size_t)i * kk + j) * 16 + t] : (int16_t)-1;
-						out->edge_sim[(size_t)n_out * q.len_t + t] = do_flow ? sim[((size_t)i * kk + j) * 16 + t] : 0.0f;
-					}
-				n_out++;
-			}
-			out->n_out = n_out;
+			// winners of this query.  With traceback the score is restated from the canonical aligner score of the flow kernel (the
+			// oracle's, bit for bit) and the winners are put in that order.  Rows are slices here; 16 columns per traceback.
+			vk_host::selected sel;
+			sel.keys = keys.data() + (size_t)i * kk; sel.cap = kk;
+			if (do_flow) { sel.raw = raw.data() + (size_t)i * kk; sel.map = map.data() + (size_t)i * kk * 16; sel.sim = sim.data() + (size_t)i * kk * 16; sel.stride = 16; }
+			// (no tag weights in a batch: every matched token counts 1)
+			if (do_flow) vk_host::score_selected(sel, rs, q.min_score, k, false, vk_host::by_traceback{sel, q.len_t, nullptr, (float)q.len_t, 0.0f, q.boost});
+			else vk_host::score_selected(sel, rs, q.min_score, k, false);
+			for (int j = 0; j < rs.n_out && !do_flow && out->raw_score; j++)
+				VK_HIP(hipMemcpy(&rs.raw[(size_t)j], c->d_braw + (size_t)i * n + sel.row(j), 4, hipMemcpyDeviceToHost));
+			vk_host::write_result_set(out, sel, rs, q.len_t, q.want_flow != 0);
 		}
 		if (canon_tr && (rc = batch_winner_rows(c, qs + base, qb, outs + base, keys.data(), kk, k, st, keep))) return rc;
 		float ms = 0;
@@ -423,15 +395,12 @@ static int query_batch_span(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_q
 	std::vector<uint8_t> &all = keep.vec<uint8_t>((size_t)chunk_tiles * tb);
 	std::vector<uint64_t> &keys = keep.vec<uint64_t>((size_t)(waves ? chunk : 1) * (size_t)kk);
 	// a query's winners from its kk selected keys, best first: score, slice, and the aligner score -- the score itself without a booster
-	const auto emit = [&](int i, const uint64_t *sel) {
-		vk_topk_out *out = &outs[i];
-		const int n_out = vk_host::count_keys(sel, kk);
-		for (int j = 0; j < n_out; j++) {
-			out->score[j] = vk_host::key_score(sel[j]);
-			out->sentence[j] = (int64_t)vk_host::key_row(sel[j]);
-			if (out->raw_score) out->raw_score[j] = out->score[j];
-		}
-		out->n_out = n_out;
+	vk_host::result_set rs;
+	const auto emit = [&](int i, const uint64_t *keys_i) {
+		vk_host::selected sel;
+		sel.keys = keys_i; sel.cap = kk;
+		vk_host::score_selected(sel, rs, floor, kk, false);
+		vk_host::write_result_set(&outs[i], sel, rs, qs[i].len_t, false);
 	};
 
 	VkSpanBatchParams p{};
@@ -648,8 +617,8 @@ static int query_batch_body(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_q
 	// with flows: k + 8 candidates per query, restated on the host from their canonical rows; the k best are kept (batch_winner_rows)
 	bool canon_tr = qs[0].want_flow != 0;
 	for (int i = 0; i < n_queries; i++) canon_tr = canon_tr && outs[i].sim_rows != nullptr;
-	const int kk = canon_tr ? k + 8 : k;   // (<= 64: checked above)
-	const float sel_floor = canon_tr ? qs[0].min_score - 1e-5f * std::max(1.0f, std::fabs(qs[0].min_score)) : qs[0].min_score;
+	const int kk = canon_tr ? k + vk_host::kCanonMargin : k;   // (<= 64: checked above)
+	const float sel_floor = canon_tr ? vk_host::restated_floor(qs[0].min_score) : qs[0].min_score;
 	const int64_t nw1 = (n + 4095) / 4096;
 	const size_t need_k = (size_t)n_queries * (size_t)nw1 * (size_t)kk;
 	for (auto &b : c->d_bkeys) if ((rc = b.reserve(need_k, &c->device_bytes))) return rc;
@@ -850,21 +819,13 @@ static int query_batch_body(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_q
 	std::vector<uint64_t> &keys = keep.vec<uint64_t>((size_t)n_queries * (size_t)kk);
 	VK_HIP(hipMemcpy2DAsync(keys.data(), (size_t)kk * 8, c->d_bkeys[cur], (size_t)stride * 8, (size_t)kk * 8, (size_t)n_queries, hipMemcpyDeviceToHost, st));
 	VK_HIP(hipStreamSynchronize(st));
+	vk_host::result_set rs;
 	for (int i = 0; i < n_queries && !canon_tr; i++) {   // without flows: the scores of the GEMM pass (kk == k)
-		vk_topk_out *out = &outs[i];
-		int n_out = 0;
-		for (int j = 0; j < k; j++) {
-			const uint64_t key = keys[(size_t)i * k + j];
-			if (key == 0) break;
-			const float s = vk_host::key_score(key);
-			const int64_t g = (int64_t)vk_host::key_row(key);
-			out->score[j] = s;
-			out->sentence[j] = g;
-			if (out->raw_score) out->raw_score[j] = (qs[i].boost ? s / qs[i].boost[g] : s) * (float)qs[i].len_t;
-			if (qs[i].want_flow && out->mapping && out->edge_sim) vk_host::no_flow(out->mapping + (size_t)j * qs[i].len_t, out->edge_sim + (size_t)j * qs[i].len_t, qs[i].len_t);
-			n_out++;
-		}
-		out->n_out = n_out;
+		vk_host::selected sel;
+		sel.keys = keys.data() + (size_t)i * k; sel.cap = k;
+		vk_host::score_selected(sel, rs, qs[i].min_score, k, false);
+		for (int j = 0; j < rs.n_out && outs[i].raw_score; j++) rs.raw[(size_t)j] = vk_host::unboosted_sum(rs.val[(size_t)j], qs[i].boost, sel.row(j), qs[i].len_t);
+		vk_host::write_result_set(&outs[i], sel, rs, qs[i].len_t, qs[i].want_flow != 0);
 	}
 	if (canon_tr && (rc = batch_winner_rows(c, qs, n_queries, outs, keys.data(), kk, k, st, keep, tiles16.empty() ? nullptr : tiles16.data()))) return rc;
 	c->have_scores = false;

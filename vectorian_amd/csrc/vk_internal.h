@@ -516,6 +516,8 @@ int fill_query_tables(vk_corpus *c, const vk_query_desc *q, const uint8_t *d_qti
 	return VK_OK;
 }
 
+// the slice of a row of the slice table as the writer of a result set takes it (vk_host::selected): null where rows are slices
+inline const int32_t *slice_of_row(const vk_corpus *c) { return c->entry_sent.empty() ? nullptr : c->entry_sent.data(); }
 // row of the slice table of a slice (long slices sit in padded groups); the inverse of entry_sent is built when first needed
 int64_t row_of_sentence(vk_corpus *c, int64_t s) {
 	if (c->entry_sent.empty()) return s;

@@ -123,11 +123,10 @@ int vk_longq_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_
 	VK_HIP(hipEventRecord(c->ev[2], st));
 	c->ev2_recorded = true;
 
-	// ---- bounded result set: k + 8 slices selected, all of them retraced canonically, the k best kept (vk_query)
+	// ---- bounded result set: k + kCanonMargin slices selected, all of them retraced canonically, the k best kept (vk_result_host.h)
 	const bool do_flow = q->want_flow != 0;
-	constexpr int kCanonMargin = 8;
-	const int kk = only ? q->n_only : (int)std::min<int64_t>(do_flow ? std::min(k + kCanonMargin, VK_MAX_MATCHES) : k, n);
-	const float sel_floor = do_flow ? q->min_score - 1e-5f * std::max(1.0f, std::fabs(q->min_score)) : q->min_score;
+	const int kk = only ? q->n_only : (int)std::min<int64_t>(do_flow ? std::min(k + vk_host::kCanonMargin, VK_MAX_MATCHES) : k, n);
+	const float sel_floor = do_flow ? vk_host::restated_floor(q->min_score) : q->min_score;
 	const uint64_t *d_sel = c->d_keys[0];   // the selected keys on the device, best first
 	if (only) {
 		std::vector<uint64_t> &hk = keep.vec<uint64_t>((size_t)q->n_only);
@@ -167,40 +166,19 @@ int vk_longq_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_
 		VK_HIP(hipMemcpyAsync(sim.data(), lq.sim, sim.size() * 4, hipMemcpyDeviceToHost, st));
 	}
 	VK_HIP(hipStreamSynchronize(st));
-	const int n_sel = vk_host::count_keys(keys.data(), kk);
-	std::vector<int> order((size_t)n_sel);
-	std::vector<float> val((size_t)std::max(n_sel, 1));
-	for (int i = 0; i < n_sel; i++) {
-		order[(size_t)i] = i;
-		val[(size_t)i] = vk_host::key_score(keys[(size_t)i]);
-	}
-	const auto row_at = [&](int i) { return (int64_t)vk_host::key_row(keys[(size_t)i]); };
-	auto sentence_of = [c](int64_t row) { return c->entry_sent.empty() ? row : (int64_t)c->entry_sent[(size_t)row]; };
-	int n_out = n_sel;
-	if (do_flow) {
-		// the winners' scores from their canonical aligner scores (no submatch weight with such queries)
-		for (int i = 0; i < n_sel; i++)
-			val[(size_t)i] = vk_host::reference_score(raw[(size_t)i], &map[(size_t)i * LTP], LT, q->tag_weights, total, 0.0f, q->boost ? q->boost[sentence_of(row_at(i))] : 1.0f);
-		if (!only) vk_host::rank_above(order, q->min_score, [&](int i) { return val[(size_t)i]; }, row_at);
-		n_out = std::min((int)order.size(), only ? q->n_only : k);
-	} else if (out->raw_score && n_out > 0) {
+	vk_host::selected sel;
+	sel.keys = keys.data(); sel.cap = kk; sel.slice_of_row = slice_of_row(c);
+	if (do_flow) { sel.raw = raw.data(); sel.map = map.data(); sel.sim = sim.data(); sel.stride = LTP; }
+	vk_host::result_set rs;
+	// the winners' scores from their canonical aligner scores (no submatch weight with such queries)
+	if (do_flow) vk_host::score_selected(sel, rs, q->min_score, only ? q->n_only : k, only, vk_host::by_traceback{sel, LT, q->tag_weights, total, 0.0f, q->boost});
+	else if (vk_host::score_selected(sel, rs, q->min_score, kk, only) > 0 && out->raw_score) {
 		std::vector<float> &all_raw = keep.vec<float>((size_t)n);
 		VK_HIP(hipMemcpyAsync(all_raw.data(), c->d_raw, (size_t)n * 4, hipMemcpyDeviceToHost, st));
 		VK_HIP(hipStreamSynchronize(st));
-		for (int i = 0; i < n_out; i++) raw[(size_t)i] = all_raw[(size_t)row_at(i)];
+		for (int i = 0; i < rs.n_out; i++) rs.raw[(size_t)i] = all_raw[(size_t)sel.row(i)];
 	}
-	for (int i = 0; i < n_out; i++) {
-		const int src = order[(size_t)i];
-		out->score[i] = val[(size_t)src];
-		out->sentence[i] = sentence_of(row_at(src));
-		if (out->raw_score) out->raw_score[i] = raw[(size_t)src];
-		if (do_flow)
-			for (int j = 0; j < LT; j++) {
-				out->mapping[(size_t)i * LT + j] = map[(size_t)src * LTP + j];
-				out->edge_sim[(size_t)i * LT + j] = sim[(size_t)src * LTP + j];
-			}
-	}
-	out->n_out = n_out;
+	vk_host::write_result_set(out, sel, rs, LT, do_flow);
 	c->have_scores = !only;
 
 	state_timings(c, true);

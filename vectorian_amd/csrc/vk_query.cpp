@@ -10,7 +10,7 @@
 // The route of a query (vk_route_host.h): the facts it is decided from, copied from the corpus and the query -- one place for
 // vk_validate_query, which refuses a shape before anything is enqueued, and for query_body.  (bound_pass stays false here: the
 // handle's back-off is asked by the query that runs.)
-static constexpr int kCanonMargin = 8;   // runners-up selected with the winners where the host restates the winners' scores
+using vk_host::kCanonMargin;   // runners-up selected with the winners where the host restates the winners' scores
 static const vk_host::route_fits kRouteFits{vk_score32_waves, vk_wide_ring_rows, vk_wide_lds_demand};
 static bool exact_transport(const vk_query_desc *q) { return vk_host::exact_transport(q->algorithm, q->wmd_full != 0); }
 static vk_host::route_facts route_facts_of(const vk_corpus *c, const vk_query_desc *q, const vk_topk_out *out) {
@@ -329,7 +329,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	const bool wide_query = q->len_t > VK_FAST_QUERY_LEN;   // 17 .. 64 tokens
 	const bool xlong = c->max_len > VK_MAX_SENT_LEN;       // whole documents as slices: the one-wave-per-slice family, state in global memory
 	const bool wide_family = r.flow != vk_host::FLOW_NARROW;   // the winners' tracebacks (and some scoring pass) on that family: VkWideParams
-	auto sentence_of = [c](int64_t row) { return c->entry_sent.empty() ? row : (int64_t)c->entry_sent[(size_t)row]; };
+	const int32_t *to_slice = slice_of_row(c);
 	const bool is_static_l = c->desc.layout == VK_LAYOUT_STATIC;
 	// transport algorithms: similarity rows (and, for exact transport, the optimal plan) of the winners, from which
 	// the host states their SparseFlow / DenseFlow.  rows_idx: rows of the slice table, best first.
@@ -471,7 +471,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	// result set are the oracle's floats, whichever kernel ranked the slices (per query, batched GEMM, a shard of the corpus).
 	const bool canon_tr = q->algorithm == VK_ALG_RWMD && !q->wmd_full && q->want_flow && out->sim_rows != nullptr;
 	const int kk = facts.kk;
-	const float sel_floor = (do_flow || canon_tr) ? q->min_score - 1e-5f * std::max(1.0f, std::fabs(q->min_score)) : q->min_score;
+	const float sel_floor = (do_flow || canon_tr) ? vk_host::restated_floor(q->min_score) : q->min_score;
 
 	// ---- the fused scoring kernel ------------------------------------------
 	// handles on one corpus take turns: this scoring kernel starts when the peer's has finished (its selection and
@@ -711,14 +711,14 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		VK_HIP(hipMemcpyAsync(raws.data(), c->d_wrd_raw, (size_t)cnt * 4, hipMemcpyDeviceToHost, st));
 		VK_HIP(hipStreamSynchronize(st));
 		if ((rc = transport_flows(rows_idx, true, w.qmass, w.mass_mode, w.raw_masses))) return rc;
-		for (int i = 0; i < cnt; i++) {
+		vk_host::selected sel;
+		sel.keys = hk.data(); sel.cap = cnt; sel.slice_of_row = to_slice;
+		vk_host::result_set rs;
+		vk_host::score_selected(sel, rs, q->min_score, cnt, true, [&](int i) {   // (an empty slice: no solver took it)
 			const bool empty = (*c->h_end)[(size_t)rows_idx[(size_t)i]] - (*c->h_start)[(size_t)rows_idx[(size_t)i]] < 1;
-			out->score[i] = empty ? -INFINITY : vals[(size_t)i];
-			out->sentence[i] = q->only_slices[i];
-			if (out->raw_score) out->raw_score[i] = empty ? -INFINITY : raws[(size_t)i];
-			if (out->mapping && out->edge_sim) vk_host::no_flow(out->mapping + i * (size_t)q->len_t, out->edge_sim + i * (size_t)q->len_t, q->len_t);
-		}
-		out->n_out = cnt;
+			return empty ? std::make_pair(-INFINITY, -INFINITY) : std::make_pair(raws[(size_t)i], vals[(size_t)i]);
+		});
+		vk_host::write_result_set(out, sel, rs, q->len_t, true);
 		return VK_OK;
 	}
 	if (exact_transport(q)) {
@@ -736,8 +736,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		if ((rc = c->d_wrd_raw.reserve(cap, &c->device_bytes))) return rc;
 		if ((rc = c->d_wrd_val.reserve(cap, &c->device_bytes))) return rc;
 		if ((rc = c->d_counter.reserve(4, &c->device_bytes))) return rc;
-		struct Cand { float val, raw; int64_t g; };
-		std::vector<Cand> best;
+		std::vector<vk_host::candidate> best, round;
 		std::vector<uint64_t> &keys = keep.vec<uint64_t>();
 		std::vector<float> &vals = keep.vec<float>(), &raws = keep.vec<float>();
 		VkWrdParams w{};
@@ -759,14 +758,9 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 			float ub = INFINITY;
 			for (int i = 0; i < n_cand; i++) {
 				ub = std::min(ub, vk_host::key_score(keys[(size_t)i]));
-				if (vals[(size_t)i] > q->min_score)
-					best.push_back({vals[(size_t)i], raws[(size_t)i], (int64_t)vk_host::key_row(keys[(size_t)i])});
+				round.push_back({vals[(size_t)i], raws[(size_t)i], (int64_t)vk_host::key_row(keys[(size_t)i]), {}, {}});
 			}
-			const auto better = [](const Cand &a, const Cand &b) { return vk_host::ranks_before(a.val, a.g, b.val, b.g); };
-			if ((int)best.size() > k) {
-				std::partial_sort(best.begin(), best.begin() + k, best.end(), better);
-				best.resize((size_t)k);
-			} else std::sort(best.begin(), best.end(), better);
+			vk_host::keep_best(best, round, q->min_score, k);
 			*ub_min = ub;
 			*n_cand_out = n_cand;
 			return VK_OK;
@@ -794,18 +788,12 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		VK_HIP(hipEventRecord(c->ev[3], st));
 		{
 			std::vector<int64_t> rows_idx;
-			for (const Cand &b : best) rows_idx.push_back(b.g);
+			for (const vk_host::candidate &b : best) rows_idx.push_back(b.row);
 			if ((rc = transport_flows(rows_idx, true, w.qmass, w.mass_mode, w.raw_masses))) return rc;
 		}
 		VK_HIP(hipEventRecord(c->ev[4], st));
 		VK_HIP(hipStreamSynchronize(st));
-		for (size_t i = 0; i < best.size(); i++) {
-			out->score[i] = best[i].val;
-			out->sentence[i] = sentence_of(best[i].g);
-			if (out->raw_score) out->raw_score[i] = best[i].raw;
-			if (q->want_flow && out->mapping && out->edge_sim) vk_host::no_flow(out->mapping + i * (size_t)q->len_t, out->edge_sim + i * (size_t)q->len_t, q->len_t);
-		}
-		out->n_out = (int)best.size();
+		vk_host::write_best(out, best, to_slice, q->len_t, q->want_flow != 0);
 		state_timings(c, false);
 		return VK_OK;
 	}
@@ -867,11 +855,13 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		const float m_star = total * (1.0f - powf(1.0f / (wsub + 1.0f), 1.0f / wsub));
 		VK_HIP(vk_launch_submatch_bound(c->d_raw, p.boost, n, total, wsub, m_star, c->d_scores, st));
 		const int M = 512;
-		struct Cand { float val, raw; int64_t row; std::vector<int16_t> map; std::vector<float> sim; };
-		std::vector<Cand> best;
+		std::vector<vk_host::candidate> best, round;
 		std::vector<uint64_t> &keys = keep.vec<uint64_t>((size_t)M);
 		std::vector<float> &raws = keep.vec<float>((size_t)M), &sims = keep.vec<float>((size_t)M * ostride);
 		std::vector<int16_t> &maps = keep.vec<int16_t>((size_t)M * ostride);
+		vk_host::selected cand;
+		cand.keys = keys.data(); cand.cap = M; cand.raw = raws.data(); cand.map = maps.data(); cand.sim = sims.data(); cand.stride = ostride; cand.slice_of_row = to_slice;
+		vk_host::result_set scored;
 		for (;;) {
 			const uint64_t *d_cand = nullptr;
 			if ((rc = select_blocks(c, q->min_score, M, st, &d_cand))) return rc;
@@ -882,41 +872,24 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 			VK_HIP(hipMemcpyAsync(maps.data(), c->d_out_map, maps.size() * 2, hipMemcpyDeviceToHost, st));
 			VK_HIP(hipMemcpyAsync(sims.data(), c->d_out_sim, sims.size() * 4, hipMemcpyDeviceToHost, st));
 			VK_HIP(hipStreamSynchronize(st));
-			const int n_cand = vk_host::count_keys(keys.data(), M);
-			float ub_last = INFINITY;
-			for (int i = 0; i < n_cand; i++) {
-				ub_last = vk_host::key_score(keys[(size_t)i]);
-				const int64_t row = (int64_t)vk_host::key_row(keys[(size_t)i]);
-				const float val = vk_host::reference_score(raws[(size_t)i], &maps[(size_t)i * ostride], q->len_t, q->tag_weights, total, wsub, q->boost ? q->boost[sentence_of(row)] : 1.0f);
-				if (val > q->min_score) {
-					Cand cd{val, raws[(size_t)i], row, {}, {}};
-					cd.map.assign(maps.begin() + (size_t)i * ostride, maps.begin() + (size_t)i * ostride + q->len_t);
-					cd.sim.assign(sims.begin() + (size_t)i * ostride, sims.begin() + (size_t)i * ostride + q->len_t);
-					best.push_back(std::move(cd));
-				}
-			}
-			std::sort(best.begin(), best.end(), [](const Cand &a, const Cand &b) { return vk_host::ranks_before(a.val, a.row, b.val, b.row); });
-			if ((int)best.size() > k) best.resize((size_t)k);
+			// the round's candidates above min_score, with their tracebacks (the next round overwrites the buffers they came back in)
+			vk_host::score_selected(cand, scored, q->min_score, M, false, vk_host::by_traceback{cand, q->len_t, q->tag_weights, total, wsub, q->boost});
+			const int n_cand = (int)scored.val.size();
+			const float ub_last = n_cand > 0 ? vk_host::key_score(keys[(size_t)n_cand - 1]) : INFINITY;   // the smallest bound among them
+			for (const int i : scored.order)
+				round.push_back({scored.val[(size_t)i], scored.raw[(size_t)i], cand.row(i), {maps.begin() + (size_t)i * ostride, maps.begin() + (size_t)i * ostride + q->len_t},
+					{sims.begin() + (size_t)i * ostride, sims.begin() + (size_t)i * ostride + q->len_t}});
+			vk_host::keep_best(best, round, q->min_score, k);
 			if (n_cand < M) break;
 			if ((int)best.size() == k && best.back().val > ub_last) break;
 		}
 		VK_HIP(hipEventRecord(c->ev[3], st));
 		VK_HIP(hipEventRecord(c->ev[4], st));
 		VK_HIP(hipStreamSynchronize(st));
-		for (size_t i = 0; i < best.size(); i++) {
-			out->score[i] = best[i].val;
-			out->sentence[i] = sentence_of(best[i].row);
-			if (out->raw_score) out->raw_score[i] = best[i].raw;
-			if (q->want_flow && out->mapping && out->edge_sim)
-				for (int j = 0; j < q->len_t; j++) {
-					out->mapping[i * (size_t)q->len_t + j] = best[i].map[(size_t)j];
-					out->edge_sim[i * (size_t)q->len_t + j] = best[i].sim[(size_t)j];
-				}
-		}
-		out->n_out = (int)best.size();
+		vk_host::write_best(out, best, to_slice, q->len_t, q->want_flow != 0);
 		if (out->sim_rows && !best.empty()) {   // similarity rows of the winners on request (debug hook)
 			std::vector<int64_t> rows_idx;
-			for (const Cand &b : best) rows_idx.push_back(b.row);
+			for (const vk_host::candidate &b : best) rows_idx.push_back(b.row);
 			float no_mass[VK_MAX_QUERY_LEN] = {0};
 			if ((rc = transport_flows(rows_idx, false, no_mass, 0, 0))) return rc;
 		}
@@ -975,26 +948,29 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	}
 	VK_HIP(hipStreamSynchronize(st));
 
-	const int n_sel = vk_host::count_keys(keys.data(), kk);
-	// order[i]: position among the selected slices of the i-th result
-	std::vector<int> order((size_t)n_sel);
-	std::vector<float> val((size_t)std::max(n_sel, 1));
-	for (int i = 0; i < n_sel; i++) {
-		order[(size_t)i] = i;
-		val[(size_t)i] = vk_host::key_score(keys[(size_t)i]);
-	}
-	const auto row_at = [&](int i) { return (int64_t)vk_host::key_row(keys[(size_t)i]); };
-	const auto rank_restated = [&]() {   // the k best of the restated scores, in the order of a result set (listed slices keep the caller's order)
-		if (!only) vk_host::rank_above(order, q->min_score, [&](int i) { return val[(size_t)i]; }, row_at);
-		return std::min((int)order.size(), only ? q->n_only : k);
-	};
-	int n_out = n_sel;
-	if (do_flow) {
-		// the winners' scores from their canonical aligner scores (searches with a submatch weight take the candidate rounds above)
-		for (int i = 0; i < n_sel; i++)
-			val[(size_t)i] = vk_host::reference_score(raw[(size_t)i], &map[(size_t)i * ostride], q->len_t, q->tag_weights, p.ref_total,
-				only ? q->submatch_weight : 0.0f, q->boost ? q->boost[sentence_of(row_at(i))] : 1.0f);
-		n_out = rank_restated();
+	vk_host::selected sel;
+	sel.keys = keys.data(); sel.cap = kk; sel.slice_of_row = to_slice;
+	if (do_flow) { sel.raw = raw.data(); sel.map = map.data(); sel.sim = sim.data(); sel.stride = ostride; }
+	const int n_sel = vk_host::count_keys(keys.data(), kk), limit = only ? q->n_only : k;   // (n_sel: the rows below are fetched before anything is scored)
+	vk_host::result_set rs;
+	// the winners' scores from their canonical aligner scores (searches with a submatch weight take the candidate rounds above)
+	if (do_flow) vk_host::score_selected(sel, rs, q->min_score, limit, only, vk_host::by_traceback{sel, q->len_t, q->tag_weights, p.ref_total, only ? q->submatch_weight : 0.0f, q->boost});
+	else if (!(canon_tr && n_sel > 0)) {
+		if (out->raw_score && n_sel > 0) {
+			// the aligner scores of the winners from the scoring pass's array (a large result set: the whole array in one copy, gathered here);
+			// the span pass that wrote none: the score itself
+			if (n_sel > 256 && !r.span_skip_raw) {
+				std::vector<float> &all_raw = keep.vec<float>((size_t)n);
+				VK_HIP(hipMemcpyAsync(all_raw.data(), c->d_raw, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+				VK_HIP(hipStreamSynchronize(st));
+				for (int i = 0; i < n_sel; i++) raw[(size_t)i] = all_raw[(size_t)sel.row(i)];
+			} else for (int i = 0; i < n_sel; i++) {
+				if (!r.span_skip_raw) VK_HIP(hipMemcpyAsync(&raw[(size_t)i], c->d_raw + sel.row(i), 4, hipMemcpyDeviceToHost, st));
+			}
+			VK_HIP(hipStreamSynchronize(st));
+			if (!r.span_skip_raw) sel.raw = raw.data();
+		}
+		vk_host::score_selected(sel, rs, q->min_score, kk, only);
 	}
 	// canon_tr: similarity rows of every selected slice -- in the handle's pinned staging (a std::vector made the copy of a document
 	// corpus's winners, 12 MB for 18 x 5,056 rows x 32 columns, go through the runtime's bounce buffers: 2 - 4 ms of a 5.7 ms query)
@@ -1005,7 +981,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		if ((rc = c->h_brows.reserve(rows_bytes / 4, nullptr))) return rc;
 		rows_all = c->h_brows;
 		std::vector<int64_t> rows_idx;
-		for (int i = 0; i < n_sel; i++) rows_idx.push_back(row_at(i));
+		for (int i = 0; i < n_sel; i++) rows_idx.push_back(sel.row(i));
 		float no_mass[VK_MAX_QUERY_LEN] = {0};
 		if ((rc = transport_flows(rows_idx, false, no_mass, 0, 0, rows_all))) return rc;
 		// vocabulary keys (static layout): token ids, or (id, tag) pairs when the similarity is tag-weighted (alignment/bow.h:106-127, 150-176)
@@ -1014,62 +990,37 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		std::vector<int32_t> key_t((size_t)q->len_t), key_s;
 		for (int j = 0; vocab && j < q->len_t; j++) key_t[(size_t)j] = tagged ? q->q_token_ids[j] * 256 + (int32_t)(uint8_t)q->q_tags[j] : q->q_token_ids[j];
 		const float total = ref_total_of(q);
-		for (int i = 0; i < n_sel; i++) {
-			const int64_t row = rows_idx[(size_t)i];
-			const int32_t t_a = (*c->h_start)[(size_t)row], len_s = (*c->h_end)[(size_t)row] - t_a;
-			const float boost = q->boost ? q->boost[sentence_of(row)] : 1.0f;
-			if (len_s < 1 || len_s > rows_R) {   // no rows for this one (longer than the caller's room): it keeps the scoring pass's value
-				if (only) { raw[(size_t)i] = val[(size_t)i] = len_s < 1 ? -INFINITY : NAN; continue; }   // (no scoring pass ran: an empty slice has no score, a longer one cannot be stated)
-				VK_HIP(hipMemcpy(&raw[(size_t)i], c->d_raw + row, 4, hipMemcpyDeviceToHost));
-				continue;
+		// no rows for a slice that is empty or longer than the caller's room: it keeps the scoring pass's values (listed: no scoring pass
+		// ran -- an empty slice has no score, a longer one cannot be stated)
+		const auto len_of = [&](int i) { return (*c->h_end)[(size_t)rows_idx[(size_t)i]] - (*c->h_start)[(size_t)rows_idx[(size_t)i]]; };
+		for (int i = 0; i < n_sel && !only; i++)
+			if (len_of(i) < 1 || len_of(i) > rows_R) VK_HIP(hipMemcpy(&raw[(size_t)i], c->d_raw + rows_idx[(size_t)i], 4, hipMemcpyDeviceToHost));
+		vk_host::score_selected(sel, rs, q->min_score, limit, only, [&](int i) -> std::pair<float, float> {
+			const int32_t t_a = (*c->h_start)[(size_t)rows_idx[(size_t)i]], len_s = len_of(i);
+			if (len_s < 1 || len_s > rows_R) {
+				const float none = len_s < 1 ? -INFINITY : NAN;
+				return only ? std::make_pair(none, none) : std::make_pair(raw[(size_t)i], vk_host::key_score(keys[(size_t)i]));
 			}
 			if (vocab) {
 				key_s.resize((size_t)len_s);
 				for (int u = 0; u < len_s; u++)
 					key_s[(size_t)u] = tagged ? (*c->h_tok)[(size_t)(t_a + u)] * 256 + (int32_t)(uint8_t)(*c->h_tag)[(size_t)(t_a + u)] : (*c->h_tok)[(size_t)(t_a + u)];
 			}
-			raw[(size_t)i] = vk_host::rwmd_from_rows(rows_all + (size_t)i * rows_R * rows_W, rows_W, len_s, q->len_t,
+			const float raw_i = vk_host::rwmd_from_rows(rows_all + (size_t)i * rows_R * rows_W, rows_W, len_s, q->len_t,
 				vocab ? key_s.data() : nullptr, vocab ? key_t.data() : nullptr, q->rwmd_injective != 0, q->rwmd_symmetric != 0, q->rwmd_normalize_bow != 0);
-			val[(size_t)i] = (raw[(size_t)i] / total) * boost;   // reference_score with every query token matched: the sum of the weights (match.h:165-176)
-		}
-		n_out = rank_restated();
+			// reference_score with every query token matched: the sum of the weights (match.h:165-176)
+			return {raw_i, (raw_i / total) * (q->boost ? q->boost[sel.slice(i)] : 1.0f)};
+		});
 	}
-	std::vector<float> &raw_sel = keep.vec<float>((size_t)std::max(n_out, 1));
-	if (!do_flow && !(canon_tr && n_sel > 0) && out->raw_score && n_out > 0) {
-		// gather the aligner scores of the winners (a large result set: the whole array in one copy, gathered here)
-		if (n_out > 256 && !r.span_skip_raw) {
-			std::vector<float> &all_raw = keep.vec<float>((size_t)n);
-			VK_HIP(hipMemcpyAsync(all_raw.data(), c->d_raw, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-			VK_HIP(hipStreamSynchronize(st));
-			for (int i = 0; i < n_out; i++) raw_sel[(size_t)i] = all_raw[(size_t)row_at(i)];
-		} else for (int i = 0; i < n_out; i++) {
-			if (!r.span_skip_raw) VK_HIP(hipMemcpyAsync(&raw_sel[(size_t)i], c->d_raw + row_at(i), 4, hipMemcpyDeviceToHost, st));
-		}
-		VK_HIP(hipStreamSynchronize(st));
-	}
-	for (int i = 0; i < n_out; i++) {
-		const int src = order[(size_t)i];
-		const float s = val[(size_t)src];
-		out->score[i] = s;
-		out->sentence[i] = sentence_of(row_at(src));
-		if (out->raw_score) out->raw_score[i] = (do_flow || canon_tr) ? raw[(size_t)src] : r.span_skip_raw ? s : raw_sel[(size_t)i];
-		if (do_flow) {
-			for (int j = 0; j < q->len_t; j++) {
-				out->mapping[(size_t)i * q->len_t + j] = map[(size_t)src * ostride + j];
-				out->edge_sim[(size_t)i * q->len_t + j] = sim[(size_t)src * ostride + j];
-			}
-		} else if (q->want_flow && out->mapping && out->edge_sim) {
-			vk_host::no_flow(out->mapping + (size_t)i * q->len_t, out->edge_sim + (size_t)i * q->len_t, q->len_t);
-		}
-	}
-	out->n_out = n_out;
+	const int n_out = rs.n_out;
+	vk_host::write_result_set(out, sel, rs, q->len_t, q->want_flow != 0);
 	c->have_scores = !only;
 	if (canon_tr && n_out > 0) {
 		for (int i = 0; i < n_out; i++)   // the rows of the winners, in their final order
-			memcpy(out->sim_rows + (size_t)i * rows_R * rows_W, rows_all + (size_t)order[(size_t)i] * rows_R * rows_W, (size_t)rows_R * rows_W * 4);
+			memcpy(out->sim_rows + (size_t)i * rows_R * rows_W, rows_all + (size_t)rs.order[(size_t)i] * rows_R * rows_W, (size_t)rows_R * rows_W * 4);
 	} else if ((q->algorithm == VK_ALG_RWMD || (is_align && rows_on_request)) && n_out > 0) {
 		std::vector<int64_t> rows_idx;
-		for (int i = 0; i < n_out; i++) rows_idx.push_back(row_at(order[(size_t)i]));
+		for (int i = 0; i < n_out; i++) rows_idx.push_back(sel.row(rs.order[(size_t)i]));
 		float no_mass[VK_MAX_QUERY_LEN] = {0};
 		if ((rc = transport_flows(rows_idx, false, no_mass, 0, 0))) return rc;
 	}
@@ -1105,17 +1056,14 @@ int vk_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out) {
 		out_flow.mapping = own_map.data(); out_flow.edge_sim = own_sim.data();
 		restate = vk_validate_query(c, &q_flow, &out_flow) == VK_OK;   // (a result set too large to retrace stays on the scoring pass's scores)
 	}
-	if (restate) {
-		const int rc2 = vk_run_guarded([&](vk_host_keep &keep) { return query_body(c, &q_flow, &out_flow, keep); },
-			[&]() { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream); },
-			[](const char *what) { return fail(VK_ERR_INVALID, std::string("vk_query: ") + what); });
-		out->n_out = out_flow.n_out;
-		return rc2;
-	}
+	const vk_query_desc *q_run = restate ? &q_flow : q;
+	vk_topk_out *out_run = restate ? &out_flow : out;
 	// an error inside the body leaves no copy in flight behind: the stream is drained before the body's host buffers die
-	return vk_run_guarded([&](vk_host_keep &keep) { return query_body(c, q, out, keep); },
+	const int rc2 = vk_run_guarded([&](vk_host_keep &keep) { return query_body(c, q_run, out_run, keep); },
 		[&]() { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream); },
 		[](const char *what) { return fail(VK_ERR_INVALID, std::string("vk_query: ") + what); });
+	if (restate) out->n_out = out_flow.n_out;
+	return rc2;
 }
 
 int vk_merge_topk(const vk_topk_out *sets, int32_t n_sets, int32_t len_t, int32_t max_matches, vk_topk_out *out) {
@@ -1132,13 +1080,8 @@ int vk_merge_topk(const vk_topk_out *sets, int32_t n_sets, int32_t len_t, int32_
 	for (int i = 0; i < n_out; i++) {
 		const Ref &r = all[(size_t)i];
 		const vk_topk_out &src = sets[r.set];
-		out->score[i] = r.score;
-		out->sentence[i] = r.sent;
-		if (out->raw_score) out->raw_score[i] = src.raw_score ? src.raw_score[r.idx] : 0.0f;
-		if (out->mapping && src.mapping)
-			memcpy(out->mapping + (size_t)i * len_t, src.mapping + (size_t)r.idx * len_t, (size_t)len_t * 2);
-		if (out->edge_sim && src.edge_sim)
-			memcpy(out->edge_sim + (size_t)i * len_t, src.edge_sim + (size_t)r.idx * len_t, (size_t)len_t * 4);
+		vk_host::write_winner(out, i, len_t, r.score, r.sent, src.raw_score ? src.raw_score[r.idx] : 0.0f, nullptr, nullptr, false);
+		vk_host::merge_rows(out, i, len_t, src.mapping ? src.mapping + (size_t)r.idx * len_t : nullptr, src.edge_sim ? src.edge_sim + (size_t)r.idx * len_t : nullptr);
 	}
 	out->n_out = n_out;
 	return VK_OK;
@@ -1203,11 +1146,10 @@ int vk_merge_records(const int32_t *records, int32_t n_sets, int32_t len_t, int3
 	const int n_out = (int)std::min<size_t>(all.size(), (size_t)k);
 	for (int i = 0; i < n_out; i++) {
 		const int32_t *r = all[(size_t)i].rec;
-		out->score[i] = all[(size_t)i].score;
-		out->sentence[i] = all[(size_t)i].sent;
-		if (out->raw_score) memcpy(out->raw_score + i, r + 2, 4);
-		if (out->mapping) memcpy(out->mapping + (size_t)i * len_t, r + 5, (size_t)len_t * 2);
-		if (out->edge_sim) memcpy(out->edge_sim + (size_t)i * len_t, r + 5 + w / 2, (size_t)len_t * 4);
+		float raw;
+		memcpy(&raw, r + 2, 4);
+		vk_host::write_winner(out, i, len_t, all[(size_t)i].score, all[(size_t)i].sent, raw, nullptr, nullptr, false);
+		vk_host::merge_rows(out, i, len_t, (const int16_t *)(r + 5), (const float *)(r + 5 + w / 2));
 	}
 	out->n_out = n_out;
 	return VK_OK;

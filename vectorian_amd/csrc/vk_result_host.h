@@ -1,6 +1,7 @@
 // vk_result_host.h -- from "the selected keys and their tracebacks" to a result set: the host-side rules every query path shares
 // (vk_query.cpp, vk_batch.cpp, vk_longq_host.cpp).  One definition each of the selection keys' encoding, the order of a result set,
-// the score of a winner restated from its traceback, and the forms of the gap costs the kernels are launched with.
+// the score of a winner restated from its traceback, the writer of a result set (the one place where the fields of a vk_topk_out are
+// assigned), and the forms of the gap costs the kernels are launched with.
 // Host only, no HIP types: tests/test_result_host.py compiles it with g++ and holds each rule against its statement in numpy (CPU tier).
 #ifndef VK_RESULT_HOST_H
 #define VK_RESULT_HOST_H
@@ -12,6 +13,9 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <tuple>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace vk_host {
@@ -70,6 +74,117 @@ inline void no_flow(int16_t *map_row, float *sim_row, int len_t) {
 		sim_row[j] = 0.0f;
 	}
 }
+
+// ---- where the host restates the winners' scores: this many runners-up are selected with them, above a floor lowered by the
+// rounding slack of the scoring pass; the k best restated scores above min_score itself are kept
+constexpr int kCanonMargin = 8;
+inline float restated_floor(float min_score) { return min_score - 1e-5f * std::max(1.0f, std::fabs(min_score)); }
+
+// ---- the writer of a result set.  Every query path ends here: score_selected, then write_result_set; the candidate rounds (exact
+// transports, submatch weight) keep_best, then write_best.  Callers: query_body's four exits, vk_merge_topk and vk_merge_records
+// (vk_query.cpp); vk_longq_query (vk_longq_host.cpp); batch_winner_rows, query_batch_shared_pass, query_batch_span and the GEMM
+// path of query_batch_body (vk_batch.cpp).
+// What came back from the device for one query: `cap` key slots, best first (up to the first empty one); the aligner scores where
+// the path has them; where the winners were retraced, the rows of their mappings and edge similarities, `stride` elements apart.
+// slice_of_row: the slice of a row of the slice table; null where rows are slices.
+struct selected {
+	const uint64_t *keys = nullptr;
+	int cap = 0;
+	const float *raw = nullptr;
+	const int16_t *map = nullptr;
+	const float *sim = nullptr;
+	int stride = 0;
+	const int32_t *slice_of_row = nullptr;
+	int64_t row(int i) const { return (int64_t)key_row(keys[i]); }
+	int64_t slice(int i) const { return slice_of_row ? (int64_t)slice_of_row[row(i)] : row(i); }
+};
+// a result set in the making: val / raw by position among the selected keys, order[i] the position of the i-th result (kept by the
+// caller from query to query: no allocation per query on the batched paths)
+struct result_set {
+	std::vector<int> order;
+	std::vector<float> val, raw;
+	int n_out = 0;
+};
+// how score_selected restates position i: a callable returning (raw, score).  as_selected: not at all, the keys' scores in the keys'
+// order (raw: the traceback's where there is one, else the score, for the caller to replace where the path states another).
+// by_traceback: reference_score of the position's own traceback; boost by slice, null = none.
+struct as_selected {};
+struct by_traceback {
+	const selected &v;
+	int len_t;
+	const float *tag_weights;
+	float total, submatch_weight;
+	const float *boost;
+	std::pair<float, float> operator()(int i) const {
+		return {v.raw[i], reference_score(v.raw[i], v.map + (size_t)i * v.stride, len_t, tag_weights, total, submatch_weight, boost ? boost[v.slice(i)] : 1.0f)};
+	}
+};
+// The scores of the selected slices and how many of them are results: restated scores are ranked (rank_above: those not above
+// min_score leave; ties by row, which orders as the slice does) unless the slices are `listed`, which keep the caller's order and
+// ignore min_score; at most `limit` (k, or the number listed) are results.
+template <typename Restate = as_selected>
+int score_selected(const selected &v, result_set &rs, float min_score, int limit, bool listed, Restate restate = {}) {
+	const int n_sel = count_keys(v.keys, v.cap);
+	rs.order.resize((size_t)n_sel); rs.val.resize((size_t)n_sel); rs.raw.resize((size_t)n_sel);
+	for (int i = 0; i < n_sel; i++) {
+		rs.order[(size_t)i] = i;
+		rs.val[(size_t)i] = key_score(v.keys[i]);
+		rs.raw[(size_t)i] = v.raw ? v.raw[i] : rs.val[(size_t)i];
+	}
+	if constexpr (!std::is_same<Restate, as_selected>::value) {
+		for (int i = 0; i < n_sel; i++) std::tie(rs.raw[(size_t)i], rs.val[(size_t)i]) = restate(i);
+		if (!listed) rank_above(rs.order, min_score, [&](int i) { return rs.val[(size_t)i]; }, [&](int i) { return v.row(i); });
+	}
+	return rs.n_out = std::min((int)rs.order.size(), limit);
+}
+// Winner i of a result set: score, slice, the aligner score if the caller has an array for it.  Flows only where the caller asked
+// for them (`flows`) and has both arrays: the len_t entries of the mapping and the edge similarities from the winner's rows, or,
+// where the path states none (no rows), no_flow.  Nothing else is touched.
+inline void write_winner(vk_topk_out *out, int i, int len_t, float score, int64_t slice, float raw, const int16_t *map_row, const float *sim_row, bool flows) {
+	out->score[i] = score;
+	out->sentence[i] = slice;
+	if (out->raw_score) out->raw_score[i] = raw;
+	if (!(flows && out->mapping && out->edge_sim)) return;
+	if (!map_row) return no_flow(out->mapping + (size_t)i * len_t, out->edge_sim + (size_t)i * len_t, len_t);
+	memcpy(out->mapping + (size_t)i * len_t, map_row, (size_t)len_t * sizeof(int16_t));
+	memcpy(out->edge_sim + (size_t)i * len_t, sim_row, (size_t)len_t * sizeof(float));
+}
+// the merges of result sets (vk_merge_topk, vk_merge_records) carry along whichever rows source and destination both have
+inline void merge_rows(vk_topk_out *out, int i, int len_t, const int16_t *map_row, const float *sim_row) {
+	if (map_row && out->mapping) memcpy(out->mapping + (size_t)i * len_t, map_row, (size_t)len_t * sizeof(int16_t));
+	if (sim_row && out->edge_sim) memcpy(out->edge_sim + (size_t)i * len_t, sim_row, (size_t)len_t * sizeof(float));
+}
+inline void write_result_set(vk_topk_out *out, const selected &v, const result_set &rs, int len_t, bool flows) {
+	for (int i = 0; i < rs.n_out; i++) {
+		const int src = rs.order[(size_t)i];
+		write_winner(out, i, len_t, rs.val[(size_t)src], v.slice(src), rs.raw[(size_t)src], v.map ? v.map + (size_t)src * v.stride : nullptr,
+			v.sim ? v.sim + (size_t)src * v.stride : nullptr, flows);
+	}
+	out->n_out = rs.n_out;
+}
+// The candidate rounds: a round's candidates above min_score join the best so far, which stay in the order of a result set, k at most
+// (a candidate that leaves takes its traceback with it).  map / sim: the traceback of a candidate scored from it; empty for the
+// transports.  When to stop is the caller's rule.
+struct candidate { float val, raw; int64_t row; std::vector<int16_t> map; std::vector<float> sim; };
+inline void keep_best(std::vector<candidate> &best, std::vector<candidate> &round, float min_score, int k) {
+	for (candidate &cd : round)
+		if (cd.val > min_score) best.push_back(std::move(cd));
+	round.clear();
+	const auto better = [](const candidate &a, const candidate &b) { return ranks_before(a.val, a.row, b.val, b.row); };
+	if ((int)best.size() > k) {
+		std::partial_sort(best.begin(), best.begin() + k, best.end(), better);
+		best.resize((size_t)k);
+	} else std::sort(best.begin(), best.end(), better);
+}
+inline void write_best(vk_topk_out *out, const std::vector<candidate> &best, const int32_t *slice_of_row, int len_t, bool flows) {
+	for (size_t i = 0; i < best.size(); i++) {
+		const candidate &b = best[i];
+		write_winner(out, (int)i, len_t, b.val, slice_of_row ? (int64_t)slice_of_row[b.row] : b.row, b.raw, b.map.empty() ? nullptr : b.map.data(), b.sim.data(), flows);
+	}
+	out->n_out = (int)best.size();
+}
+// the aligner score behind a score of the batched relaxed-WMD pass: the boost taken out, the mean over the query's tokens undone
+inline float unboosted_sum(float score, const float *boost, int64_t slice, int len_t) { return (boost ? score / boost[slice] : score) * (float)len_t; }
 
 // ---- gap costs
 inline float gap_cost(const vk_gap &g, int k) {
