@@ -304,6 +304,29 @@ int vk_corpus_set_sim_ops(vk_corpus_t *c, const int32_t *kinds, const float *arg
  * of the rows (they are gone by then).  VK_SIMSRC_COSINE is accepted at any time. */
 enum { VK_SIMSRC_COSINE = 0, VK_SIMSRC_PNORM = 1, VK_SIMSRC_SQRT_COSINE = 2 };
 int vk_corpus_set_sim_source(vk_corpus_t *c, int32_t kind, float arg);
+/* The span similarity: declares a VK_LAYOUT_CONTEXTUAL handle of one-row slices (the span-embedding index: one vector per sentence
+ * or window) to be a span corpus under the VectorSim (source, chain) -- what EmbeddedSpanSim(embedding, sim) hands to
+ * SpanEncoderIndex._find (vectorian/index.py:679-730).  The score of span i for a query row q is ops(src(span_i, q)) as one float32,
+ * UNCLIPPED (the reference has no clip here: a bare VK_SIMSRC_PNORM ranks the farthest span first, as upstream does):
+ *   src_kind / src_arg as vk_corpus_set_sim_source: VK_SIMSRC_PNORM and VK_SIMSRC_SQRT_COSINE run on the UNMODIFIED fp32 rows of both
+ *     sides (the cell: csrc/vk_sim_src_host.h; q_vectors as given, q_normalize keeps its meaning for the cosine tile only);
+ *     VK_SIMSRC_COSINE is the unclipped sum of the matrix-pipe chain on the unit tiles -- the float the plain handle clips;
+ *   op_kinds / op_args / n_ops as vk_corpus_set_sim_ops, applied to the source's value (csrc/vk_sim_ops_host.h).
+ * Admission is score > max(min_score, 0): NaN (a span row of NaN under a p-norm) and negative values are never matches, and a value
+ * of exactly 0 is dropped where the reference keeps it (as the plain span handle does under min_score = 0).  The order of a result
+ * set is that of every other (score, then row).  (VK_SIMSRC_COSINE, n_ops = 0) is the handle as it always was.
+ * A source that is not the cosine keeps a second, fp32 copy of the rows (ceil(d / 16) KiB per 16 spans, counted by
+ * vk_corpus_device_bytes) which vk_corpus_append_vectors and vk_corpus_append_pooled fill: such a call comes BEFORE the first append.
+ * Once the copy exists -- and for a cosine source always, before or after vk_corpus_finalize -- the similarity may be changed at any
+ * time.  Views inherit the similarity and share the copy.
+ * Every query on such a handle is span-shaped: one query token, VK_ALG_ALIGN, VK_LOCAL, no tag or submatch weights, no boost, no
+ * want_flow, no only_slices, no sim_rows; anything else returns VK_ERR_UNSUPPORTED, naming what was asked, before anything is enqueued.
+ * vk_query_batch runs such queries one by one, with vk_query's bits.
+ * VK_ERR_INVALID: null handle, unknown kind, p not finite or <= 0, a bad operator, more than VK_MAX_SIM_OPS of them.
+ * VK_ERR_UNSUPPORTED: a VK_LAYOUT_STATIC handle; a source beside the cosine over rows of more than 1024 features.  VK_ERR_STATE: a
+ * source beside the cosine after the first append, on a finalized handle or on a view that keeps no copy of the rows.  A refused call
+ * leaves the handle as it was. */
+int vk_corpus_set_span_sim(vk_corpus_t *c, int32_t src_kind, float src_arg, const int32_t *op_kinds, const float *op_args, int32_t n_ops);
 /* Token similarity combinators over several static embeddings (MixedTokenSimilarity, MaximumTokenSimilarity and -- see below --
  * MinimumTokenSimilarity of vectorian/sim/modifier.py), VK_LAYOUT_STATIC only.  The reference builds every operand's matrix completely
  * -- VectorSim, chain, sim[id(t_j)][j] = 1, clip -- and combines the CLIPPED matrices cell by cell, without another clip

@@ -50,8 +50,12 @@ def main():
 		"the same width -- reported beside the cosine as sim_mix: prepare_ms and the whole query's wall time, each query's")
 	ap.add_argument("--span-batch", type=int, default=0, metavar="B", help="the span-embedding index's shape (one vector per slice, as --len-t 1 "
 		"--min-len 1 --max-len 1 --gap linear): times query_batch of B one-vector queries with HipSpanEncoderIndex's options; prints pairs/s and the route")
+	ap.add_argument("--span-sim", action="append", default=[], metavar="KIND[:ARG]", help="the span-embedding index's shape, may be repeated: after the "
+		"plain cosine, the same one-vector queries under this span similarity (vk_corpus_set_span_sim) -- pnorm:P under Scale(s), "
+		"DistanceToSimilarity with the median distance at one half, sqrt-cosine bare, cosine under Bias(1), Scale(0.5) -- reported beside the "
+		"cosine as span_sims: score_ms (device events) and the whole query's wall time, each query's, and the bytes the scoring pass reads")
 	args = ap.parse_args()
-	if args.span_batch > 0:
+	if args.span_batch > 0 or args.span_sim:
 		args.alg, args.layout, args.len_t, args.min_len, args.max_len = "align", "contextual", 1, 1, 1
 
 	import torch
@@ -175,6 +179,13 @@ def main():
 		return
 	corpus = core.Corpus(layout=core.VK_LAYOUT_CONTEXTUAL, d=args.d, n_tokens=n_tok, n_sentences=args.sentences,
 		keep_magnitudes=args.alg == "wrd", precision=args.precision)
+	span_sims = []
+	for text in args.span_sim:
+		kind, _, arg = text.partition(":")
+		span_sims.append((text, {"cosine": core.VK_SIMSRC_COSINE, "pnorm": core.VK_SIMSRC_PNORM, "sqrt-cosine": core.VK_SIMSRC_SQRT_COSINE}[kind], float(arg or 0)))
+	if any(kind != core.VK_SIMSRC_COSINE for _, kind, _ in span_sims):
+		# the handle keeps the unmodified rows from its first append on, then goes back to the cosine for the plain run
+		corpus.set_span_sim(next((kind, arg) for _, kind, arg in span_sims if kind != core.VK_SIMSRC_COSINE), [])
 	E_dev = torch.from_numpy(E).to(device)
 	gen = torch.Generator(device=device)
 	gen.manual_seed(7)
@@ -191,6 +202,8 @@ def main():
 		del x, idx
 	corpus.set_sentences(off)
 	corpus.finalize()
+	if span_sims:
+		corpus.set_span_sim(None, [])
 
 	filter_ms = None
 	n_tok_scored = n_tok
@@ -226,6 +239,39 @@ def main():
 	def step(q):
 		return corpus.query(q, algorithm=alg, locality=loc, gap_s=gap, gap_t=gap, q_normalize=True, max_matches=args.k,
 			min_score=0.0 if loc != 1 else -1e9, want_flow=args.alg == "align")
+
+	if span_sims:
+		def each():
+			"""score_ms and wall time of every query after the warm-up"""
+			out = []
+			for i in range(args.warmup + args.steps):
+				torch.cuda.synchronize()
+				t0 = time.perf_counter()
+				top = corpus.query(qs[i], q_normalize=True, locality=0, gap_s=0.0, gap_t=0.0, max_matches=args.k, min_score=0.0, want_flow=False)
+				ms = (time.perf_counter() - t0) * 1e3
+				if i >= args.warmup:
+					out.append((corpus.last_timings()["score_ms"], ms, top.n))
+			return {"score_ms_each": [a for a, _, _ in out], "query_ms_each": [b for _, b, _ in out], "score_ms_median": float(np.median([a for a, _, _ in out])),
+				"query_ms_median": float(np.median([b for _, b, _ in out])), "matches_min": int(min(n for _, _, n in out))}
+		unit_bytes = args.sentences * ((args.d + 31) // 32 * 32) * (4 if args.precision == "f32" else 2)
+		raw_bytes = args.sentences * ((args.d + 15) // 16 * 16) * 4
+		by_sim = {"cosine (plain)": dict(each(), bytes_read=unit_bytes)}
+		for text, kind, arg in span_sims:
+			ops = []
+			if kind == core.VK_SIMSRC_PNORM:
+				sample = E[rng.integers(0, V, size=256)]
+				dist = (np.abs(sample[:128, None] - sample[None, 128:]) ** arg).sum(-1) ** (1 / arg)
+				ops = [(core.VK_SIMOP_SCALE, 1 / (2 * float(np.median(dist)))), (core.VK_SIMOP_ONE_MINUS, 0.0)]
+			elif kind == core.VK_SIMSRC_COSINE:
+				ops = [(core.VK_SIMOP_BIAS, 1.0), (core.VK_SIMOP_SCALE, 0.5)]
+			corpus.set_span_sim(None if kind == core.VK_SIMSRC_COSINE else (kind, arg), ops)
+			by_sim[text] = dict(each(), bytes_read=unit_bytes if kind == core.VK_SIMSRC_COSINE else raw_bytes)
+		for r in by_sim.values():
+			r["TB_per_s"] = r["bytes_read"] / (r["score_ms_median"] * 1e-3) / 1e12
+		print(json.dumps({"span_sims": by_sim, "d": args.d, "precision": args.precision, "spans": args.sentences, "k": args.k, "steps": args.steps,
+			"device_bytes": corpus.device_bytes}))
+		corpus.close()
+		return
 
 	if args.span_batch > 0:
 		import ctypes

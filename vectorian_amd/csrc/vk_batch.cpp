@@ -557,13 +557,15 @@ static int query_batch_body(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_q
 	}
 	// a source that is not the cosine (vk_corpus_set_sim_source) or a combinator (vk_corpus_set_sim_mix): the batch's 16-bit table is
 	// the cosine's -- query by query
-	const bool sourced = c->table_is_canonical();
-	if (sourced) gemm = false;
+	// (a span similarity, vk_corpus_set_span_sim: no shared route computes it -- not the span GEMM pass, not the shared pass: query by
+	// query through vk_query's code, with vk_query's bits)
+	const bool sourced = c->table_is_canonical(), span_sim = c->span_sim.active();
+	if (sourced || span_sim) gemm = false;
 	if (!gemm) {
 		// one-token queries over one-token slices: the span pass, before the shared pass would take them two at a time
-		const int rcs = query_batch_span(c, qs, n_queries, outs, keep);
+		const int rcs = span_sim ? VK_ERR_UNSUPPORTED : query_batch_span(c, qs, n_queries, outs, keep);
 		if (rcs != VK_ERR_UNSUPPORTED) return rcs;
-		const int rcb = sourced ? VK_ERR_UNSUPPORTED : query_batch_shared_pass(c, qs, n_queries, outs, keep);
+		const int rcb = (sourced || span_sim) ? VK_ERR_UNSUPPORTED : query_batch_shared_pass(c, qs, n_queries, outs, keep);
 		if (rcb != VK_ERR_UNSUPPORTED) return rcb;
 		c->batch_state[VK_BS_ROUTE] = 1;
 		for (int i = 0; i < n_queries; i++) {

@@ -269,6 +269,8 @@ static int append_pooled_body(vk_corpus *c, const void *rows, int64_t n_rows, in
 	VK_HIP(vk_launch_pool_spans(dev_rows, dtype == VK_BF16, ids ? (const int32_t *)d_ids : nullptr, d_spans, d_spans + n_spans, n_spans, d, agg,
 		d_pooled, c->stream));
 	VK_HIP(vk_launch_pack(d_pooled, 0, n_spans, d, c->d_pad, c->rows_appended, c->d_tiles, c->d_mag, normalize, c->prec, c->stream));
+	if (c->raw_rows)   // a span similarity beside the cosine: the aggregates once more, unmodified (a row of NaN stays NaN), as fp32 tiles
+		VK_HIP(vk_launch_pack(d_pooled, 0, n_spans, d, c->raw_tile_bytes / 64, c->rows_appended, *c->raw_rows, nullptr, 0, 1, c->stream));
 	if (pooled_out) VK_HIP(hipMemcpyAsync(pooled_out, d_pooled, (size_t)n_spans * (size_t)d * 4, hipMemcpyDeviceToHost, c->stream));
 	VK_HIP(hipStreamSynchronize(c->stream));
 	c->rows_appended += n_spans;
@@ -282,7 +284,8 @@ int vk_corpus_append_pooled(vk_corpus_t *c, const void *rows, int64_t n_rows, in
 	if (c->is_view) return fail(VK_ERR_STATE, "rows are appended to the owning handle, before taking views");
 	if (c->desc.layout != VK_LAYOUT_CONTEXTUAL)
 		return fail(VK_ERR_UNSUPPORTED, "pooled span vectors are appended to a VK_LAYOUT_CONTEXTUAL handle (one row per span): this corpus is VK_LAYOUT_STATIC");
-	if (c->sim_src.kind != VK_SIMSRC_COSINE || c->mixed() || c->raw_rows)
+	// (a span similarity -- vk_corpus_set_span_sim -- is no such source: its copy of the unmodified rows is packed below)
+	if (c->sim_src.kind != VK_SIMSRC_COSINE || c->mixed() || (c->raw_rows && !c->span_sim.sourced()))
 		return fail(VK_ERR_UNSUPPORTED, "pooled span vectors under a similarity source or combinator: the span corpus computes the cosine");
 	if (dtype != VK_F32 && dtype != VK_BF16) return fail(VK_ERR_INVALID, "bad dtype");
 	if (mem != VK_MEM_HOST && mem != VK_MEM_DEVICE) return fail(VK_ERR_INVALID, "bad memory kind");
@@ -588,6 +591,44 @@ int vk_corpus_set_sim_source(vk_corpus_t *c, int32_t kind, float arg) {
 	return VK_OK;
 }
 
+// The span similarity (vk_span_sim_host.h): a VK_LAYOUT_CONTEXTUAL handle of one-row slices under a VectorSim that is not
+// the bare cosine.  Host state in fields of its own (vk_corpus_shape::span_sim); a source that is not the cosine reads the UNMODIFIED
+// rows, of which the handle allocates the second, fp32 copy here as vk_corpus_set_sim_source does for a static handle -- hence before
+// the first append.  Everything is validated before anything changes: a refused call leaves the handle as it was.
+int vk_corpus_set_span_sim(vk_corpus_t *c, int32_t src_kind, float src_arg, const int32_t *op_kinds, const float *op_args, int32_t n_ops) {
+	if (!c || (n_ops > 0 && (!op_kinds || !op_args))) return fail(VK_ERR_INVALID, "null argument");
+	if (vk_host::sim_src_check(src_kind, src_arg) != VK_OK)
+		return fail(VK_ERR_INVALID, src_kind == VK_SIMSRC_PNORM ? "vk_corpus_set_span_sim: VK_SIMSRC_PNORM: p must be finite and > 0" : "vk_corpus_set_span_sim: unknown similarity source " + std::to_string(src_kind));
+	int bad = -1;
+	if (vk_host::sim_ops_check(op_kinds, op_args, n_ops, &bad) != VK_OK) {
+		if (bad < 0) return fail(VK_ERR_INVALID, "vk_corpus_set_span_sim: n_ops must be 0 .. VK_MAX_SIM_OPS (8), got " + std::to_string(n_ops));
+		return fail(VK_ERR_INVALID, "vk_corpus_set_span_sim: similarity operator " + std::to_string(bad) + ": unknown kind or an argument that is not finite");
+	}
+	if (c->desc.layout != VK_LAYOUT_CONTEXTUAL)
+		return fail(VK_ERR_UNSUPPORTED, "a span similarity is set on a VK_LAYOUT_CONTEXTUAL handle (one row per span): this corpus is VK_LAYOUT_STATIC (vk_corpus_set_sim_source, vk_corpus_set_sim_ops)");
+	vk_host::span_sim sim{};
+	sim.src = vk_host::sim_src{src_kind, src_kind == VK_SIMSRC_PNORM ? src_arg : 0.0f};
+	sim.ops.n = n_ops;
+	for (int i = 0; i < n_ops; i++) { sim.ops.kind[i] = op_kinds[i]; sim.ops.arg[i] = op_args[i]; }
+	if (sim.sourced() && !c->raw_rows) {
+		if (c->desc.d > vk_host::kSimSrcMaxD)
+			return fail(VK_ERR_UNSUPPORTED, "span similarities beside the cosine: rows of at most " + std::to_string(vk_host::kSimSrcMaxD) + " features (the query is staged in 4 KiB of LDS)");
+		if (c->rows_appended > 0 || c->finalized || c->is_view || c->shares_vectors)
+			return fail(VK_ERR_STATE, "a span similarity beside the cosine is set before the first append: it reads the unmodified rows, and they are gone");
+		VK_HIP(hipSetDevice(c->device));
+		const int raw_tile_bytes = vk_host::span_sim_raw_tile_bytes(c->desc.d);
+		const size_t bytes = (size_t)c->n_tiles * (size_t)raw_tile_bytes;
+		auto rows = std::make_shared<vk_devbuf<uint8_t>>();
+		if (int rc = rows->reserve(bytes, nullptr)) return rc;
+		VK_HIP(hipMemsetAsync(*rows, 0, bytes, c->stream));   // (an error leaves the handle without the copy: `rows` frees it)
+		VK_HIP(hipStreamSynchronize(c->stream));
+		c->raw_rows = rows; c->raw_tile_bytes = raw_tile_bytes;
+		c->device_bytes += (int64_t)bytes;   // counted by hand, as under vk_corpus_set_sim_source: the buffer may outlive this handle
+	}
+	c->span_sim = sim;
+	return VK_OK;
+}
+
 // The combinator of a mixed handle (vk_sim_mix_host.h): host state, read when a query fills its tables.  Before the first
 // append, as a source is: the operands' rows arrive beside the handle's own.
 int vk_corpus_set_sim_mix(vk_corpus_t *c, int32_t kind, int32_t n_operands, const double *weights) {
@@ -714,6 +755,9 @@ int vk_corpus_set_query_operand(vk_corpus_t *c, int32_t i, const void *q_vectors
 int vk_corpus_filter(vk_corpus_t *src, uint64_t pos_mask, uint64_t tag_mask, vk_corpus_t **out) {
 	if (!src || !out) return fail(VK_ERR_INVALID, "null argument");
 	if (!src->finalized) return fail(VK_ERR_STATE, "corpus not finalized");
+	// (a filtered span would be a slice without a row: no query on such a handle is span-shaped, and the copy of the unmodified rows
+	// is not filtered)
+	if (src->span_sim.active()) return fail(VK_ERR_UNSUPPORTED, "token filters on a handle under a span similarity (vk_corpus_set_span_sim): a span is one row");
 	if (pos_mask && !src->d_pos) return fail(VK_ERR_STATE, "pos filter needs vk_corpus_set_token_pos");
 	if (tag_mask && !src->d_tag) return fail(VK_ERR_STATE, "tag filter needs vk_corpus_set_token_tags");
 	VK_HIP(hipSetDevice(src->device));

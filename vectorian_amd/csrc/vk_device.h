@@ -399,6 +399,22 @@ struct VkSpanBatchParams {
 	float *matrix;             // [n_queries x n_pad] clipped cosines
 };
 
+// vk_span_sim_kernel / vk_span_ops_kernel (vk_span_sim.hip): a one-row query against the rows of a span corpus under the
+// handle's span similarity (vk_corpus_set_span_sim) -- the score of span i is ops(src(span_i, q)), unclipped.  Geometry: vk_span_sim_host.h
+struct VkSpanSimParams {
+	vk_host::sim_src src;      // the cosine: the MFMA chain on the unit tiles (tiles, qtile); else the cell of vk_sim_src_host.h on the raw copy
+	vk_host::sim_ops ops;
+	const uint8_t *tiles;      // the corpus's unit tiles, 16 spans each, and the query's tile
+	const uint8_t *qtile;
+	int32_t tile_bytes, nk32, tail, prec;
+	const uint8_t *raw_tiles;  // the unmodified rows in the fp32 tile layout: raw_tile_bytes = ceil(d / 16) KiB per 16 spans
+	int32_t raw_tile_bytes, d;
+	const float *q_row;        // the query's unmodified row [d]
+	float q_abs_sum;           // sum_k |q_k| (vk_host::sim_src_abs_sum; the sqrt-cosine reads it)
+	int64_t n;                 // spans
+	float *scores;             // [n]
+};
+
 #ifdef __cplusplus
 namespace vk_host { struct shadow_format; }   // vk_bound_host.h
 
@@ -487,6 +503,7 @@ int32_t vk_score_m7t_tail_k(void);   // ... and over the 8-bit shadow (vk_score_
 int32_t vk_score_m9f_takes(const VkScoreParams *p);
 hipError_t vk_launch_score_m9f(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
 hipError_t vk_launch_span(const VkScoreParams *p, hipStream_t stream);
+hipError_t vk_launch_span_sim(const VkSpanSimParams *p, hipStream_t stream);   // a span corpus under its span similarity (vk_span_sim.hip)
 hipError_t vk_launch_span_batch(const VkSpanBatchParams *p, hipStream_t stream);   // a batch of one-token queries over the same tiles (vk_span_batch.hip)
 hipError_t vk_launch_score_batch(const VkScoreBatchParams *p, int32_t lt, size_t smem, hipStream_t stream);
 hipError_t vk_launch_topk_scores(const float *scores, int64_t n, float min_score, int32_t k, uint64_t *out,

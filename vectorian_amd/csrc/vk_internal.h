@@ -11,6 +11,7 @@
 #include "vk_bound_host.h"
 #include "vk_route_host.h"
 #include "vk_span_batch_host.h"
+#include "vk_span_sim_host.h"
 #include "vk_sim_ops_host.h"
 
 #include <algorithm>
@@ -177,6 +178,11 @@ struct vk_corpus_shape {
 		std::shared_ptr<vk_devbuf<uint8_t>> raw_rows;   // under a source that is not the cosine: the unmodified rows, fp32 tiles of raw_tile_bytes
 		int raw_tile_bytes = 0;
 	} operands[VK_MAX_SIM_OPERANDS - 1];
+	// the span similarity of a VK_LAYOUT_CONTEXTUAL handle of one-row slices (vk_corpus_set_span_sim; vk_span_sim_host.h), in
+	// fields of its own: nothing keyed on sim_ops.n > 0 or table_is_canonical() engages for such a handle -- the scoring pass's float IS
+	// the result.  Under a source that is not the cosine the handle keeps the unmodified rows in raw_rows, as a static handle does.
+	// Views inherit it with the shape.
+	vk_host::span_sim span_sim{};
 	bool mixed() const { return sim_mix.kind != VK_SIMMIX_NONE; }
 	// what the kernels' sim_src says: not the cosine -- read the table's cell -- under a source of the handle's or a combinator
 	int dev_sim_src() const { return mixed() ? VK_DEV_SIMSRC_MIXED : sim_src.kind; }

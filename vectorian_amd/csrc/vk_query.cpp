@@ -43,6 +43,16 @@ int vk_validate_query(const vk_corpus *c, const vk_query_desc *q, const vk_topk_
 	if (!c->finalized) return fail(VK_ERR_STATE, "corpus not finalized");
 	if (q->len_t < 1) return fail(VK_ERR_INVALID, "empty query");
 	if (q->len_t > VK_MAX_LONG_QUERY_LEN) return fail(VK_ERR_UNSUPPORTED, "query longer than VK_MAX_LONG_QUERY_LEN (512) tokens");
+	if (c->span_sim.active()) {
+		// a span corpus under its span similarity (vk_corpus_set_span_sim): vk_span_sim_kernel / vk_span_ops_kernel score one query row
+		// against one-row slices and nothing else does -- decided here, before anything is enqueued (vk_span_sim_host.h)
+		vk_host::span_sim_query s;
+		s.algorithm = q->algorithm; s.locality = q->locality; s.len_t = q->len_t; s.uniform_len = c->uniform_len;
+		s.tagged = q->tag_weights != nullptr; s.submatch = q->submatch_weight != 0.0f; s.boost = q->boost != nullptr;
+		s.want_flow = q->want_flow != 0; s.only = q->only_slices != nullptr; s.sim_rows = out->sim_rows != nullptr;
+		if (const char *what = vk_host::span_sim_refusal(s))
+			return fail(VK_ERR_UNSUPPORTED, std::string("a handle under a span similarity (vk_corpus_set_span_sim) answers one-row local alignment queries over one-row slices, score = sim(span, query): this query asks for ") + what);
+	}
 	if (q->len_t > VK_MAX_QUERY_LEN) {
 		// 65 .. 512 tokens: the role-swapped one-wave-per-slice kernel (vk_longq_kernel) -- alignments over slices of at most
 		// VK_MAX_SENT_LEN tokens (those of more than 64: its block form)
@@ -402,6 +412,9 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		VK_HIP(hipMemcpyAsync(c->d_qtile8, qtile8.data(), qtile8.size(), hipMemcpyHostToDevice, st));
 	}
 
+	// a span similarity beside the cosine: the query's row as given too -- q_normalize is the cosine tile's alone
+	if (c->span_sim.sourced() && (rc = upload_source_query(c, q, keep, st))) return rc;
+
 	VkScoreParams p{};
 	float qmass_all[VK_MAX_QUERY_LEN] = {0};   // masses of the query tokens (transport algorithms), all 64 columns
 	const size_t n_ws = std::max<size_t>((size_t)kGapTable, (size_t)c->max_len + 2);   // w_s up to the longest slice
@@ -471,7 +484,8 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	// result set are the oracle's floats, whichever kernel ranked the slices (per query, batched GEMM, a shard of the corpus).
 	const bool canon_tr = q->algorithm == VK_ALG_RWMD && !q->wmd_full && q->want_flow && out->sim_rows != nullptr;
 	const int kk = facts.kk;
-	const float sel_floor = (do_flow || canon_tr) ? vk_host::restated_floor(q->min_score) : q->min_score;
+	// (a span similarity: admission is score > max(min_score, 0) -- its scores are no clipped cosines, NaN and negative values are no matches)
+	const float sel_floor = c->span_sim.active() ? vk_host::span_sim_floor(q->min_score) : (do_flow || canon_tr) ? vk_host::restated_floor(q->min_score) : q->min_score;
 
 	// ---- the fused scoring kernel ------------------------------------------
 	// handles on one corpus take turns: this scoring kernel starts when the peer's has finished (its selection and
@@ -613,9 +627,28 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 		// span-embedding index: one vector per slice, one query vector -> the clipped cosine is the local alignment score.
 		// The aligner scores are written only if something reads them: the traceback kernel restates those of the winners, and
 		// without a booster the score IS the aligner score ((raw / 1) * 1)
+		if (c->span_sim.active()) {
+			// ... under a span similarity: the score is ops(src(span, q)), unclipped; no raw array (vk_validate_query has
+			// refused boosters, so r.span_skip_raw holds: the aligner score of a winner is its score)
+			VkSpanSimParams sp{};
+			sp.src = c->span_sim.src; sp.ops = c->span_sim.ops;
+			sp.tiles = c->d_tiles; sp.qtile = c->d_qtile; sp.tile_bytes = c->tile_bytes; sp.nk32 = c->nk32; sp.tail = c->tail; sp.prec = c->prec;
+			sp.n = n; sp.scores = c->d_scores;
+			if (c->span_sim.sourced()) {
+				if (!c->raw_rows) return fail(VK_ERR_STATE, "span similarity beside the cosine without the copy of the unmodified rows");
+				// the query's row as the caller gives it (uploaded with the query tile, above) and sum_k |q_k|, as the table kernel's
+				std::vector<float> &qrow = keep.vec<float>((size_t)c->desc.d);
+				for (int kf = 0; kf < c->desc.d; kf++)
+					qrow[(size_t)kf] = q->q_dtype == VK_F32 ? ((const float *)q->q_vectors)[kf] : bf16_to_f32(((const uint16_t *)q->q_vectors)[kf]);
+				sp.raw_tiles = *c->raw_rows; sp.raw_tile_bytes = c->raw_tile_bytes; sp.d = c->desc.d;
+				sp.q_row = c->d_qraw; sp.q_abs_sum = vk_host::sim_src_abs_sum(qrow.data(), c->desc.d);
+			}
+			VK_HIP(vk_launch_span_sim(&sp, st));
+		} else {
 		VkScoreParams ps = p;
 		if (r.span_skip_raw) ps.raw = nullptr;
 		VK_HIP(vk_launch_span(&ps, st));
+		}
 	} else if (!wide_query) {
 	p.max_short_len = VK_FAST_SENT_LEN;
 	// the aligner scores of all slices: read by the submatch bound and, without traceback, for the winners; with traceback the

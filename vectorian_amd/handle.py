@@ -148,6 +148,18 @@ class Corpus:
 		beside the cosine reads the unmodified rows, so it is set BEFORE append_vectors; static layout only."""
 		_core._check(_core.lib().vk_corpus_set_sim_source(self._h, int(kind), float(arg)))
 
+	def set_span_sim(self, source=None, ops=()):
+		"""the span similarity of a contextual handle of one-row slices (vk_corpus_set_span_sim): source -- None for the cosine, else
+		(kind, arg) as set_sim_source -- and its operator chain as set_sim_ops.  The score of a span is ops(source(span, query)),
+		unclipped; admission is score > max(min_score, 0).  A source beside the cosine reads the unmodified rows, so it is set BEFORE
+		the first append_vectors / append_pooled.  Views inherit it."""
+		pairs = [tuple(op.sim_op) if hasattr(op, "sim_op") else tuple(op) for op in ops]
+		kinds = np.ascontiguousarray([int(k) for k, _ in pairs], dtype=np.int32)
+		args = np.ascontiguousarray([a for _, a in pairs], dtype=np.float32)
+		kind, arg = source if source is not None else (_core.VK_SIMSRC_COSINE, 0.0)
+		with self.lock:
+			_core._check(_core.lib().vk_corpus_set_span_sim(self._h, int(kind), float(arg), _core._np_ptr(kinds), _core._np_ptr(args), len(pairs)))
+
 	def set_sim_mix(self, kind, n_operands, weights=None):
 		"""a token similarity combinator over n_operands static embeddings (vk_corpus_set_sim_mix): core.VK_SIMMIX_AVERAGE with one
 		weight per operand (float64), or core.VK_SIMMIX_MAXIMUM.  Operand 0 is this handle; set BEFORE append_vectors."""

@@ -238,10 +238,12 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 	def _operator_chain(similarity, embedding):
 		"""(source, chain) of the vector similarity: the source's (kind, float32 arg) of vk_corpus_set_sim_source -- None for
 		CosineSim -- and the (kind, float32 arg) pairs of the operator chain, empty without one; or the reason this similarity does
-		not run here"""
+		not run here.  embedding: the token embedding the similarity runs over (sources and chains: static ones
+		only), or None for the vectors of a span index, which are nobody's tokens"""
 		if isinstance(similarity, CosineSim):
 			return None, []
-		computes = "the HIP path computes CosineSim, PNormDistance and ImprovedSqrtCosineSim (over contextual embeddings CosineSim only), not other VectorSims"
+		over = "" if embedding is None else " (over contextual embeddings CosineSim only)"
+		computes = f"the HIP path computes CosineSim, PNormDistance and ImprovedSqrtCosineSim{over}, not other VectorSims"
 		if not isinstance(similarity, ModifiedVectorSim):
 			return HipBruteForceIndex._source_of(similarity, similarity, embedding, f"{similarity.name}: {computes}"), []
 		source, operators = similarity.source, similarity.operators
@@ -250,10 +252,10 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 		src = None
 		if not isinstance(source, CosineSim):
 			src = HipBruteForceIndex._source_of(source, similarity, embedding,
-				f"{similarity.name}: the HIP path modifies CosineSim, PNormDistance and ImprovedSqrtCosineSim (over contextual embeddings CosineSim only), not {source.name}")
+				f"{similarity.name}: the HIP path modifies CosineSim, PNormDistance and ImprovedSqrtCosineSim{over}, not {source.name}")
 		if len(operators) > core.VK_MAX_SIM_OPS:
 			raise NotImplementedError(f"{similarity.name}: {len(operators)} operators; the HIP path takes at most {core.VK_MAX_SIM_OPS}")
-		if not embedding.is_static:
+		if embedding is not None and not embedding.is_static:
 			raise NotImplementedError(f"{similarity.name}: operators on the cosine run over static embeddings only; "
 				f"{embedding.name} is contextual")
 		ops = []
@@ -313,7 +315,7 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 		"""(kind, float32 arg) of a source that is not the cosine, or why it does not run here"""
 		if type(source) not in (PNormDistance, EuclideanDistance, ImprovedSqrtCosineSim):   # (a subclass may compute anything)
 			raise NotImplementedError(refusal)
-		if not embedding.is_static:
+		if embedding is not None and not embedding.is_static:
 			raise NotImplementedError(f"{similarity.name}: {source.name} runs over static embeddings only; {embedding.name} is contextual")
 		kind, arg = source.sim_source
 		if kind == core.VK_SIMSRC_PNORM and not (np.isfinite(arg) and arg > 0):
@@ -522,9 +524,18 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 
 
 class HipSpanEncoderIndex(Index):
-	"""Brute-force cosine search over ONE embedding per span: what SpanEncoderIndex / FaissCosineIndex('Flat')
+	"""Brute-force search over ONE embedding per span: what SpanEncoderIndex / FaissCosineIndex('Flat')
 	do (vectorian/index.py:679-810), as a matrix-vector product + bounded result set on the GPU.  Realised on
-	the same kernels: a corpus of one-token slices, a one-token query, score = clip(cosine)."""
+	the same kernels: a corpus of one-token slices, a one-token query, score = clip(cosine).
+
+	Under a VectorSim that is not the bare CosineSim -- PNormDistance, EuclideanDistance, ImprovedSqrtCosineSim, or ONE
+	ModifiedVectorSim of up to 8 operators of vectorian_amd.kernel on one of them or on CosineSim -- the score of a span is
+	sim(span, query) as one float32, on the unmodified vectors for the three sources, with NO clip afterwards, as in the reference's
+	SpanEncoderIndex._find.  A bare PNormDistance therefore ranks the FARTHEST span first, as upstream does: wrap it in
+	ModifiedVectorSim(.., DistanceToSimilarity()) or RadialBasis.  A match is a span whose score is > max(min_score, 0): NaN and
+	negative values are never matches (upstream: NaN -> -inf, stop below 0), and a score of exactly 0 is dropped where upstream keeps
+	it -- as the cosine index does under its default min_score = 0.  FuzzyJaccardSim, DirectionalDistance, user-defined VectorSims
+	and subclasses are refused by name."""
 
 	def __init__(self, partition, embedding, span_sim, nlp=None, vectors=None, device=0, corpus_factory=None):
 		super().__init__(partition, span_sim)
@@ -551,7 +562,16 @@ class HipSpanEncoderIndex(Index):
 			if vectors.shape != (n, embedding.dimension):
 				raise ValueError(f"expected {(n, embedding.dimension)} span vectors, got {vectors.shape}")
 		make = corpus_factory or core.Corpus
+		# the VectorSim: (source, chain) by the token path's rules, minus "static embeddings only" -- a span vector is nobody's token
+		vector_sim = getattr(span_sim, "vector_sim", None)
+		source, chain = (None, []) if vector_sim is None else HipBruteForceIndex._operator_chain(vector_sim, None)
 		self._corpus = make(layout=core.VK_LAYOUT_CONTEXTUAL, d=embedding.dimension, n_tokens=n, n_sentences=n, device=device)
+		if source is not None or chain:
+			if not hasattr(self._corpus, "set_span_sim"):   # a capability of the backend: core.Corpus has it
+				self._corpus.close()
+				raise NotImplementedError(f"{vector_sim.name}: this backend's span index computes CosineSim only")
+			# before the first append: a source beside the cosine reads the unmodified rows, of which the handle keeps a copy
+			self._corpus.set_span_sim(source, chain)
 		if pooled:
 			self._append_pooled(embedding)
 		else:

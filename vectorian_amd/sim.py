@@ -14,8 +14,9 @@ TokenSimilarityModifier / MixedTokenSimilarity / MaximumTokenSimilarity / Minimu
 (DESIGN 14): `MixedTokenSimilarity([EmbeddingTokenSim(a, CosineSim()), EmbeddingTokenSim(b, CosineSim())], [2, 1])`.
 SpanEmbedding / AggregatedSpanEmbedding / EmbeddedSpanSim   vectorian/embedding/span.py:27-93, vectorian/sim/span.py:74-95: one vector
 per span, from the caller or -- the mean, minimum or maximum of the span's token vectors -- pooled on the device:
-`AggregatedSpanEmbedding(emb, np.mean).to_sentence_sim()`.
-FuzzyJaccardSim, DirectionalDistance, user-defined VectorSims, chains and combinators over contextual embeddings, nested
+`AggregatedSpanEmbedding(emb, np.mean).to_sentence_sim()`.  The VectorSim of a span index is any of the above, unclipped, over span
+vectors of any origin: `emb.to_sentence_sim(ModifiedVectorSim(PNormDistance(2), RadialBasis(0.5)))`.
+FuzzyJaccardSim, DirectionalDistance, user-defined VectorSims, chains and combinators over contextual TOKEN embeddings, nested
 combinators, UnaryTokenSimilarityModifier and a combinator under WordRotatorsDistance are out of scope and are rejected explicitly
 rather than ignored; the tag-weighted variant is a "next" row.
 """
@@ -346,11 +347,14 @@ class EmbeddedSpanSim(SpanSim):
 	def embedding(self):
 		return self._embedding
 
+	@property
+	def vector_sim(self):
+		return self._vector_sim
+
 	def create_index(self, partition, **kwargs):
 		# the reference picks FaissCosineIndex / SpanEncoderIndex here (vectorian/sim/span.py:83-88)
+		# (the index resolves the VectorSim -- DESIGN 17 -- or says why it does not run here)
 		from vectorian_amd.index import HipSpanEncoderIndex
-		if not isinstance(self._vector_sim, CosineSim):
-			raise NotImplementedError(f"{self._vector_sim.name}: the HIP path computes CosineSim")
 		return HipSpanEncoderIndex(partition, self._embedding, self, **kwargs)
 
 	def to_args(self, index):
