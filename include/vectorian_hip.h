@@ -363,6 +363,44 @@ int vk_corpus_append_operand_vectors(vk_corpus_t *c, int32_t i, const void *rows
  * on a mixed handle that lacks an operand's rows, or whose len_t differs from theirs, ends with VK_ERR_STATE before anything is
  * enqueued.  Calls on one handle are the caller's to serialise: set the operands and run the query under one lock. */
 int vk_corpus_set_query_operand(vk_corpus_t *c, int32_t i, const void *q_vectors, int32_t len_t, int32_t q_dtype, int32_t q_normalize);
+
+/* --- the booster of a Saliency, compiled and kept on the device (vectorian/saliency.py; Booster, document.h:175-187): keyword signals
+ *     per slice, smoothed over a document's neighbouring slices, averaged into one multiplicative weight per slice.  The arithmetic of
+ *     every cell: vectorian_amd/csrc/vk_saliency_host.h.
+ * A finalized handle keeps up to VK_MAX_SIGNALS signal slots of n_sentences floats (counted by vk_corpus_device_bytes) until
+ * vk_corpus_set_saliency averages them.  Every call below needs a finalized handle (VK_ERR_STATE before that), answers
+ * VK_ERR_UNSUPPORTED on a handle under a span similarity (vk_corpus_set_span_sim: the span index has no boosters), checks its arguments
+ * before it touches the handle -- a refused call leaves the handle as it was -- and returns after the device has finished.
+ * Calls on one handle are the caller's to serialise. */
+#define VK_MAX_SIGNALS 8
+typedef enum { VK_SIGNAL_FILTER_MAX = 0, VK_SIGNAL_FILTER_CONV = 1 } vk_signal_filter_kind;
+/* slot <- the keyword signal: per slice, float32(min(count, max_count)) / max_count over the tokens whose vocabulary id is one of
+ * keyword_ids [n_keywords] (host; each in [0, vocab_size), else VK_ERR_INVALID; n_keywords = 0: a signal of zeros).  A token whose id is
+ * negative or beyond the vocabulary never counts.  token_ids: NULL on a VK_LAYOUT_STATIC handle, which reads its resident ids; on a
+ * VK_LAYOUT_CONTEXTUAL handle host [n_tokens] ids for this call (they go to a workspace, not into the handle) and vocab_size the size of
+ * their vocabulary -- NULL there: VK_ERR_INVALID.  vocab_size is ignored on a static handle (its own holds). */
+int vk_signal_keywords(vk_corpus_t *c, int32_t slot, const int32_t *keyword_ids, int32_t n_keywords, int32_t max_count,
+	const int32_t *token_ids, int32_t vocab_size);
+/* slot <- values: host [n_sentences] floats (a CustomSignal) */
+int vk_signal_set(vk_corpus_t *c, int32_t slot, const float *values);
+/* slot <- the slot's signal filtered per document: doc_off host [n_docs + 1], ascending from 0 to n_sentences -- document d's slices are
+ * [doc_off[d], doc_off[d + 1]).  VK_SIGNAL_FILTER_MAX: scipy.ndimage.maximum_filter(x, size=width), mode reflect, pulse NULL.
+ * VK_SIGNAL_FILTER_CONV: np.convolve(x, pulse, mode="same") in float64 with pulse host [width] doubles as they are (ConvFilter divides
+ * by their sum before), taps added in ascending order, rounded to float32; a document of fewer than `width` slices passes through.
+ * width: 1 .. 4096.  A slot that holds no signal: VK_ERR_STATE. */
+int vk_signal_filter(vk_corpus_t *c, int32_t slot, int32_t kind, int32_t width, const double *pulse, const int64_t *doc_off, int64_t n_docs);
+/* The booster: np.average([ones, signal(slots[0]), .., signal(slots[n - 1])], axis=0, weights=weights) with weights host [n + 1]
+ * doubles (the ones' first; finite, not negative, their sum > 0), in float64, rounded to float32 once; n = 0: all ones.  It becomes
+ * RESIDENT, per row of the slice table, with its host copy and the answer to "is every boost >= 0 and none NaN" (the bound pass's
+ * precondition): vk_query / vk_query_batch with boost == NULL then run under it on every route that honours a boost -- as if the caller
+ * had passed that array, bit for bit, with nothing scanned or copied per query; a query's own boost overrides it; a route that takes no
+ * boost (the span batch pass) is not taken.  Every slot is freed.  boost_out: NULL, or host [n_sentences] for the compiled booster.
+ * The views of a corpus (vk_corpus_view) share its booster, before and after they are taken; a filtered corpus starts without one.
+ * Called on the owning handle (a view: VK_ERR_STATE), with no query in flight on any handle of the corpus. */
+int vk_corpus_set_saliency(vk_corpus_t *c, const int32_t *slots, const double *weights, int32_t n, float *boost_out);
+/* no resident booster any more (and none before: fine); the slots stay as they are */
+int vk_corpus_clear_saliency(vk_corpus_t *c);
+
 int vk_corpus_free(vk_corpus_t *c);
 int vk_corpus_device_bytes(const vk_corpus_t *c, int64_t *bytes);
 

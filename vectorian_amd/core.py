@@ -42,6 +42,9 @@ VK_MAX_SIM_OPERANDS = 4
 VK_SIMMIX_NONE, VK_SIMMIX_AVERAGE, VK_SIMMIX_MAXIMUM = 0, 1, 2
 # the aggregates of pooled span vectors (vk_corpus_append_pooled; vectorian_amd/sim.py AggregatedSpanEmbedding)
 VK_POOL_MEAN, VK_POOL_MIN, VK_POOL_MAX = 0, 1, 2
+# the signal slots of a handle and the filters of a signal (vk_signal_filter; vectorian_amd/saliency.py states each one)
+VK_MAX_SIGNALS = 8
+VK_SIGNAL_FILTER_MAX, VK_SIGNAL_FILTER_CONV = 0, 1
 
 
 class Locality(enum.IntEnum):
@@ -105,6 +108,7 @@ EXPORTS = [
 	"vk_abi_version", "vk_last_error", "vk_init", "vk_device_count", "vk_corpus_view",
 	"vk_corpus_create", "vk_corpus_append_vectors", "vk_corpus_append_pooled", "vk_corpus_set_token_ids", "vk_corpus_set_token_pos", "vk_corpus_set_token_tags", "vk_corpus_filter", "vk_corpus_set_sim_ops", "vk_corpus_set_sim_source", "vk_corpus_set_span_sim",
 	"vk_corpus_set_sim_mix", "vk_corpus_set_sim_operand", "vk_corpus_append_operand_vectors", "vk_corpus_set_query_operand",
+	"vk_signal_keywords", "vk_signal_set", "vk_signal_filter", "vk_corpus_set_saliency", "vk_corpus_clear_saliency",
 	"vk_corpus_set_sentences", "vk_corpus_set_slices", "vk_corpus_finalize", "vk_corpus_free", "vk_corpus_device_bytes",
 	"vk_query", "vk_query_batch", "vk_last_scores", "vk_last_timings", "vk_merge_topk",
 	"vk_record_words", "vk_pack_records", "vk_merge_records", "vk_rwmd_from_rows"]
@@ -165,6 +169,11 @@ def lib():
 		L.vk_corpus_set_sim_operand.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_int32]
 		L.vk_corpus_append_operand_vectors.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32]
 		L.vk_corpus_set_query_operand.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+		L.vk_signal_keywords.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
+		L.vk_signal_set.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+		L.vk_signal_filter.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]
+		L.vk_corpus_set_saliency.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+		L.vk_corpus_clear_saliency.argtypes = [C.c_void_p]
 		L.vk_corpus_device_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
 		L.vk_query.argtypes = [C.c_void_p, C.POINTER(_QueryDesc), C.POINTER(_TopkOut)]
 		L.vk_query_batch.argtypes = [C.c_void_p, C.POINTER(_QueryDesc), C.c_int32, C.POINTER(_TopkOut)]

@@ -242,14 +242,14 @@ static int query_batch_shared_pass(vk_corpus_t *c, const vk_query_desc *qs, int3
 	if ((rc = c->d_ws.reserve(kGapTable, &c->device_bytes))) return rc;
 	VK_HIP(hipMemcpyAsync(c->d_ws, ws, kGapTable * sizeof(float), hipMemcpyHostToDevice, st));
 	VK_HIP(hipMemcpyAsync(c->d_wt, wt, 160 * sizeof(float), hipMemcpyHostToDevice, st));
-	if (q0.boost) {
+	if (q0.boost && !c->boost_is_resident(q0.boost)) {
 		if ((rc = c->d_boost.reserve((size_t)n + 8, &c->device_bytes))) return rc;
 		VK_HIP(hipMemcpyAsync(c->d_boost, q0.boost, (size_t)n * 4, hipMemcpyHostToDevice, st));   // no long slices: rows == slices
 	}
 	corpus_fields(p, c);
 	p.n_sent = (int32_t)n;
 	p.qtiles = c->d_bq; p.locality = q0.locality; p.ws = c->d_ws; p.wt = c->d_wt + 80; p.wt0 = c->d_wt;
-	p.boost = q0.boost ? (float *)c->d_boost : nullptr; p.scores = c->d_bscores; p.raw = c->d_braw;
+	p.boost = c->dev_boost(q0.boost); p.scores = c->d_bscores; p.raw = c->d_braw;
 	if (q0.want_flow && q0.algorithm == VK_ALG_ALIGN) p.raw = nullptr;   // the flow kernel restates the winners' aligner scores; nothing else reads the array (no submatch weights here)
 
 	float score_ms_total = 0.0f, total_ms = 0.0f;
@@ -710,7 +710,7 @@ static int query_batch_body(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_q
 		qparam[(size_t)(i / qpt) * 8 + 4 + (size_t)(i % qpt)] = qinv[(size_t)i];
 	}
 	if (b32) VK_HIP(hipMemcpyAsync(d_qparam, qparam.data(), qparam.size() * 4, hipMemcpyHostToDevice, st));
-	if (qs[0].boost) {
+	if (qs[0].boost && !c->boost_is_resident(qs[0].boost)) {
 		if ((rc = c->d_boost.reserve((size_t)n + 8, &c->device_bytes))) return rc;
 		VK_HIP(hipMemcpyAsync(c->d_boost, qs[0].boost, (size_t)n * 4, hipMemcpyHostToDevice, st));
 	}
@@ -726,7 +726,7 @@ static int query_batch_body(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_q
 	p.qtiles = c->d_bq; p.q_len = c->d_bqlen; p.n_queries = n_queries; p.n_sent = (int32_t)n;
 	p.tiles_per_sent = c->uniform_len / 16;
 	p.symmetric = qs[0].rwmd_symmetric; p.nbow = qs[0].rwmd_normalize_bow;
-	p.boost = qs[0].boost ? (float *)c->d_boost : nullptr;
+	p.boost = c->dev_boost(qs[0].boost);
 	p.scores = c->d_bscores;
 	p.n_qtiles = n_qtiles; p.qpt = qpt; p.q_inv_len = d_qinv; p.q_param = d_qparam; p.dense = dense ? 1 : 0;
 	p.late_mask = wide32 ? 0 : 4;   // waves w and w + 4 of a workgroup share a SIMD (768-d rows: one wave per SIMD, nobody to alternate with)
@@ -866,6 +866,13 @@ int vk_query_batch(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_queries, v
 	struct consume { vk_corpus_t *c; ~consume() { c->in_batch = false; c->drop_query_operands(); } } consumed{c};
 	c->in_batch = true;
 	if (n_queries == 0) return VK_OK;
+	// queries without a boost of their own run under the handle's resident one (vk_corpus_set_saliency), as if they had passed that array
+	std::vector<vk_query_desc> qs_res;
+	if (const float *resident = c->resident_boost()) {
+		qs_res.assign(qs, qs + n_queries);
+		for (vk_query_desc &q : qs_res) if (!q.boost) q.boost = resident;
+		qs = qs_res.data();
+	}
 	if (qs[0].abort && *qs[0].abort) {
 		for (int i = 0; i < n_queries; i++) outs[i].n_out = 0;
 		return fail(VK_ERR_ABORTED, "batch aborted by the caller");

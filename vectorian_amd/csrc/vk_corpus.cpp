@@ -4,7 +4,11 @@
 
 #include "vk_internal.h"
 #include "vk_pool_host.h"
+#include "vk_saliency_host.h"
 
+#include <functional>
+
+static_assert(vk_host::kSalMaxSignals == VK_MAX_SIGNALS && vk_host::SAL_FILTER_MAX == VK_SIGNAL_FILTER_MAX && vk_host::SAL_FILTER_CONV == VK_SIGNAL_FILTER_CONV, "vk_saliency_host.h and the C-ABI");
 static_assert(vk_host::POOL_MEAN == VK_POOL_MEAN && vk_host::POOL_MIN == VK_POOL_MIN && vk_host::POOL_MAX == VK_POOL_MAX, "vk_pool_host.h and the C-ABI");
 static_assert(vk_host::POOL_INVALID == VK_ERR_INVALID && vk_host::POOL_UNSUPPORTED == VK_ERR_UNSUPPORTED, "vk_pool_host.h and the C-ABI");
 
@@ -119,6 +123,7 @@ int vk_corpus_create(const vk_corpus_desc *desc, vk_corpus_t **out) {
 	c->device = dev;
 	c->shared = std::make_shared<vk_devblock>();
 	c->shared->device = dev;
+	c->resident = std::make_shared<vk_resident_boost>();
 	c->d_pad = (desc->d + 15) / 16 * 16;
 	c->prec = desc->precision == VK_PREC_F32 ? 1 : 0;
 	if (c->prec) {
@@ -750,6 +755,193 @@ int vk_corpus_set_query_operand(vk_corpus_t *c, int32_t i, const void *q_vectors
 	return VK_OK;
 }
 
+// ---- the booster of a Saliency (vk_saliency_host.h, vk_saliency.hip).  Every entry point validates all of its arguments
+// before it touches the handle, keeps what it uploads for the call in buffers of the call, and returns after the stream has drained.
+
+// what every signal call asks of the handle and of the slot
+static int signal_call_ok(const vk_corpus *c, int32_t slot, const char *who) {
+	if (!c) return fail(VK_ERR_INVALID, "null argument");
+	if (!c->finalized) return fail(VK_ERR_STATE, std::string(who) + ": corpus not finalized");
+	if (c->span_sim.active()) return fail(VK_ERR_UNSUPPORTED, std::string(who) + ": a handle under a span similarity (vk_corpus_set_span_sim) has no boosters");
+	if (slot < 0 || slot >= VK_MAX_SIGNALS) return fail(VK_ERR_INVALID, std::string(who) + ": slot must be 0 .. VK_MAX_SIGNALS - 1");
+	return VK_OK;
+}
+// a buffer of d_signal that no slot names (there is one more buffer than slots)
+static int free_signal_buffer(const vk_corpus *c) {
+	for (int b = 0; b <= VK_MAX_SIGNALS; b++)
+		if (std::find(std::begin(c->signal_buf), std::end(c->signal_buf), b) == std::end(c->signal_buf)) return b;
+	return -1;
+}
+// the buffer a slot's new signal is written to: its own again, or a free one
+static int signal_buffer_for(vk_corpus *c, int32_t slot, int *buf) {
+	*buf = c->signal_buf[slot] >= 0 ? c->signal_buf[slot] : free_signal_buffer(c);
+	return c->d_signal[*buf].reserve((size_t)c->desc.n_sentences, &c->device_bytes);
+}
+// runs `body` on the handle's device and leaves nothing in flight behind it, whatever it returns
+static int signal_run(vk_corpus *c, const std::function<int()> &body) {
+	VK_HIP(hipSetDevice(c->device));
+	const int rc = body();
+	const hipError_t drained = hipStreamSynchronize(c->stream);
+	if (!rc && drained != hipSuccess) return fail(VK_ERR_HIP, std::string("a saliency kernel failed: ") + hipGetErrorString(drained));
+	return rc;
+}
+
+int vk_signal_keywords(vk_corpus_t *c, int32_t slot, const int32_t *keyword_ids, int32_t n_keywords, int32_t max_count, const int32_t *token_ids,
+	int32_t vocab_size) {
+	if (int rc = signal_call_ok(c, slot, "vk_signal_keywords")) return rc;
+	const bool is_static = c->desc.layout == VK_LAYOUT_STATIC;
+	if (!is_static && !token_ids) return fail(VK_ERR_INVALID, "vk_signal_keywords: a VK_LAYOUT_CONTEXTUAL handle keeps no token ids: pass them for the call");
+	const int64_t V = is_static ? c->desc.vocab_size : vocab_size;
+	if (V < 1) return fail(VK_ERR_INVALID, "vk_signal_keywords: vocab_size must be >= 1");
+	if (max_count < 1) return fail(VK_ERR_INVALID, "vk_signal_keywords: max_count must be >= 1");
+	if (n_keywords < 0 || (n_keywords > 0 && !keyword_ids)) return fail(VK_ERR_INVALID, "vk_signal_keywords: bad keyword ids");
+	std::vector<uint32_t> bitmap((size_t)vk_host::sal_bitmap_words(V), 0u);
+	for (int32_t k = 0; k < n_keywords; k++) {
+		if (keyword_ids[k] < 0 || keyword_ids[k] >= V) return fail(VK_ERR_INVALID, "vk_signal_keywords: a keyword id outside the vocabulary");
+		vk_host::sal_bitmap_set(bitmap.data(), keyword_ids[k]);
+	}
+	const int64_t ns = c->desc.n_sentences, nt = c->desc.n_tokens;
+	if (!c->entry_sent.empty()) (void)row_of_sentence(c, 0);   // builds sent_entry
+	vk_devbuf<uint32_t> d_bitmap;
+	vk_devbuf<int32_t> d_ids, d_rows;
+	return signal_run(c, [&]() -> int {
+		hipStream_t st = c->stream;
+		int rc, buf = -1;
+		if ((rc = d_bitmap.reserve(bitmap.size(), nullptr))) return rc;
+		VK_HIP(hipMemcpyAsync(d_bitmap, bitmap.data(), bitmap.size() * 4, hipMemcpyHostToDevice, st));
+		const int32_t *ids = c->d_tok_id;
+		if (!is_static) {
+			if ((rc = d_ids.reserve((size_t)nt + 64, nullptr))) return rc;
+			if (nt > 0) VK_HIP(hipMemcpyAsync(d_ids, token_ids, (size_t)nt * 4, hipMemcpyHostToDevice, st));
+			ids = d_ids;
+		}
+		const int32_t *rows = nullptr;
+		if (!c->entry_sent.empty()) {
+			if ((rc = d_rows.reserve((size_t)ns, nullptr))) return rc;
+			VK_HIP(hipMemcpyAsync(d_rows, c->sent_entry.data(), (size_t)ns * 4, hipMemcpyHostToDevice, st));
+			rows = d_rows;
+		}
+		if ((rc = signal_buffer_for(c, slot, &buf))) return rc;
+		VK_HIP(vk_launch_keyword_signal(ids, c->d_sent_start, c->d_sent_end, rows, ns, d_bitmap, V, max_count, c->d_signal[buf], st));
+		VK_HIP(hipStreamSynchronize(st));
+		c->signal_buf[slot] = buf;
+		return VK_OK;
+	});
+}
+
+int vk_signal_set(vk_corpus_t *c, int32_t slot, const float *values) {
+	if (int rc = signal_call_ok(c, slot, "vk_signal_set")) return rc;
+	if (!values && c->desc.n_sentences > 0) return fail(VK_ERR_INVALID, "vk_signal_set: values is null");
+	return signal_run(c, [&]() -> int {
+		int buf = -1;
+		if (int rc = signal_buffer_for(c, slot, &buf)) return rc;
+		if (c->desc.n_sentences > 0) VK_HIP(hipMemcpyAsync(c->d_signal[buf], values, (size_t)c->desc.n_sentences * 4, hipMemcpyHostToDevice, c->stream));
+		VK_HIP(hipStreamSynchronize(c->stream));
+		c->signal_buf[slot] = buf;
+		return VK_OK;
+	});
+}
+
+int vk_signal_filter(vk_corpus_t *c, int32_t slot, int32_t kind, int32_t width, const double *pulse, const int64_t *doc_off, int64_t n_docs) {
+	if (int rc = signal_call_ok(c, slot, "vk_signal_filter")) return rc;
+	if (kind != VK_SIGNAL_FILTER_MAX && kind != VK_SIGNAL_FILTER_CONV) return fail(VK_ERR_INVALID, "vk_signal_filter: unknown filter kind " + std::to_string(kind));
+	if (width < 1 || width > vk_host::kSalMaxWidth) return fail(VK_ERR_INVALID, "vk_signal_filter: width must be 1 .. 4096");
+	if (kind == VK_SIGNAL_FILTER_CONV && !pulse) return fail(VK_ERR_INVALID, "vk_signal_filter: a convolution needs its pulse");
+	if (!doc_off) return fail(VK_ERR_INVALID, "vk_signal_filter: doc_off is null");
+	const char *why = "";
+	if (vk_host::sal_check_docs(doc_off, n_docs, c->desc.n_sentences, &why)) return fail(VK_ERR_INVALID, std::string("vk_signal_filter: ") + why);
+	if (c->signal_buf[slot] < 0) return fail(VK_ERR_STATE, "vk_signal_filter: the slot holds no signal");
+	vk_devbuf<int64_t> d_off;
+	vk_devbuf<double> d_pulse;
+	return signal_run(c, [&]() -> int {
+		hipStream_t st = c->stream;
+		int rc;
+		if (c->desc.n_sentences == 0) return VK_OK;
+		if ((rc = d_off.reserve((size_t)n_docs + 1, nullptr))) return rc;
+		VK_HIP(hipMemcpyAsync(d_off, doc_off, ((size_t)n_docs + 1) * 8, hipMemcpyHostToDevice, st));
+		if (kind == VK_SIGNAL_FILTER_CONV) {
+			if ((rc = d_pulse.reserve((size_t)width, nullptr))) return rc;
+			VK_HIP(hipMemcpyAsync(d_pulse, pulse, (size_t)width * 8, hipMemcpyHostToDevice, st));
+		}
+		const int to = free_signal_buffer(c);
+		if ((rc = c->d_signal[to].reserve((size_t)c->desc.n_sentences, &c->device_bytes))) return rc;
+		VK_HIP(vk_launch_signal_filter(c->d_signal[c->signal_buf[slot]], c->d_signal[to], d_off, n_docs, c->desc.n_sentences, kind, width,
+			kind == VK_SIGNAL_FILTER_CONV ? (const double *)d_pulse : nullptr, st));
+		VK_HIP(hipStreamSynchronize(st));
+		c->signal_buf[slot] = to;   // (the buffer it leaves is the next filter's)
+		return VK_OK;
+	});
+}
+
+int vk_corpus_set_saliency(vk_corpus_t *c, const int32_t *slots, const double *weights, int32_t n, float *boost_out) {
+	if (int rc = signal_call_ok(c, 0, "vk_corpus_set_saliency")) return rc;
+	if (c->is_view) return fail(VK_ERR_STATE, "vk_corpus_set_saliency: the booster is set on the owning handle (its views share it)");
+	if (n < 0 || n > VK_MAX_SIGNALS || (n > 0 && !slots) || !weights) return fail(VK_ERR_INVALID, "vk_corpus_set_saliency: 0 .. VK_MAX_SIGNALS slots and their weights");
+	VkBoostAverageArgs a{};
+	for (int32_t k = 0; k <= n; k++) {
+		if (!(weights[k] >= 0.0) || !std::isfinite(weights[k])) return fail(VK_ERR_INVALID, "vk_corpus_set_saliency: weights must be finite and not negative");
+		a.weights[k] = weights[k];
+	}
+	a.wsum = vk_host::sal_numpy_sum(weights, (int64_t)n + 1);
+	if (!(a.wsum > 0.0)) return fail(VK_ERR_INVALID, "vk_corpus_set_saliency: the weights sum to 0");
+	for (int32_t k = 0; k < n; k++) {
+		if (slots[k] < 0 || slots[k] >= VK_MAX_SIGNALS) return fail(VK_ERR_INVALID, "vk_corpus_set_saliency: slot must be 0 .. VK_MAX_SIGNALS - 1");
+		if (c->signal_buf[slots[k]] < 0) return fail(VK_ERR_STATE, "vk_corpus_set_saliency: slot " + std::to_string(slots[k]) + " holds no signal");
+		a.signals[k] = c->d_signal[c->signal_buf[slots[k]]];
+	}
+	a.n_signals = n;
+	const int64_t ns = c->desc.n_sentences, ne = c->n_entries;
+	vk_resident_boost &res = *c->resident;
+	vk_devbuf<int32_t> d_entry, d_bad;
+	vk_devbuf<float> d_slices;
+	std::vector<float> host((size_t)std::max<int64_t>(ns, 1), 1.0f);   // (never empty: its address names the resident booster)
+	int32_t bad = 0;
+	const int rc = signal_run(c, [&]() -> int {
+		hipStream_t st = c->stream;
+		int rc;
+		if (!c->entry_sent.empty()) {
+			if ((rc = d_entry.reserve((size_t)ne, nullptr))) return rc;
+			VK_HIP(hipMemcpyAsync(d_entry, c->entry_sent.data(), (size_t)ne * 4, hipMemcpyHostToDevice, st));
+			a.entry_sent = d_entry;
+		}
+		if ((rc = d_slices.reserve((size_t)ns, nullptr)) || (rc = d_bad.reserve(4, nullptr))) return rc;
+		VK_HIP(hipMemsetAsync(d_bad, 0, 16, st));
+		res.active = false;   // from here on the rows change: a failure leaves the corpus without a booster, not with half of one
+		if ((rc = res.rows.reserve((size_t)ne + 8, nullptr))) return rc;
+		a.n_entries = ne; a.rows = res.rows; a.slices = d_slices; a.bad = d_bad;
+		VK_HIP(vk_launch_boost_average(&a, st));
+		if (ns > 0) VK_HIP(hipMemcpyAsync(host.data(), d_slices, (size_t)ns * 4, hipMemcpyDeviceToHost, st));
+		VK_HIP(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+		VK_HIP(hipStreamSynchronize(st));
+		return VK_OK;
+	});
+	const int64_t counted = (int64_t)(res.rows.capacity() * sizeof(float));
+	c->device_bytes += counted - res.counted;
+	res.counted = counted;
+	if (rc) { res.host.clear(); return rc; }
+	res.host.swap(host);
+	res.nonneg = bad == 0;
+	res.active = true;
+	if (boost_out && ns > 0) memcpy(boost_out, res.host.data(), (size_t)ns * 4);
+	for (int k = 0; k < VK_MAX_SIGNALS; k++) c->signal_buf[k] = -1;
+	for (auto &b : c->d_signal) b.reset();
+	return VK_OK;
+}
+
+int vk_corpus_clear_saliency(vk_corpus_t *c) {
+	if (int rc = signal_call_ok(c, 0, "vk_corpus_clear_saliency")) return rc;
+	if (c->is_view) return fail(VK_ERR_STATE, "vk_corpus_clear_saliency: the booster is cleared on the owning handle (its views share it)");
+	VK_HIP(hipSetDevice(c->device));
+	vk_resident_boost &res = *c->resident;
+	res.active = false;
+	res.nonneg = true;
+	res.host.clear();
+	res.rows.reset();
+	c->device_bytes -= res.counted;
+	res.counted = 0;
+	return VK_OK;
+}
+
 // The filtered corpus: keep flags and their scan on the device, slice table re-indexed, token rows / ids / codes /
 // magnitudes gathered.  A handle of its own (stream, workspaces); the static layout shares the vocabulary arrays.
 int vk_corpus_filter(vk_corpus_t *src, uint64_t pos_mask, uint64_t tag_mask, vk_corpus_t **out) {
@@ -805,6 +997,7 @@ int vk_corpus_filter(vk_corpus_t *src, uint64_t pos_mask, uint64_t tag_mask, vk_
 			c->desc = desc; c->device = src->device;
 			c->shared = std::make_shared<vk_devblock>();
 			c->shared->device = src->device;
+			c->resident = std::make_shared<vk_resident_boost>();   // (a booster is per slice of ITS corpus: a filtered corpus starts without one)
 			c->d_pad = src->d_pad; c->nk32 = src->nk32; c->tail = src->tail; c->tile_bytes = src->tile_bytes; c->prec = src->prec;
 			c->rows_total = c->rows_appended = src->rows_total; c->n_tiles = src->n_tiles;
 			c->d_tiles = src->d_tiles; c->d_mag = src->d_mag; c->shares_vectors = true;

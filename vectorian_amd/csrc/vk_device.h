@@ -415,6 +415,19 @@ struct VkSpanSimParams {
 	float *scores;             // [n]
 };
 
+// vk_boost_average_kernel (vk_saliency.hip): the booster of a Saliency from its signals.  The cell: vk_saliency_host.h
+struct VkBoostAverageArgs {
+	const float *signals[8];   // [n_sentences] each, n_signals of them (vk_host::kSalMaxSignals)
+	double weights[9];         // of the ones, then of every signal
+	double wsum;               // their sum (vk_host::sal_numpy_sum)
+	int32_t n_signals;
+	const int32_t *entry_sent; // [n_entries] slice of a row of the slice table, -1 = padding; null: rows are slices
+	int64_t n_entries;
+	float *rows;               // [n_entries + 8] the booster per row of the slice table (padding: 1)
+	float *slices;             // [n_sentences] ... per slice
+	int32_t *bad;              // raised by a boost that is negative or NaN
+};
+
 #ifdef __cplusplus
 namespace vk_host { struct shadow_format; }   // vk_bound_host.h
 
@@ -473,6 +486,14 @@ hipError_t vk_launch_pack(const void *in, int32_t dtype_bf16, int64_t n_rows, in
 // rows[ids[start .. end)] when ids is given; everything on the device
 hipError_t vk_launch_pool_spans(const void *rows, int32_t dtype_bf16, const int32_t *ids, const int64_t *start, const int64_t *end,
 	int64_t n_spans, int32_t d, int32_t agg, float *out, hipStream_t stream);
+// the booster of a Saliency (vk_saliency.hip; vk_saliency_host.h), everything on the device: the keyword signal of every slice from the
+// token ids and a bitmap of the keyword ids over the vocabulary (row_of_slice: null where rows of the slice table are slices); a
+// signal filtered per document into another buffer (pulse: the taps of a convolution, float64); the average into the booster
+hipError_t vk_launch_keyword_signal(const int32_t *ids, const int32_t *sent_start, const int32_t *sent_end, const int32_t *row_of_slice,
+	int64_t n_slices, const uint32_t *bitmap, int64_t vocab_size, int32_t max_count, float *signal, hipStream_t stream);
+hipError_t vk_launch_signal_filter(const float *x, float *y, const int64_t *doc_off, int64_t n_docs, int64_t n_slices, int32_t kind,
+	int32_t width, const double *pulse, hipStream_t stream);
+hipError_t vk_launch_boost_average(const VkBoostAverageArgs *p, hipStream_t stream);
 // queries of 17..32 tokens, linear / affine gaps (vk_score32.hip)
 size_t vk_score32_lds_bytes(int32_t nk32, int32_t tail, int32_t max_pair_tiles, int32_t len_t, int32_t gap_mode, int32_t waves);
 int32_t vk_score32_waves(int32_t nk32, int32_t tail, int32_t max_pair_tiles, int32_t len_t, int32_t gap_mode);   // waves per workgroup that fit the LDS: 4, 2, 1 or 0 (none)

@@ -13,6 +13,7 @@
 #include "vk_span_batch_host.h"
 #include "vk_span_sim_host.h"
 #include "vk_sim_ops_host.h"
+#include "vk_saliency_host.h"
 
 #include <algorithm>
 #include <atomic>
@@ -113,6 +114,17 @@ std::mutex &vk_ring_mutex();
 // What a view takes over from its source (vk_corpus_view assigns this part in one statement): the description of the resident corpus,
 // the aliases of the arrays several handles read and their owners, the host mirrors.  Nothing a handle has for itself belongs here --
 // no workspace, event, stream, lazily built layout or ring link.
+// The resident booster of a corpus (vk_corpus_set_saliency): one block that the owning handle and its views hold together --
+// what the owner sets or clears, the views see.  `rows`: the booster per row of the slice table, as upload_boost lays a caller's array
+// out (padding rows: 1); `host`: per slice, what the winners' restated scores read; `nonneg`: every boost >= 0 and none NaN, computed
+// where the booster was (the bound pass's precondition).  Counted in the owner's device_bytes by hand, as raw_rows is.
+struct vk_resident_boost {
+	bool active = false, nonneg = true;
+	vk_devbuf<float> rows;
+	std::vector<float> host;
+	int64_t counted = 0;
+};
+
 struct vk_corpus_shape {
 	vk_corpus_desc desc{};
 	int device = 0;
@@ -183,6 +195,12 @@ struct vk_corpus_shape {
 	// the result.  Under a source that is not the cosine the handle keeps the unmodified rows in raw_rows, as a static handle does.
 	// Views inherit it with the shape.
 	vk_host::span_sim span_sim{};
+	// the resident booster (made with the handle; a view's is its source's, a filtered corpus has its own, empty one)
+	std::shared_ptr<vk_resident_boost> resident;
+	// the booster a query without one of its own runs under: the host copy of the resident one, or null.  The query paths see it as
+	// the query's boost -- every rule that reads q->boost holds as it stands -- and know it by its address (boost_is_resident)
+	const float *resident_boost() const { return resident && resident->active ? resident->host.data() : nullptr; }
+	bool boost_is_resident(const float *boost) const { return boost != nullptr && boost == resident_boost(); }
 	bool mixed() const { return sim_mix.kind != VK_SIMMIX_NONE; }
 	// what the kernels' sim_src says: not the cosine -- read the table's cell -- under a source of the handle's or a combinator
 	int dev_sim_src() const { return mixed() ? VK_DEV_SIMSRC_MIXED : sim_src.kind; }
@@ -240,6 +258,12 @@ struct vk_corpus : vk_corpus_shape {
 	bool in_batch = false;        // vk_query_batch is running its queries one by one: it clears the pending rows, not vk_query
 	void drop_query_operands() { for (auto &m : mixop) m.pending.clear(); q_operand_at = 0; }
 	vk_devbuf<float> d_scores, d_raw, d_boost;
+	// the booster of a query on the device, per row of the slice table: the resident one, or the query's own in d_boost (upload_boost)
+	const float *dev_boost(const float *boost) const { return !boost ? nullptr : boost_is_resident(boost) ? (const float *)resident->rows : (const float *)d_boost; }
+	// the signal slots of a Saliency being compiled (vk_signal_*): slot k lives in d_signal[signal_buf[k]] (-1: empty); a filter writes
+	// into a free buffer and the slot moves there.  Freed by vk_corpus_set_saliency
+	vk_devbuf<float> d_signal[VK_MAX_SIGNALS + 1];
+	int signal_buf[VK_MAX_SIGNALS] = {-1, -1, -1, -1, -1, -1, -1, -1};
 	vk_devbuf<uint64_t> d_keys[2];
 	vk_devbuf<float> d_out_raw, d_out_sim;   // the winners' outputs: at least VK_MAX_MATCHES of them (grown by a query that asks for more matches)
 	vk_devbuf<int16_t> d_out_map;
@@ -415,8 +439,13 @@ int select_blocks(vk_corpus *c, float floor, int kk, hipStream_t st, const uint6
 
 // the caller's boost per slice as d_boost per row of the slice table (padding rows: 1)
 // (nonneg: also answers whether every slice's boost is >= 0 -- the bound pass needs it; one more pass over the caller's array, vectorised)
+// (the resident booster is on the device already, and its answer with it)
 int upload_boost(vk_corpus *c, const float *boost, vk_host_keep &keep, hipStream_t st, bool *nonneg = nullptr) {
 	const int64_t n = c->n_entries;
+	if (c->boost_is_resident(boost)) {
+		if (nonneg) *nonneg = c->resident->nonneg;
+		return VK_OK;
+	}
 	if (nonneg) {
 		float least = 0.0f;
 		bool nan = false;

@@ -76,7 +76,7 @@ int vk_longq_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_
 		p.tw_keep = 1.0f - q->pos_mismatch_penalty; p.tw_threshold = q->similarity_threshold;
 	}
 	p.ref_total = total;
-	p.boost = q->boost ? (float *)c->d_boost : nullptr;
+	p.boost = c->dev_boost(q->boost);
 	p.scores = c->d_scores; p.raw = q->want_flow ? nullptr : (float *)c->d_raw;   // with traceback the retrace restates the winners' aligner scores
 	p.d = c->desc.d; p.q_ids = is_static ? lq.il + LTP : nullptr;
 

@@ -497,7 +497,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	p.table = c->d_table; p.n_sent = (int32_t)n;
 	p.qtile = c->d_qtile; p.len_t = q->len_t; p.locality = q->locality;
 	p.ws = c->d_ws; p.wt = c->d_wt + 80; p.wt0 = c->d_wt;
-	p.boost = q->boost ? (float *)c->d_boost : nullptr;
+	p.boost = c->dev_boost(q->boost);
 	p.scores = c->d_scores; p.raw = c->d_raw;
 	tag_weight_fields(p, c, q, VK_FAST_QUERY_LEN);
 	// vocabulary transports with tag weights over the static layout: the cells upstream writes twice (static_vocab_fixup,
@@ -1067,6 +1067,9 @@ extern "C" {
 int vk_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out) {
 	// the rows vk_corpus_set_query_operand left belong to this query, however it ends (a batch run query by query drops its own)
 	struct consume { vk_corpus_t *c; ~consume() { if (c && !c->in_batch) c->drop_query_operands(); } } consumed{c};
+	// a query without a boost of its own runs under the handle's resident one (vk_corpus_set_saliency), as if it had passed that array
+	vk_query_desc q_res;
+	if (c && q && !q->boost && c->resident_boost()) { q_res = *q; q_res.boost = c->resident_boost(); q = &q_res; }
 	const int rc = vk_validate_query(c, q, out);
 	if (rc) return rc;
 	if (q->abort && *q->abort) { out->n_out = 0; return fail(VK_ERR_ABORTED, "query aborted by the caller"); }

@@ -135,7 +135,7 @@ class DebugHookMixin:
 				ids = ids[(lens_all[ids] > 0) & np.isfinite(scores[ids])]
 				if len(ids) == 0:
 					continue
-				top = corpus.query(local["qv"].unmodified, q_normalize=True, boost=self._dev_boost, want_flow=True, only_slices=ids, **call)
+				top = corpus.query(local["qv"].unmodified, q_normalize=True, boost=self._boost_of(corpus), want_flow=True, only_slices=ids, **call)
 				stated = np.isfinite(top.score[:top.n])
 				scores[ids[:top.n][stated]] = top.score[:top.n][stated]
 			heap, k, floor = [], args["max_matches"], float(args["min_score"])
@@ -163,7 +163,7 @@ class DebugHookMixin:
 				ids = ids[lens_all[ids] > 0]
 				if len(ids) == 0:
 					continue
-				top = corpus.query(local["qv"].unmodified, q_normalize=True, boost=self._dev_boost, want_flow=True, only_slices=ids, **call)
+				top = corpus.query(local["qv"].unmodified, q_normalize=True, boost=self._boost_of(corpus), want_flow=True, only_slices=ids, **call)
 				chunk = self._matches_from_topk(p_query, top, local["gaps"], args, qmag, masks, local["q_tag_codes"])
 				for i, m in enumerate(chunk):
 					if not np.isfinite(m.score):
@@ -187,7 +187,7 @@ class DebugHookMixin:
 			ids = ids[lens > 0]   # Spans::iterate skips empty slices
 			if len(ids) == 0:
 				continue
-			top = corpus.query(local["qv"].unmodified, q_normalize=True, boost=self._dev_boost, want_flow=True, only_slices=ids, **call)
+			top = corpus.query(local["qv"].unmodified, q_normalize=True, boost=self._boost_of(corpus), want_flow=True, only_slices=ids, **call)
 			for i in range(top.n):
 				g = off + int(ids[i])
 				len_s = int(self._slice_end[g] - self._slice_start[g]) if not masks else len(self._index_map(g, masks))

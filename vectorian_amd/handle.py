@@ -203,6 +203,57 @@ class Corpus:
 	def finalize(self):
 		_core._check(_core.lib().vk_corpus_finalize(self._h))
 
+	# ---- the booster of a Saliency, compiled and kept on the device (vk_signal_*, vk_corpus_set_saliency; vectorian_amd/saliency.py
+	# drives these).  After finalize; every call returns when the device has finished.
+
+	def signal_keywords(self, slot, keyword_ids, max_count=1, token_ids=None, vocab_size=None):
+		"""slot <- the keyword signal of every slice: float32(min(count, max_count)) / max_count over the tokens whose vocabulary id is
+		among keyword_ids.  A static handle reads its resident token ids; a contextual one takes token_ids [n_tokens] and the size of
+		their vocabulary for the call"""
+		kw = np.ascontiguousarray(keyword_ids, dtype=np.int32).reshape(-1)
+		ids = None if token_ids is None else np.ascontiguousarray(token_ids, dtype=np.int32)
+		if ids is not None and ids.shape != (self.n_tokens,):
+			raise ValueError("token_ids must hold one id per token")
+		with self.lock:
+			_core._check(_core.lib().vk_signal_keywords(self._h, int(slot), _core._np_ptr(kw), len(kw), int(max_count),
+				None if ids is None else _core._np_ptr(ids), int(self.vocab_size if vocab_size is None else vocab_size)))
+
+	def signal_set(self, slot, values):
+		"""slot <- values: one float per slice (a CustomSignal)"""
+		v = np.ascontiguousarray(values, dtype=np.float32)
+		if v.shape != (self.n_sentences,):
+			raise ValueError("a signal holds one float per slice")
+		with self.lock:
+			_core._check(_core.lib().vk_signal_set(self._h, int(slot), _core._np_ptr(v)))
+
+	def signal_filter(self, slot, kind, width, doc_off, pulse=None):
+		"""slot <- its signal filtered per document (doc_off: [n_docs + 1] offsets into the slices): core.VK_SIGNAL_FILTER_MAX over
+		windows of `width` slices, or core.VK_SIGNAL_FILTER_CONV with the float64 `pulse` of `width` taps"""
+		off = np.ascontiguousarray(doc_off, dtype=np.int64)
+		p = None if pulse is None else np.ascontiguousarray(pulse, dtype=np.float64)
+		if p is not None and p.shape != (int(width),):
+			raise ValueError("a pulse holds `width` taps")
+		with self.lock:
+			_core._check(_core.lib().vk_signal_filter(self._h, int(slot), int(kind), int(width), None if p is None else _core._np_ptr(p),
+				_core._np_ptr(off), len(off) - 1))
+
+	def set_saliency(self, slots, weights):
+		"""averages the signals of `slots` under `weights` (float64; the ones' weight first) into the corpus's RESIDENT booster and frees
+		the slots: queries with boost=None then run under it, on this handle and its views.  Returns the booster, float32 [n_slices]"""
+		s = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+		w = np.ascontiguousarray(weights, dtype=np.float64)
+		if w.shape != (len(s) + 1,):
+			raise ValueError("one weight for the ones and one per slot")
+		out = np.empty(self.n_sentences, dtype=np.float32)
+		with self.lock:
+			_core._check(_core.lib().vk_corpus_set_saliency(self._h, _core._np_ptr(s), _core._np_ptr(w), len(s), _core._np_ptr(out)))
+		return out
+
+	def clear_saliency(self):
+		"""no resident booster any more (vk_corpus_clear_saliency)"""
+		with self.lock:
+			_core._check(_core.lib().vk_corpus_clear_saliency(self._h))
+
 	@property
 	def device_bytes(self):
 		b = C.c_int64(0)

@@ -26,6 +26,7 @@ from vectorian_amd.lanes import LanesMixin
 from vectorian_amd.match import HipMatch, Match, PyMatch, Region, TokenMatch, TokenMatchEdge, TokenMatchT, _Winners
 from vectorian_amd.options import _QUERY_OPTION_WHITELIST, _split_gap, backend_args
 from vectorian_amd.query import PreparedQuery, Query, default_tokenizer
+from vectorian_amd.saliency import Saliency
 from vectorian_amd.alignment import WordRotatorsDistance
 from vectorian_amd.modifier import (ExtremumTokenSimilarity, MixedTokenSimilarity, TokenSimilarityModifier,
 	UnaryTokenSimilarityModifier)
@@ -150,7 +151,13 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 		n_tokens, n_slices = base, len(self._slice_doc)
 
 		self._boost = None
-		if saliency is not None:
+		self._saliency = None   # a Saliency: compiled on the device after finalize, resident there; the queries pass no boost
+		if isinstance(saliency, Saliency):
+			if shard is not None:
+				raise NotImplementedError("Saliency on a sharded index (shard=): smoothing a signal needs a document's slices on both sides "
+					"of a shard border; compile the booster on one device and pass it as an array")
+			self._saliency = saliency
+		elif saliency is not None:
 			# Booster (vectorian/saliency.py:141-154 -> core.Booster): one multiplicative weight per slice
 			self._boost = np.ascontiguousarray(saliency, dtype=np.float32)
 			if self._boost.shape != (n_slices,):
@@ -233,6 +240,17 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 			self._corpus.set_slices(dev_start, dev_end)
 		self._corpus.finalize()
 		self._max_slice_len = int((np.asarray(dev_end) - np.asarray(dev_start)).max()) if len(dev_start) else 0   # of the resident part
+		if self._saliency is not None:
+			# the documents' offsets into the slices; a handle over contextual embeddings keeps no token ids: they go along for the call
+			doc_off = np.concatenate(([0], np.cumsum(np.bincount(self._slice_doc, minlength=len(session.documents))))).astype(np.int64)
+			ids = None
+			if not emb.is_static:
+				ids = np.concatenate([session.doc_token_ids(i) for i in range(len(session.documents))] or [np.zeros(0, np.int32)]).astype(np.int32)
+			try:
+				self._boost = self._saliency.compile(self._corpus, session, partition, doc_off, token_ids=ids)
+			except BaseException:
+				self._corpus.close()
+				raise
 
 	@staticmethod
 	def _operator_chain(similarity, embedding):
@@ -334,6 +352,23 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 	def corpus(self):
 		return self._corpus
 
+	@property
+	def boost(self):
+		"""the multiplicative weight of every slice, float32 [n_slices] (read-only): the array the index was given, the booster its
+		Saliency compiled to, or None without either"""
+		if self._boost is None:
+			return None
+		b = self._boost.view()
+		b.flags.writeable = False
+		return b
+
+	def _boost_of(self, corpus):
+		"""the boost= of a query on `corpus`: the caller's array; under a Saliency None on the corpus and its views -- the booster is
+		resident there -- and the compiled array on a filtered corpus, which starts without one"""
+		if self._saliency is None:
+			return self._dev_boost
+		return None if corpus is self._corpus or corpus in self._views else self._boost
+
 	def _backend_args(self, options):
 		return backend_args(options)
 
@@ -432,7 +467,7 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 		# here, under the same hold of the lock as the query itself.
 		with getattr(corpus, "lock", _NO_LOCK):
 			try:
-				top = corpus.query(qv.unmodified, q_normalize=True, boost=self._dev_boost, want_flow=True, **call)
+				top = corpus.query(qv.unmodified, q_normalize=True, boost=self._boost_of(corpus), want_flow=True, **call)
 			except core.VkError as e:
 				if e.status != core.VK_ERR_ABORTED:   # Query.abort: the matcher loop ends (match/matcher_impl.h:105), nothing was added
 					raise

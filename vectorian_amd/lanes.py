@@ -98,7 +98,7 @@ class LanesMixin:
 					for o_emb, _, _ in self._mix["operands"]] for i in idx]
 			try:
 				tops = handles[l].query_batch([np.ascontiguousarray(qv.unmodified, dtype=np.float32) for qv in qvs], q_normalize=True,
-					boost=self._dev_boost, want_flow=True, abort_flag=queries[idx[0]]._abort, **ids, **args) if idx else []
+					boost=self._boost_of(handles[l]), want_flow=True, abort_flag=queries[idx[0]]._abort, **ids, **args) if idx else []
 			except core.VkError as e:
 				if e.status != core.VK_ERR_ABORTED:
 					raise
