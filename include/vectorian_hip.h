@@ -284,11 +284,25 @@ int vk_corpus_filter(vk_corpus_t *src, uint64_t pos_mask, uint64_t tag_mask, vk_
  * State of the handle (an index has one similarity): allowed before or after vk_corpus_finalize, n_ops = 0 clears it; vk_corpus_view
  * and vk_corpus_filter copy the chain of `src` into the handle they create, after that each handle is set on its own.
  * VK_ERR_INVALID: more than VK_MAX_SIM_OPS operators, an unknown kind, an argument that is not finite.  VK_ERR_UNSUPPORTED: a
- * chain (n_ops > 0) on VK_LAYOUT_CONTEXTUAL. */
+ * chain (n_ops > 0) on VK_LAYOUT_CONTEXTUAL (such a handle takes its chain through vk_corpus_set_contextual_sim_ops). */
 #define VK_MAX_SIM_OPS 8
 enum { VK_SIMOP_BIAS = 0, VK_SIMOP_SCALE = 1, VK_SIMOP_THRESHOLD = 2,
        VK_SIMOP_ONE_MINUS = 3, VK_SIMOP_POWER = 4, VK_SIMOP_RADIAL_BASIS = 5 };
 int vk_corpus_set_sim_ops(vk_corpus_t *c, const int32_t *kinds, const float *args, int32_t n_ops);
+/* The same chain over a VK_LAYOUT_CONTEXTUAL handle (metric/contextual.cpp:40-56: any VectorSim on the token vectors, then the clip).
+ * A similarity cell is clip01(chain(cosine)) of the UNCLIPPED cosine; there is no sim[id(t_j)][j] = 1 rewrite (metric/static.cpp's
+ * alone), and the query's padding columns stay 0 whatever the chain makes of a zero.  The arithmetic of a cell: contextual_cell,
+ * csrc/vk_sim_ops_host.h.  Tag weights, every DP and transport, edge_sim, sim_rows and the flows read that cell.
+ * State of the handle, before or after vk_corpus_finalize; n_ops = 0 clears it (the handle is then what it always was); views and
+ * filtered corpora copy it.  Alignments without tracebacks are restated in the canonical arithmetic under a chain, as on a static
+ * handle.  A chained handle scores on vk_score_kernel and vk_score32_kernel only: queries of at most 64 tokens over corpora whose
+ * slices have at most 64 tokens.  vk_query answers VK_ERR_UNSUPPORTED, naming the chain and the case, before anything is enqueued,
+ * for a corpus that holds a longer slice, a longer query, and a query of 17 .. 64 tokens the multi-block kernel does not take (rows
+ * too wide for its LDS, affine gaps with a_t < 0).  No bound pass and no span kernel run under a chain; vk_query_batch runs query by
+ * query.
+ * VK_ERR_INVALID: as vk_corpus_set_sim_ops.  VK_ERR_UNSUPPORTED: a VK_LAYOUT_STATIC handle (vk_corpus_set_sim_ops is its entry
+ * point); a handle under a span similarity (vk_corpus_set_span_sim carries the span index's own chain). */
+int vk_corpus_set_contextual_sim_ops(vk_corpus_t *c, const int32_t *kinds, const float *args, int32_t n_ops);
 /* The VectorSim the operator chain runs on (the `source` of a ModifiedVectorSim, or the similarity itself), VK_LAYOUT_STATIC only:
  *   VK_SIMSRC_COSINE (every handle's, arg ignored): the cosine of the normalised rows;
  *   VK_SIMSRC_PNORM, arg p (finite, > 0): (sum_k |a_k - b_k|^p)^(1/p) (PNormDistance, vectorian/sim/vector.py:135-160) -- a DISTANCE:
@@ -323,7 +337,8 @@ int vk_corpus_set_sim_source(vk_corpus_t *c, int32_t kind, float arg);
  * want_flow, no only_slices, no sim_rows; anything else returns VK_ERR_UNSUPPORTED, naming what was asked, before anything is enqueued.
  * vk_query_batch runs such queries one by one, with vk_query's bits.
  * VK_ERR_INVALID: null handle, unknown kind, p not finite or <= 0, a bad operator, more than VK_MAX_SIM_OPS of them.
- * VK_ERR_UNSUPPORTED: a VK_LAYOUT_STATIC handle; a source beside the cosine over rows of more than 1024 features.  VK_ERR_STATE: a
+ * VK_ERR_UNSUPPORTED: a VK_LAYOUT_STATIC handle; a handle under vk_corpus_set_contextual_sim_ops (clear that chain first); a source
+ * beside the cosine over rows of more than 1024 features.  VK_ERR_STATE: a
  * source beside the cosine after the first append, on a finalized handle or on a view that keeps no copy of the rows.  A refused call
  * leaves the handle as it was. */
 int vk_corpus_set_span_sim(vk_corpus_t *c, int32_t src_kind, float src_arg, const int32_t *op_kinds, const float *op_args, int32_t n_ops);

@@ -6,6 +6,7 @@ driver's bench: that is bench.py).  Prints one JSON line per run.
   python tools/bench_configs.py --alg wrd --d 768 --min-len 8 --max-len 64 --sentences 500000
   python tools/bench_configs.py --alg align --gap exp5 --locality global --d 768 --min-len 8 --max-len 64
   python tools/bench_configs.py --span-batch 256 --d 768          the span index's shape: 256 one-vector queries per vk_query_batch
+  python tools/bench_configs.py --contextual-chain --d 300        the headline shape under operator chains on the cosine
 """
 
 import argparse
@@ -54,6 +55,11 @@ def main():
 		"plain cosine, the same one-vector queries under this span similarity (vk_corpus_set_span_sim) -- pnorm:P under Scale(s), "
 		"DistanceToSimilarity with the median distance at one half, sqrt-cosine bare, cosine under Bias(1), Scale(0.5) -- reported beside the "
 		"cosine as span_sims: score_ms (device events) and the whole query's wall time, each query's, and the bytes the scoring pass reads")
+	ap.add_argument("--contextual-chain", action="store_true", help="contextual layout: the same queries on one handle under the plain cosine, under "
+		"[Bias(0)] (the generic tile form with a trivial chain and no bound pass) and under the chains (a), (d) and (e) of tests/sim_ops_cases.py "
+		"(vk_corpus_set_contextual_sim_ops), the forms alternating within the process -- reported as contextual_chain: per form the score "
+		"kernel's time from device events (every query's, median, spread), the algorithmic bf16 bytes over it, the route's plan, and the "
+		"chain's own cost: the difference to [Bias(0)], not to the cosine")
 	args = ap.parse_args()
 	if args.span_batch > 0 or args.span_sim:
 		args.alg, args.layout, args.len_t, args.min_len, args.max_len = "align", "contextual", 1, 1, 1
@@ -239,6 +245,45 @@ def main():
 	def step(q):
 		return corpus.query(q, algorithm=alg, locality=loc, gap_s=gap, gap_t=gap, q_normalize=True, max_matches=args.k,
 			min_score=0.0 if loc != 1 else -1e9, want_flow=args.alg == "align")
+
+	if args.contextual_chain:
+		import ctypes
+		B, S, O, P, R = core.VK_SIMOP_BIAS, core.VK_SIMOP_SCALE, core.VK_SIMOP_ONE_MINUS, core.VK_SIMOP_POWER, core.VK_SIMOP_RADIAL_BASIS
+		forms = [("cosine", []), ("[Bias(0)]", [(B, 0.0)]), ("(a) (x + 1) / 2", [(B, 1.0), (S, 0.5)]),
+			("(d) eight exactly rounded operators", [(B, 1.0), (S, 0.5), (B, -0.125), (S, 1.25), (O, 0.0), (O, 0.0), (B, 0.0625), (S, 0.9)]),
+			("(e) powf", [(P, 2.5)])]
+		core.lib().vk_query_route.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+		plans = ("LISTED", "SPAN", "FUSED", "BOUNDED", "MULTI_BLOCK", "DOCW_ALL", "DOCG_ALL", "WIDE_ALL")   # route_plan, vk_route_host.h
+		runs = {name: {"score_ms_each": [], "query_ms_each": [], "plans": set()} for name, _ in forms}
+		rounds = 3
+		for rnd in range(rounds):   # the forms alternate: a drift of the device's clocks falls on all of them
+			for name, ops in forms:
+				corpus.set_contextual_sim_ops(ops)
+				for i in range(args.warmup):
+					step(qs[i])
+				for i in range(args.steps):
+					torch.cuda.synchronize()
+					t0 = time.perf_counter()
+					step(qs[args.warmup + i])
+					runs[name]["query_ms_each"].append((time.perf_counter() - t0) * 1e3)
+					runs[name]["score_ms_each"].append(corpus.last_timings()["score_ms"])
+					state = np.zeros(16, dtype=np.int64)
+					core._check(core.lib().vk_query_route(corpus._h, state.ctypes.data))
+					runs[name]["plans"].add(plans[int(state[0])])
+		corpus.set_contextual_sim_ops([])
+		bytes_alg = n_tok * args.d * 2
+		for r in runs.values():
+			ms = np.array(r["score_ms_each"])
+			r.update(plans=sorted(r["plans"]), score_ms_median=float(np.median(ms)), score_ms_min=float(ms.min()), score_ms_max=float(ms.max()),
+				query_ms_median=float(np.median(r["query_ms_each"])), algorithmic_bf16_TB_per_s=bytes_alg / (float(np.median(ms)) * 1e-3) / 1e12)
+		base = runs["[Bias(0)]"]["score_ms_median"]
+		for name, r in runs.items():
+			r["score_ms_over_bias0"] = r["score_ms_median"] - base   # the chain's own cost (the cosine: the price of the generic form and of the bound pass, negated)
+		print(json.dumps({"contextual_chain": runs, "d": args.d, "precision": args.precision, "gap": args.gap, "locality": args.locality, "len_t": args.len_t,
+			"len_s": [args.min_len, args.max_len], "sentences": args.sentences, "tokens": n_tok, "k": args.k, "steps_per_round": args.steps, "rounds": rounds,
+			"algorithmic_bf16_bytes": bytes_alg, "note": "score_ms: the scoring pass between device events (under the cosine: the bound pass and its rounds)"}))
+		corpus.close()
+		return
 
 	if span_sims:
 		def each():

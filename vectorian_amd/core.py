@@ -106,7 +106,7 @@ class _Timings(C.Structure):
 
 EXPORTS = [
 	"vk_abi_version", "vk_last_error", "vk_init", "vk_device_count", "vk_corpus_view",
-	"vk_corpus_create", "vk_corpus_append_vectors", "vk_corpus_append_pooled", "vk_corpus_set_token_ids", "vk_corpus_set_token_pos", "vk_corpus_set_token_tags", "vk_corpus_filter", "vk_corpus_set_sim_ops", "vk_corpus_set_sim_source", "vk_corpus_set_span_sim",
+	"vk_corpus_create", "vk_corpus_append_vectors", "vk_corpus_append_pooled", "vk_corpus_set_token_ids", "vk_corpus_set_token_pos", "vk_corpus_set_token_tags", "vk_corpus_filter", "vk_corpus_set_sim_ops", "vk_corpus_set_contextual_sim_ops", "vk_corpus_set_sim_source", "vk_corpus_set_span_sim",
 	"vk_corpus_set_sim_mix", "vk_corpus_set_sim_operand", "vk_corpus_append_operand_vectors", "vk_corpus_set_query_operand",
 	"vk_signal_keywords", "vk_signal_set", "vk_signal_filter", "vk_corpus_set_saliency", "vk_corpus_clear_saliency",
 	"vk_corpus_set_sentences", "vk_corpus_set_slices", "vk_corpus_finalize", "vk_corpus_free", "vk_corpus_device_bytes",
@@ -163,6 +163,7 @@ def lib():
 		L.vk_corpus_view.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
 		L.vk_corpus_filter.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p)]
 		L.vk_corpus_set_sim_ops.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+		L.vk_corpus_set_contextual_sim_ops.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
 		L.vk_corpus_set_sim_source.argtypes = [C.c_void_p, C.c_int32, C.c_float]
 		L.vk_corpus_set_span_sim.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_int32]
 		L.vk_corpus_set_sim_mix.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]

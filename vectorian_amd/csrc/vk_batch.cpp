@@ -559,11 +559,14 @@ static int query_batch_body(vk_corpus_t *c, const vk_query_desc *qs, int32_t n_q
 	// the cosine's -- query by query
 	// (a span similarity, vk_corpus_set_span_sim: no shared route computes it -- not the span GEMM pass, not the shared pass: query by
 	// query through vk_query's code, with vk_query's bits)
-	const bool sourced = c->table_is_canonical(), span_sim = c->span_sim.active();
+	// (a contextual handle under an operator chain, vk_corpus_set_contextual_sim_ops: the GEMM, span and shared passes know the clipped
+	// cosine only -- likewise)
+	const bool chained_ctx = c->desc.layout == VK_LAYOUT_CONTEXTUAL && c->sim_ops.n > 0;
+	const bool sourced = c->table_is_canonical() || chained_ctx, span_sim = c->span_sim.active();
 	if (sourced || span_sim) gemm = false;
 	if (!gemm) {
 		// one-token queries over one-token slices: the span pass, before the shared pass would take them two at a time
-		const int rcs = span_sim ? VK_ERR_UNSUPPORTED : query_batch_span(c, qs, n_queries, outs, keep);
+		const int rcs = (span_sim || chained_ctx) ? VK_ERR_UNSUPPORTED : query_batch_span(c, qs, n_queries, outs, keep);
 		if (rcs != VK_ERR_UNSUPPORTED) return rcs;
 		const int rcb = (sourced || span_sim) ? VK_ERR_UNSUPPORTED : query_batch_shared_pass(c, qs, n_queries, outs, keep);
 		if (rcb != VK_ERR_UNSUPPORTED) return rcb;

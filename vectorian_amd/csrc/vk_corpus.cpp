@@ -550,7 +550,7 @@ int vk_corpus_finalize(vk_corpus_t *c) {
 }
 
 // The operator chain of a ModifiedVectorSim on the cosine (vk_sim_ops_host.h): host state of the handle, read when a query fills its
-// kernels' parameters.  Contextual corpora refuse a chain: their ~28 clip sites and the bound pass know the clipped cosine only.
+// kernels' parameters.  Contextual corpora refuse a chain HERE, as they always have: vk_corpus_set_contextual_sim_ops is theirs.
 int vk_corpus_set_sim_ops(vk_corpus_t *c, const int32_t *kinds, const float *args, int32_t n_ops) {
 	if (!c || (n_ops > 0 && (!kinds || !args))) return fail(VK_ERR_INVALID, "null argument");
 	int bad = -1;
@@ -560,6 +560,27 @@ int vk_corpus_set_sim_ops(vk_corpus_t *c, const int32_t *kinds, const float *arg
 	}
 	if (n_ops > 0 && c->desc.layout != VK_LAYOUT_STATIC)
 		return fail(VK_ERR_UNSUPPORTED, "similarity operators run over VK_LAYOUT_STATIC only: this corpus is VK_LAYOUT_CONTEXTUAL");
+	vk_host::sim_ops ops{};
+	ops.n = n_ops;
+	for (int i = 0; i < n_ops; i++) { ops.kind[i] = kinds[i]; ops.arg[i] = args[i]; }
+	c->sim_ops = ops;
+	return VK_OK;
+}
+
+// The chain of a VK_LAYOUT_CONTEXTUAL handle: the same host state -- a handle has one layout, so one field serves both --
+// read by the router (route_facts::chained), by the scoring launches (VkScoreParams / VkWideParams) and by every kernel that restates
+// the winners' cells (sim_ops_field).  The cell is vk_host::contextual_cell.
+int vk_corpus_set_contextual_sim_ops(vk_corpus_t *c, const int32_t *kinds, const float *args, int32_t n_ops) {
+	if (!c || (n_ops > 0 && (!kinds || !args))) return fail(VK_ERR_INVALID, "null argument");
+	int bad = -1;
+	if (vk_host::sim_ops_check(kinds, args, n_ops, &bad) != VK_OK) {
+		if (bad < 0) return fail(VK_ERR_INVALID, "vk_corpus_set_contextual_sim_ops: n_ops must be 0 .. VK_MAX_SIM_OPS (8), got " + std::to_string(n_ops));
+		return fail(VK_ERR_INVALID, "vk_corpus_set_contextual_sim_ops: similarity operator " + std::to_string(bad) + ": unknown kind or an argument that is not finite");
+	}
+	if (c->desc.layout != VK_LAYOUT_CONTEXTUAL)
+		return fail(VK_ERR_UNSUPPORTED, "vk_corpus_set_contextual_sim_ops: this corpus is VK_LAYOUT_STATIC -- its chain is set with vk_corpus_set_sim_ops");
+	if (c->span_sim.active())
+		return fail(VK_ERR_UNSUPPORTED, "vk_corpus_set_contextual_sim_ops: this handle is under a span similarity (vk_corpus_set_span_sim), which carries the span index's own chain");
 	vk_host::sim_ops ops{};
 	ops.n = n_ops;
 	for (int i = 0; i < n_ops; i++) { ops.kind[i] = kinds[i]; ops.arg[i] = args[i]; }
@@ -611,6 +632,8 @@ int vk_corpus_set_span_sim(vk_corpus_t *c, int32_t src_kind, float src_arg, cons
 	}
 	if (c->desc.layout != VK_LAYOUT_CONTEXTUAL)
 		return fail(VK_ERR_UNSUPPORTED, "a span similarity is set on a VK_LAYOUT_CONTEXTUAL handle (one row per span): this corpus is VK_LAYOUT_STATIC (vk_corpus_set_sim_source, vk_corpus_set_sim_ops)");
+	if (c->sim_ops.n > 0)
+		return fail(VK_ERR_UNSUPPORTED, "vk_corpus_set_span_sim: this handle is under an operator chain of its token similarities (vk_corpus_set_contextual_sim_ops): clear it first");
 	vk_host::span_sim sim{};
 	sim.src = vk_host::sim_src{src_kind, src_kind == VK_SIMSRC_PNORM ? src_arg : 0.0f};
 	sim.ops.n = n_ops;
@@ -1002,7 +1025,7 @@ int vk_corpus_filter(vk_corpus_t *src, uint64_t pos_mask, uint64_t tag_mask, vk_
 			c->rows_total = c->rows_appended = src->rows_total; c->n_tiles = src->n_tiles;
 			c->d_tiles = src->d_tiles; c->d_mag = src->d_mag; c->shares_vectors = true;
 			c->vectors_of = src->shares_vectors ? src->vectors_of : src->shared;   // the vocabulary stays alive with this handle
-			c->sim_ops = src->sim_ops;   // the source's similarity (a contextual corpus has no chain)
+			c->sim_ops = src->sim_ops;   // the source's similarity
 			c->sim_src = src->sim_src; c->raw_rows = src->raw_rows; c->raw_tile_bytes = src->raw_tile_bytes;   // ... and the unmodified rows it may read
 			c->sim_mix = src->sim_mix;   // ... and its combinator with the operands' rows
 			for (int m = 0; m < VK_MAX_SIM_OPERANDS - 1; m++) c->operands[m] = src->operands[m];
@@ -1017,6 +1040,7 @@ int vk_corpus_filter(vk_corpus_t *src, uint64_t pos_mask, uint64_t tag_mask, vk_
 		} else {
 			int r = vk_corpus_create(&desc, &c);
 			if (r) return r;
+			c->sim_ops = src->sim_ops;   // the source's chain (vk_corpus_set_contextual_sim_ops)
 			VK_HIP(hipStreamSynchronize(c->stream));   // the zero fill of the new tiles
 			VK_HIP(vk_launch_filter_rows(src->d_tiles, c->d_tiles, src_of, n_kept, src->tile_bytes, st));
 			if (src->d_mag && c->d_mag) VK_HIP(vk_launch_filter_gather(src->d_mag, c->d_mag, 4, src_of, n_kept, st));

@@ -111,6 +111,9 @@ struct VkScoreParams {
 	float bound_tail_cost;     // gap_mode 8 / 9: the cost of every gap over more than K slice tokens (vk_host::bound_tail_cost)
 	int32_t bound_compact;     // bound_bits 6: 1 = the compact layout (MODE 9: tile_bytes = VK_DEV_FP6C_TILE_BYTES, bound_live 2); the
 	                           // dispatch reads it, no kernel does (last: the kernels' argument offsets are what they were)
+	vk_host::sim_ops sim_ops;  // contextual layout: the handle's operator chain (vk_corpus_set_contextual_sim_ops), by value; n > 0: the
+	                           // dispatch takes MODE 10 / 11 / 12, whose epilogue is vk_host::contextual_cell -- no other kernel reads it
+	                           // (behind everything else, for the same reason)
 };
 
 struct VkRwmdBatchParams {

@@ -412,7 +412,7 @@ __global__ __launch_bounds__(64) void vk_docw_kernel(VkWideParams p) {
 					float o1[1];
 					const int tok = t_a + mine;
 					if (static_layout) static_sim_canon<1>(p.tiles, p.tile_bytes, p.tok_id[tok], p.qtile, lane, p.d, p.prec, p.q_ids, p.len_t, p.sim_ops, p.sim_src, p.table, p.table_stride, o1);
-					else { sim_canon<1>(p.tiles + (int64_t)(tok >> 4) * p.tile_bytes, tok & 15, p.qtile + (int64_t)blk * p.tile_bytes, v16, p.d, p.prec, o1); o1[0] = clip01(o1[0]); }
+					else { sim_canon<1>(p.tiles + (int64_t)(tok >> 4) * p.tile_bytes, tok & 15, p.qtile + (int64_t)blk * p.tile_bytes, v16, p.d, p.prec, o1); o1[0] = vk_host::contextual_cell(o1[0], blk * 16 + v16 < p.len_t, p.sim_ops); }
 					es = o1[0];
 				}
 			}
@@ -833,7 +833,7 @@ __global__ __launch_bounds__(64) void vk_docg_kernel(VkWideParams p) {
 					float o1[1];
 					const int tok = t_a + mine;
 					if (static_layout) static_sim_canon<1>(p.tiles, p.tile_bytes, p.tok_id[tok], p.qtile, lane, p.d, p.prec, p.q_ids, p.len_t, p.sim_ops, p.sim_src, p.table, p.table_stride, o1);
-					else { sim_canon<1>(p.tiles + (int64_t)(tok >> 4) * p.tile_bytes, tok & 15, p.qtile + (int64_t)(lane >> 4) * p.tile_bytes, lane & 15, p.d, p.prec, o1); o1[0] = clip01(o1[0]); }
+					else { sim_canon<1>(p.tiles + (int64_t)(tok >> 4) * p.tile_bytes, tok & 15, p.qtile + (int64_t)(lane >> 4) * p.tile_bytes, lane & 15, p.d, p.prec, o1); o1[0] = vk_host::contextual_cell(o1[0], lane < p.len_t, p.sim_ops); }
 					es = o1[0];
 				}
 			}

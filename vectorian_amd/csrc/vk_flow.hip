@@ -67,7 +67,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6))) void vk
 		if (!(is_static && p.sim_src))   // (not the cosine: static_cell takes the table's cell)
 			sim_canon16(xrow, p.qtile, p.nk32, p.tail, p.d, PREC, canon, lane, val);
 #pragma unroll
-		for (int r = 0; r < 4; r++) val[r] = is_static ? static_cell(val[r], p.q_ids && p.q_ids[cb + r] == id, cb + r < len_t, p.sim_ops, p.sim_src, p.table, 0, id, cb + r) : clip01(val[r]);   // chain, sim[id(t_j)][j] = 1 (metric/static.cpp:46-67), clip
+		for (int r = 0; r < 4; r++) val[r] = is_static ? static_cell(val[r], p.q_ids && p.q_ids[cb + r] == id, cb + r < len_t, p.sim_ops, p.sim_src, p.table, 0, id, cb + r) : vk_host::contextual_cell(val[r], cb + r < len_t, p.sim_ops);   // chain, sim[id(t_j)][j] = 1 (metric/static.cpp:46-67; contextual: none), clip
 		*reinterpret_cast<float4 *>(S + (ti * 16 + (lane & 15)) * 16 + cb) = make_float4(val[0], val[1], val[2], val[3]);
 		if (p.pos_s) {
 			const int ps = p.pos_s[tok];
@@ -394,7 +394,7 @@ __global__ __launch_bounds__(64) void vk_wide_kernel(VkWideParams p) {
 					const int c0 = qt * 16 + (lane >> 4) * 4;
 #pragma unroll
 					for (int r = 0; r < 4; r++) {
-						val[r] = is_static ? static_cell(val[r], p.q_ids && p.q_ids[c0 + r] == id, c0 + r < len_t, p.sim_ops, p.sim_src, p.table, p.table_stride, id, c0 + r) : clip01(val[r]);
+						val[r] = is_static ? static_cell(val[r], p.q_ids && p.q_ids[c0 + r] == id, c0 + r < len_t, p.sim_ops, p.sim_src, p.table, p.table_stride, id, c0 + r) : vk_host::contextual_cell(val[r], c0 + r < len_t, p.sim_ops);
 						Sx[(lane & 15) * LQ + c0 + r] = val[r];
 						if (p.pos_s) SWx[(lane & 15) * LQ + c0 + r] = tag_weighted(val[r], twl[c0 + r], ps, tposl[c0 + r], p.tw_keep, p.tw_threshold);
 					}

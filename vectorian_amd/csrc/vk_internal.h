@@ -167,8 +167,8 @@ struct vk_corpus_shape {
 	const uint8_t *shadow = nullptr;
 	vk_host::shadow_format shadow_format;
 	float shadow_n = 0.0f, shadow_x = 0.0f;
-	// the operator chain on the cosine (vk_corpus_set_sim_ops; static layout only): a view and a filtered corpus start with their
-	// source's, after that each handle is set on its own
+	// the operator chain on the cosine (static layout: vk_corpus_set_sim_ops; contextual: vk_corpus_set_contextual_sim_ops): a
+	// view and a filtered corpus start with their source's, after that each handle is set on its own
 	vk_host::sim_ops sim_ops{};
 	// the source the chain runs on (vk_corpus_set_sim_source; vk_sim_src_host.h), inherited the same way, and -- under a source that
 	// is not the cosine -- the second, fp32 copy of the UNMODIFIED rows in the fp32 tile layout: n_tiles tiles of raw_tile_bytes.  An
@@ -362,8 +362,10 @@ template <typename P> void corpus_fields(P &p, const vk_corpus *c) {
 }
 // the handle's operator chain into the structs of the kernels that restate cells of the static layout (the others have no such field)
 // (beside it the kind of the handle's source: not the cosine, and those kernels read the table's cells instead)
-template <typename P> auto sim_ops_field(P &p, const vk_corpus *c, int) -> decltype((void)p.sim_ops) { p.sim_ops = c->sim_ops; p.sim_src = c->dev_sim_src(); }
-template <typename P> void sim_ops_field(P &, const vk_corpus *, long) {}
+// (VkScoreParams has the chain alone -- a contextual handle's, DESIGN 19: no source to go with it)
+template <typename P> auto sim_ops_field(P &p, const vk_corpus *c, int) -> decltype((void)p.sim_ops, (void)p.sim_src) { p.sim_ops = c->sim_ops; p.sim_src = c->dev_sim_src(); }
+template <typename P> auto sim_ops_field(P &p, const vk_corpus *c, long) -> decltype((void)p.sim_ops) { p.sim_ops = c->sim_ops; }
+template <typename P> void sim_ops_field(P &, const vk_corpus *, ...) {}
 // ... and those of the structs that serve both layouts and both precisions (d_tok_id is null unless the layout is static)
 template <typename P> void corpus_fields_ids(P &p, const vk_corpus *c) {
 	corpus_fields(p, c);

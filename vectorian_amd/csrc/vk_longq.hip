@@ -90,7 +90,7 @@ __global__ __launch_bounds__(64) void vk_longq_kernel(VkLongqParams p) {
 					const int c0 = 16 * b + (lane >> 4) * 4;
 #pragma unroll
 					for (int r = 0; r < 4; r++) {
-						float x = is_static ? static_cell(val[r], p.q_ids && p.q_ids[c0 + r] == id, c0 + r < p.len_t, p.sim_ops, p.sim_src, p.table, p.table_stride, id, c0 + r) : clip01(val[r]);   // chain, sim[id(t_j)][j] = 1 (metric/static.cpp:46-67), clip
+						float x = is_static ? static_cell(val[r], p.q_ids && p.q_ids[c0 + r] == id, c0 + r < p.len_t, p.sim_ops, p.sim_src, p.table, p.table_stride, id, c0 + r) : vk_host::contextual_cell(val[r], c0 + r < p.len_t, p.sim_ops);   // chain, sim[id(t_j)][j] = 1 (metric/static.cpp:46-67), clip
 						if (p.pos_s) {
 							if (rel < len_s && c0 + r < LT) Su[(c0 + r) * 64 + rel] = x;
 							x = tag_weighted(x, p.tw[c0 + r], ps, p.tpos[c0 + r], p.tw_keep, p.tw_threshold);

@@ -20,6 +20,7 @@ static vk_host::route_facts route_facts_of(const vk_corpus *c, const vk_query_de
 	f.has_apart = c->h_apart && !c->h_apart->empty(); f.has_xlong = c->h_xlong && !c->h_xlong->empty();
 	f.max_pair_tiles = c->max_pair_tiles; f.max_short_pair_tiles = c->max_short_pair_tiles; f.uniform_len = c->uniform_len;
 	f.has_pos = c->d_pos != nullptr; f.has_tags = c->d_tag != nullptr; f.n_sentences = c->desc.n_sentences;
+	f.chained = c->desc.layout == VK_LAYOUT_CONTEXTUAL && c->sim_ops.n > 0;   // vk_corpus_set_contextual_sim_ops
 	f.algorithm = q->algorithm; f.wmd_full = q->wmd_full != 0; f.rwmd_injective = q->rwmd_injective != 0; f.len_t = q->len_t;
 	if (q->algorithm == VK_ALG_ALIGN) {
 		f.gaps = vk_host::classify_gaps(q->gap_s, q->gap_t);
@@ -56,6 +57,10 @@ int vk_validate_query(const vk_corpus *c, const vk_query_desc *q, const vk_topk_
 	if (q->len_t > VK_MAX_QUERY_LEN) {
 		// 65 .. 512 tokens: the role-swapped one-wave-per-slice kernel (vk_longq_kernel) -- alignments over slices of at most
 		// VK_MAX_SENT_LEN tokens (those of more than 64: its block form)
+		if (c->desc.layout == VK_LAYOUT_CONTEXTUAL && c->sim_ops.n > 0) {   // under an operator chain: the router's refusal, by name
+			const vk_host::query_route r = vk_host::route_query(route_facts_of(c, q, out), vk_host::route_switches{}, kRouteFits);
+			return fail(r.status, r.message);
+		}
 		if (q->algorithm != VK_ALG_ALIGN) return fail(VK_ERR_UNSUPPORTED, "queries of more than VK_MAX_QUERY_LEN (64) tokens: alignments only (the transports keep a lane per query token)");
 		if (c->max_len > VK_MAX_SENT_LEN) return fail(VK_ERR_UNSUPPORTED, "queries of more than 64 tokens over a corpus that holds a slice of more than VK_MAX_SENT_LEN (512) tokens: the state of such a slice does not fit a workgroup's LDS");
 		if (q->submatch_weight != 0.0f) return fail(VK_ERR_UNSUPPORTED, "queries of more than 64 tokens with a submatch weight");
@@ -63,8 +68,9 @@ int vk_validate_query(const vk_corpus *c, const vk_query_desc *q, const vk_topk_
 		if (q->max_matches > VK_MAX_MATCHES) return fail(VK_ERR_UNSUPPORTED, "queries of more than 64 tokens: max_matches <= VK_MAX_MATCHES");
 	}
 	if (q->len_t <= VK_MAX_QUERY_LEN) {   // (the switches a refusal reads: none)
-		const vk_host::query_route r = vk_host::route_query(route_facts_of(c, q, out), vk_host::route_switches{}, kRouteFits);
-		if (r.status != VK_OK && !r.fits32) return fail(r.status, r.message);
+		const vk_host::route_facts facts = route_facts_of(c, q, out);
+		const vk_host::query_route r = vk_host::route_query(facts, vk_host::route_switches{}, kRouteFits);
+		if (r.status != VK_OK && (!r.fits32 || facts.chained)) return fail(r.status, r.message);   // (under an operator chain: every refusal of the route)
 	}
 	// Slices of more than VK_MAX_SENT_LEN tokens (whole documents as slices, up to VK_MAX_DOC_LEN): alignments -- the
 	// one-wave-per-slice kernel with the slice's state in global memory (vk_wide_kernel, global-state form; the same form takes a
@@ -329,7 +335,7 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	const vk_host::route_switches sw = vk_host::read_route_switches();
 	vk_host::route_facts facts = route_facts_of(c, q, out);
 	const int bound_mode = bound_pass_mode();
-	facts.bound_pass = c->shadow && bound_mode >= 0 && (bound_mode > 0 || c->desc.n_sentences >= kBoundPassMinSentences) && vk_host::bound_pass_takes(facts) &&
+	facts.bound_pass = !facts.chained && c->shadow && bound_mode >= 0 && (bound_mode > 0 || c->desc.n_sentences >= kBoundPassMinSentences) && vk_host::bound_pass_takes(facts) &&
 		(bound_mode != 0 || c->bp.backoff.take());
 	const vk_host::query_route r = vk_host::route_query(facts, sw, kRouteFits);
 	if (r.status != VK_OK) return fail(r.status, r.message);
@@ -668,15 +674,17 @@ static int query_body(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, 
 	// leave 32, and the traceback kernel of the previous query has to wait until this kernel has drained (2.3 - 2.8 ms); with
 	// the query tile in LDS the kernel takes 136 and runs at the same speed, the neighbours beside it.
 	// Linear / affine gaps take 112 registers in the register form.  VK_QREG=1 / VK_QLDS=1 force one or the other.
+	// Under an operator chain every width takes the generic tile form (MODE 10 / 11 / 12): no specialised query tile
 	const bool reg_history = p.gap_mode == 3 || p.gap_mode == 6;
-	if (!is_static && c->prec == 0 && c->nk32 == 10 && c->tail == 1)
+	const bool chained = facts.chained;
+	if (!chained && !is_static && c->prec == 0 && c->nk32 == 10 && c->tail == 1)
 		p.q_mode3 = sw.qlds ? 1 : sw.qreg ? 0 : (reg_history ? 1 : 0);
-	if (!is_static && c->prec == 1 && c->nk32 == 19 && !sw.no_f32_special) p.q_mode3 = 1;   // fp32 rows at 300-d: MODE 4 (all 19 blocks of a tile in flight)
-	const size_t qlds = (!is_static && ((c->prec == 0 && c->nk32 == 24 && c->tail == 0) || p.q_mode3)) ? (size_t)c->nk32 * 1024 : 0;   // MODE 3 / 4: query tile in LDS
+	if (!chained && !is_static && c->prec == 1 && c->nk32 == 19 && !sw.no_f32_special) p.q_mode3 = 1;   // fp32 rows at 300-d: MODE 4 (all 19 blocks of a tile in flight)
+	const size_t qlds = (!chained && !is_static && ((c->prec == 0 && c->nk32 == 24 && c->tail == 0) || p.q_mode3)) ? (size_t)c->nk32 * 1024 : 0;   // MODE 3 / 4: query tile in LDS
 	smem += qlds;
 	// the generic contextual kernel (MODE 1: fp32 tiles, or a d without a specialised form) stages the query tile in LDS when it fits
 	// beside the strips of at least two workgroups per CU
-	if (!is_static && qlds == 0 && !(c->prec == 0 && c->nk32 == 10 && c->tail == 1)) {
+	if (!is_static && qlds == 0 && (chained || !(c->prec == 0 && c->nk32 == 10 && c->tail == 1))) {
 		const size_t qb = ((size_t)c->tile_bytes + 1023) / 1024 * 1024;
 		if (2 * (smem + qb) <= 160 * 1024 && !sw.no_qlds1) { p.q_lds = (int32_t)qb; smem += qb; }
 	}
@@ -1073,7 +1081,7 @@ int vk_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out) {
 	const int rc = vk_validate_query(c, q, out);
 	if (rc) return rc;
 	if (q->abort && *q->abort) { out->n_out = 0; return fail(VK_ERR_ABORTED, "query aborted by the caller"); }
-	// Under an operator chain (vk_corpus_set_sim_ops) the winners of an alignment are restated in the canonical arithmetic whether
+	// Under an operator chain (vk_corpus_set_sim_ops, vk_corpus_set_contextual_sim_ops) the winners of an alignment are restated in the canonical arithmetic whether
 	// or not the caller wants their tracebacks: an operator such as THRESHOLD makes a score discontinuous in its cells, so the sums of
 	// the scoring pass (matrix pipe order) state no score to within a rounding error as they do for the plain cosine.  The query runs
 	// with tracebacks into arrays of its own; the caller's mapping / edge_sim stay untouched, as without a chain.

@@ -30,6 +30,9 @@ struct route_facts {
 	bool submatch = false, tagged = false, has_q_tags = false, has_q_ids = false, only = false, want_flow = false;
 	int locality = VK_LOCAL, kk = 0;
 	bool sim_rows = false, raw_score = false, boost = false;
+	// a contextual handle under an operator chain (vk_corpus_set_contextual_sim_ops): only vk_score_kernel and
+	// vk_score32_kernel have the chain in their epilogue -- no bound pass, no span kernel, and every other scoring pass is refused
+	bool chained = false;
 };
 
 // From which k on the table w_s is constant up to the corpus's longest slice (a saturated table; 0: no such tail, or no table)
@@ -107,8 +110,21 @@ inline bool bound_pass_takes(const route_facts &f) {
 	return f.algorithm == VK_ALG_ALIGN && f.len_t <= VK_FAST_QUERY_LEN && !f.submatch && !f.tagged && !f.only && f.n_long_groups == 0 && f.max_len <= VK_FAST_SENT_LEN;
 }
 
+// The refusals of a contextual handle under an operator chain: the chain and the case, by name
+constexpr const char *kChainedLongSlices = "an operator chain on a contextual handle (vk_corpus_set_contextual_sim_ops) over a corpus that holds a slice of more than 64 tokens: "
+	"the doc / docw / docg / wide / longq scoring kernels know the clipped cosine only (vk_score_kernel and vk_score32_kernel run the chain)";
+constexpr const char *kChainedLongQuery = "an operator chain on a contextual handle (vk_corpus_set_contextual_sim_ops) under a query of more than 64 tokens: "
+	"the doc / docw / docg / wide / longq scoring kernels know the clipped cosine only (vk_score_kernel and vk_score32_kernel run the chain)";
+constexpr const char *kChainedWideQuery = "an operator chain on a contextual handle (vk_corpus_set_contextual_sim_ops) under a query of 17 .. 64 tokens that the multi-block kernel "
+	"does not take (rows too wide for its LDS, affine gaps with a_t < 0, VK_NO_SCORE32): the doc / docw / docg / wide / longq scoring kernels know the clipped cosine only";
+
 inline query_route route_query(const route_facts &f, const route_switches &sw, const route_fits &fits) {
 	query_route r;
+	if (f.chained && f.len_t > VK_MAX_QUERY_LEN) {   // (vk_longq_kernel: asked by vk_validate_query, which routes no other query this long)
+		r.status = VK_ERR_UNSUPPORTED;
+		r.message = kChainedLongQuery;
+		return r;
+	}
 	const bool align = f.algorithm == VK_ALG_ALIGN, rwmd = f.algorithm == VK_ALG_RWMD;
 	const bool exact = exact_transport(f.algorithm, f.wmd_full);
 	const bool relaxed_11 = rwmd && !f.wmd_full && f.rwmd_injective;   // a stream of row / column minima
@@ -152,6 +168,12 @@ inline query_route route_query(const route_facts &f, const route_switches &sw, c
 	// (affine gaps: the prefix-scan form of F needs open_t >= extend_t)
 	const bool multi_block = wide_query && fits32 && (skips_long || (!has_mid && f.max_len <= VK_FAST_SENT_LEN)) && (apart || !xlong) &&
 		(!align || base != 1 || f.gaps.a_t >= 0.0f) && (exact || fill || !sw.no_score32);
+	// a contextual handle under an operator chain: every scoring pass is vk_score_kernel or vk_score32_kernel, or the query is refused
+	if (f.chained && (has_mid || xlong || (wide_query && !multi_block))) {
+		r.status = VK_ERR_UNSUPPORTED;
+		r.message = (has_mid || xlong) ? kChainedLongSlices : kChainedWideQuery;
+		return r;
+	}
 	// exact transport and the 1:n RWMD have no other kernel for such queries: refused before anything is enqueued.  (Over a finalized
 	// corpus whose long slices vk_validate_query has admitted, the kernel is ruled out by its LDS demand alone: fits32 is false.)
 	if (wide_query && (exact || fill) && !multi_block) {
@@ -162,7 +184,8 @@ inline query_route route_query(const route_facts &f, const route_switches &sw, c
 	}
 
 	// ---- the scoring plan and the pass of each class of slices
-	const bool span = !wide_query && align && !is_static && f.len_t == 1 && f.uniform_len == 1 && f.locality == VK_LOCAL && !f.tagged;
+	// (under a chain the score of a one-token slice is no clipped cosine: the fused kernel; nor does the shadow bound a chain's output)
+	const bool span = !f.chained && !wide_query && align && !is_static && f.len_t == 1 && f.uniform_len == 1 && f.locality == VK_LOCAL && !f.tagged;
 	const route_pass wide_pass = docw ? PASS_DOCW : docg ? PASS_DOCG : PASS_WIDE, doc_pass = doc ? PASS_DOC : PASS_WIDE;
 	if (f.only) r.plan = PLAN_LISTED;
 	else if (wide_query) {
@@ -181,7 +204,7 @@ inline query_route route_query(const route_facts &f, const route_switches &sw, c
 		r.plan = PLAN_SPAN;
 		r.pass[CLASS_SHORT] = PASS_SPAN;
 	} else {
-		r.plan = (f.bound_pass && bound_pass_takes(f) && f.kk <= VK_MAX_MATCHES) ? PLAN_BOUNDED : PLAN_FUSED;
+		r.plan = (!f.chained && f.bound_pass && bound_pass_takes(f) && f.kk <= VK_MAX_MATCHES) ? PLAN_BOUNDED : PLAN_FUSED;
 		r.pass[CLASS_SHORT] = PASS_FUSED;
 		r.pass[CLASS_MID] = (mid_via_list || rwmd_mid_via_list) ? doc_pass : PASS_FUSED_LONG;
 		r.pass[CLASS_XLONG] = doc_pass;

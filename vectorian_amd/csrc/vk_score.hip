@@ -12,6 +12,9 @@ extern "C" hipError_t vk_launch_score_m7(const VkScoreParams *p, int32_t grid, s
 extern "C" hipError_t vk_launch_score_m8(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
 extern "C" hipError_t vk_launch_score_m9(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
 extern "C" hipError_t vk_launch_score_m4(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
+extern "C" hipError_t vk_launch_score_m10(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
+extern "C" hipError_t vk_launch_score_m11(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
+extern "C" hipError_t vk_launch_score_m12(const VkScoreParams *p, int32_t grid, size_t smem_bytes, hipStream_t stream);
 
 extern "C" hipError_t vk_launch_score(const VkScoreParams *pp, int32_t grid, size_t smem_bytes, hipStream_t stream) {
 	const VkScoreParams &p = *pp;
@@ -19,6 +22,8 @@ extern "C" hipError_t vk_launch_score(const VkScoreParams *pp, int32_t grid, siz
 	if (p.bound_bits == 6) return vk_launch_score_m8(pp, grid, smem_bytes, stream);   // ... over the 6-bit shadow
 	if (p.bound_bits == 8) return vk_launch_score_m7(pp, grid, smem_bytes, stream);   // the bound pass over the 8-bit shadow
 	if (p.layout == VK_DEV_LAYOUT_STATIC) return vk_launch_score_m2(pp, grid, smem_bytes, stream);
+	// a contextual handle under an operator chain: the generic tile form at every width, the chain in its epilogue
+	if (p.sim_ops.n > 0) return p.prec == 1 ? vk_launch_score_m12(pp, grid, smem_bytes, stream) : p.nk32 >= 8 ? vk_launch_score_m11(pp, grid, smem_bytes, stream) : vk_launch_score_m10(pp, grid, smem_bytes, stream);
 	if (p.prec == 0 && p.nk32 == 10 && p.tail == 1) return p.q_mode3 ? vk_launch_score_m3_300(pp, grid, smem_bytes, stream) : vk_launch_score_m0(pp, grid, smem_bytes, stream);
 	if (p.prec == 0 && p.nk32 == 24 && p.tail == 0) return vk_launch_score_m3(pp, grid, smem_bytes, stream);
 	if (p.prec == 1 && p.nk32 == 19 && p.q_mode3) return vk_launch_score_m4(pp, grid, smem_bytes, stream);   // fp32 rows, 300-d

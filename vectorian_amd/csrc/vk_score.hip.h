@@ -19,6 +19,9 @@
 //           the cosine MODE 0 / 3 compute, so the score is an upper bound of theirs (the bound pass)
 //   MODE 8: the 6-bit (E2M3) shadow, three K-steps of 128 features (NK32 = 3): as MODE 7, the product on the scaled fp6 MFMA
 //   MODE 9: MODE 8 over the compact 6-bit shadow (3,712-byte tiles): the tile's loads differ, nothing else does
+//   MODE 10 / 11 / 12: MODE 1 / 5 / 6 of a contextual handle under an operator chain (vk_corpus_set_contextual_sim_ops): a
+//           cell is vk_host::contextual_cell -- the chain on the unclipped cosine, zeros on the columns past the query, the clip.  Every
+//           width takes these (the 300-d and 768-d forms of MODE 0 / 3 / 4 know the clipped cosine only)
 // GAP: 0 linear, 1 affine, 2 general (LDS history, serial in-row chain),
 //      3 general, sentences <= 32 tokens, strictly subadditive w_t (register history),
 //      4 relaxed word mover's distance (no DP: row / column minima of 1 - S),
@@ -85,7 +88,8 @@ static hipError_t launch_sized(K kernel, const VkScoreParams &p, int want_blocks
 	// (ragged 8..64 tokens, 400 k sentences: 3.37 ms at 1, 3.45 ms at 2 per CU)
 	// -- the 768-d specialisation only: the generic kernel at 1024-d loses 20 % (32 tokens) to 38 % (ragged) with one group
 	// per CU (tools/sweep_dims.py)
-	if (p.nk32 == 24 && p.tail == 0 && p.prec == 0 && p.layout != VK_DEV_LAYOUT_STATIC && !bound_pass) occ = 1;
+	// (nor under an operator chain, which runs 768-d rows on the generic form: MODE 11)
+	if (p.nk32 == 24 && p.tail == 0 && p.prec == 0 && p.layout != VK_DEV_LAYOUT_STATIC && !bound_pass && p.sim_ops.n == 0) occ = 1;
 	if (residency > 0) occ = residency < real_occ ? residency : real_occ;
 	const char *ov = getenv("VK_BLOCKS_PER_CU");   // read per launch: tools/sweep_dims.py varies it inside one process
 	if (ov && atoi(ov) > 0) occ = atoi(ov) < real_occ ? atoi(ov) : real_occ;

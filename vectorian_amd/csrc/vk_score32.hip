@@ -465,7 +465,9 @@ __device__ __forceinline__ float dp32_general(const float *__restrict__ S, int s
 // NWMAX: waves per workgroup the kernel may be launched with.  12 (round 4; the three-block balance of 33..48-token queries over slices
 // of at most 32 tokens takes 165 registers): ONE workgroup of twelve waves per CU shares the query tiles -- three waves per SIMD where
 // two workgroups of four left two (the LDS of a CU holds the 39 KB of query tiles twice, not three times)
-template <int GAP, bool STATIC, int NB, bool B3 = false, int NWMAX = 4>
+// CHAIN (contextual forms only): the handle's operator chain (vk_corpus_set_contextual_sim_ops) -- a cell is
+// vk_host::contextual_cell, not the clipped cosine
+template <int GAP, bool STATIC, int NB, bool B3 = false, int NWMAX = 4, bool CHAIN = false>
 __global__ __launch_bounds__(64 * NWMAX) __attribute__((amdgpu_waves_per_eu(NWMAX > 4 ? 3 : 2))) void vk_score32_kernel(VkWideParams p, int32_t rows_per_wave, int32_t stride, int32_t slack) {
 	constexpr int LPS = 16 * NB, PER = 64 / LPS;   // lanes per slice, slices per wave
 	extern __shared__ float4 vk_smem32[];
@@ -632,7 +634,8 @@ __global__ __launch_bounds__(64 * NWMAX) __attribute__((amdgpu_waves_per_eu(NWMA
 			for (int b = 0; b < NB; b++) {
 #pragma unroll
 				for (int r = 0; r < 4; r++) {
-					acc[b][r] = clip01(acc[b][r]);
+					if constexpr (CHAIN) acc[b][r] = vk_host::contextual_cell(acc[b][r], 16 * b + cq + r < p.len_t, p.sim_ops);   // the chain, zeros past the query, the clip
+					else acc[b][r] = clip01(acc[b][r]);
 					if (p.pos_s) acc[b][r] = tag_weighted(acc[b][r], p.tw[16 * b + cq + r], ps, p.tpos[16 * b + cq + r], p.tw_keep, p.tw_threshold);
 				}
 				if (16 * b + cq < stride) *reinterpret_cast<f32x4 *>(row + 16 * b) = acc[b];
@@ -775,6 +778,20 @@ extern "C" hipError_t vk_launch_score32(const VkWideParams *p, int32_t tiles, hi
 	const bool twelve = four && p->gap_mode == 3 && p->len_t <= 48 && !is_static && waves == 4 && !getenv("VK_NO_TWELVE") &&
 		vk_score32_lds_bytes(p->nk32, p->tail, tiles, p->len_t, p->gap_mode, 12) <= 156 * 1024;
 	if (twelve) { waves = 12; smem = vk_score32_lds_bytes(p->nk32, p->tail, tiles, p->len_t, p->gap_mode, 12); }
+	// a contextual handle under an operator chain: the same forms with the chain in their epilogue (static handles read a finished table)
+	if (!is_static && p->sim_ops.n > 0)
+	switch (p->gap_mode) {
+	case 0: kernel = four ? vk_score32_kernel<0, false, 4, false, 4, true> : vk_score32_kernel<0, false, 2, false, 4, true>; break;
+	case 1: kernel = four ? vk_score32_kernel<1, false, 4, false, 4, true> : vk_score32_kernel<1, false, 2, false, 4, true>; break;
+	case 4: kernel = four ? vk_score32_kernel<4, false, 4, false, 4, true> : vk_score32_kernel<4, false, 2, false, 4, true>; break;
+	case 7: kernel = four ? vk_score32_kernel<7, false, 4, false, 4, true> : vk_score32_kernel<7, false, 2, false, 4, true>; break;
+	case 5: kernel = four ? vk_score32_kernel<5, false, 4, false, 4, true> : vk_score32_kernel<5, false, 2, false, 4, true>; break;
+	case 3: kernel = twelve ? vk_score32_kernel<3, false, 4, true, 12, true> : four ? (p->len_t <= 48 ? vk_score32_kernel<3, false, 4, true, 4, true> : vk_score32_kernel<3, false, 4, false, 4, true>)
+		: bal2 ? vk_score32_kernel<3, false, 2, true, 4, true> : vk_score32_kernel<3, false, 2, false, 4, true>; break;
+	default: kernel = four ? (p->len_t <= 48 ? vk_score32_kernel<6, false, 4, true, 4, true> : vk_score32_kernel<6, false, 4, false, 4, true>)
+		: bal2 ? vk_score32_kernel<6, false, 2, true, 4, true> : vk_score32_kernel<6, false, 2, false, 4, true>; break;
+	}
+	else
 	switch (p->gap_mode) {
 	case 0: kernel = four ? (is_static ? vk_score32_kernel<0, true, 4> : vk_score32_kernel<0, false, 4>)
 		: (is_static ? vk_score32_kernel<0, true, 2> : vk_score32_kernel<0, false, 2>); break;

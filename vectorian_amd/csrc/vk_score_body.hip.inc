@@ -5,6 +5,8 @@
 //   FULL_LQ                     0: vk_score_kernel.  > 0 (GAP 8 only): local alignment and a query of FULL_LQ tokens -- a group of four
 //                               slices of exactly 32 tokens takes the straight-line DP, every other group the general form with the
 //                               locality and the column count at compile time (DESIGN 11.12)
+// MODE 10 / 11 / 12 (vk_score_m10.hip ..): MODE 1 / 5 / 6 of a contextual handle under an operator chain (DESIGN 19) -- the tile
+// product without its clip, then vk_host::contextual_cell: the chain, zeros on the columns past the query, the clip.
 // Text and not a __forceinline__ device template on purpose: the compiler simplifies a device function on its own before it inlines
 // it, and every kernel of vk_score_m0 .. m9*.hip then came out with another instruction stream (hundreds of instructions apart in
 // vk_score_m2, m3 and m8; DESIGN 11.12).  Included, the kernels that were there compile to what they were, byte for byte.
@@ -38,7 +40,8 @@
 	}
 	// MODE 1 (any d, fp32 tiles): the same staging with a runtime size; the K loop then reads the query with ds_read instead of
 	// going through L1 for every token tile
-	if constexpr (MODE == 1 || MODE == 5 || MODE == 6) {
+	constexpr bool CHAIN = MODE == 10 || MODE == 11 || MODE == 12;
+	if constexpr (MODE == 1 || MODE == 5 || MODE == 6 || CHAIN) {
 		if (p.q_lds > 0) {
 			for (int i = threadIdx.x; i * 16 < p.q_lds; i += blockDim.x)
 				vk_smem4[i] = i * 16 < p.tile_bytes ? *reinterpret_cast<const float4 *>(p.qtile + i * 16) : float4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -192,6 +195,15 @@
 				else if constexpr (MODE == 3) acc = sim_tile_qlds<NK32, TAIL>(qlds, tp, lane);
 				else if constexpr (MODE == 4) acc = sim_tile_f32_qlds<NK32>(qlds, tp, lane);
 				else if constexpr (MODE == 7) acc = sim_tile_i8<NK32>(qlds, tp, lane, p.bound_live);
+				else if constexpr (CHAIN) {
+					constexpr bool DEEP = MODE == 11 || MODE == 12;
+					constexpr int PREC = MODE == 12 ? 1 : 0;
+					if (p.q_lds > 0) acc = sim_tile_generic<DEEP, PREC, false>(qlds, tp, p.nk32, p.tail, lane);
+					else acc = sim_tile_generic<DEEP, PREC, false>(p.qtile, tp, p.nk32, p.tail, lane);
+					// lane l holds query columns 4 (l >> 4) .. + 3: the chain on those the query holds, zeros behind them, the clip
+#pragma unroll
+					for (int r = 0; r < 4; r++) acc[r] = vk_host::contextual_cell(acc[r], (lane >> 4) * 4 + r < p.len_t, p.sim_ops);
+				}
 				else {
 					// two calls, not one with a selected pointer: an LDS-or-global pointer is a flat pointer, and flat loads count
 					// on both wait counters -- every batch of tile loads would be waited for in full

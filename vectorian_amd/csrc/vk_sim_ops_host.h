@@ -70,6 +70,17 @@ VK_HOST_DEVICE inline float sim_ops_apply(float x, const sim_ops &ops) {
 	return x;
 }
 
+// One similarity cell of a VK_LAYOUT_CONTEXTUAL handle (vk_corpus_set_contextual_sim_ops; metric/contextual.cpp:40-56: the VectorSim
+// on the token vectors, then the clip): clip01(chain(cosine)) on the columns the query holds, 0 on the padding behind them -- the
+// chain of a zero cosine is no zero ((x + 1) / 2: 0.5), and the DPs' and the relaxed transports' maxima count on zeros there.  No
+// sim[id(t_j)][j] = 1 rewrite: that is metric/static.cpp's alone.  n = 0: the clipped cosine, bit for bit, whatever in_query says.
+// The scoring epilogues (vk_score_body.hip.inc, vk_score32.hip), the restatement of the winners' cells and
+// tests/test_contextual_cell_host.py all state the cell through this function.
+VK_HOST_DEVICE inline float contextual_cell(float cosine, bool in_query, const sim_ops &ops) {
+	if (ops.n > 0) cosine = in_query ? sim_ops_apply(cosine, ops) : 0.0f;
+	return fminf(fmaxf(cosine, 0.0f), 1.0f);   // clip01 (vk_common.hip.h): xt::clip(sim, 0, 1), NaN -> 0
+}
+
 } // namespace vk_host
 
 #endif

@@ -143,6 +143,16 @@ class Corpus:
 		args = np.ascontiguousarray([a for _, a in pairs], dtype=np.float32)
 		_core._check(_core.lib().vk_corpus_set_sim_ops(self._h, _core._np_ptr(kinds), _core._np_ptr(args), len(pairs)))
 
+	def set_contextual_sim_ops(self, ops):
+		"""the operator chain on the cosine of a contextual handle (vk_corpus_set_contextual_sim_ops): ops as set_sim_ops takes them;
+		empty clears it.  A cell is clip(chain(cosine)), with no rewrite of a query token's own cell; the handle then answers queries of
+		at most 64 tokens over slices of at most 64 tokens.  Views and filtered corpora made afterwards inherit it."""
+		pairs = [tuple(op.sim_op) if hasattr(op, "sim_op") else tuple(op) for op in ops]
+		kinds = np.ascontiguousarray([int(k) for k, _ in pairs], dtype=np.int32)
+		args = np.ascontiguousarray([a for _, a in pairs], dtype=np.float32)
+		with self.lock:
+			_core._check(_core.lib().vk_corpus_set_contextual_sim_ops(self._h, _core._np_ptr(kinds), _core._np_ptr(args), len(pairs)))
+
 	def set_sim_source(self, kind, arg=0.0):
 		"""the VectorSim the chain runs on (vk_corpus_set_sim_source): core.VK_SIMSRC_* and its argument (p of the p-norm).  A source
 		beside the cosine reads the unmodified rows, so it is set BEFORE append_vectors; static layout only."""

@@ -219,6 +219,13 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 				if b > a:
 					self._corpus.append_vectors(Vectors(doc.contextual_vectors(emb.name)).unmodified[a - doc_base:b - doc_base], normalize=True)
 				doc_base += doc.n_tokens
+			if self._sim_ops:
+				# the chain on the cosine of the token vectors, state of the handle as on a static index: views and filtered
+				# corpora inherit it, every rank of a sharded index sets it on its own handle
+				if not hasattr(self._corpus, "set_contextual_sim_ops"):   # a capability of the backend: core.Corpus has it
+					self._corpus.close()
+					raise NotImplementedError(self._contextual_chain_refusal(first.similarity, emb))
+				self._corpus.set_contextual_sim_ops(self._sim_ops)
 		else:
 			raise TypeError(emb)
 		self._has_pos = all(doc.pos is not None for doc in session.documents) and len(session.documents) > 0
@@ -256,8 +263,8 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 	def _operator_chain(similarity, embedding):
 		"""(source, chain) of the vector similarity: the source's (kind, float32 arg) of vk_corpus_set_sim_source -- None for
 		CosineSim -- and the (kind, float32 arg) pairs of the operator chain, empty without one; or the reason this similarity does
-		not run here.  embedding: the token embedding the similarity runs over (sources and chains: static ones
-		only), or None for the vectors of a span index, which are nobody's tokens"""
+		not run here.  embedding: the token embedding the similarity runs over (sources: static ones only; a chain
+		on the cosine of a contextual one: DESIGN 19), or None for the vectors of a span index, which are nobody's tokens"""
 		if isinstance(similarity, CosineSim):
 			return None, []
 		over = "" if embedding is None else " (over contextual embeddings CosineSim only)"
@@ -273,9 +280,8 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 				f"{similarity.name}: the HIP path modifies CosineSim, PNormDistance and ImprovedSqrtCosineSim{over}, not {source.name}")
 		if len(operators) > core.VK_MAX_SIM_OPS:
 			raise NotImplementedError(f"{similarity.name}: {len(operators)} operators; the HIP path takes at most {core.VK_MAX_SIM_OPS}")
-		if embedding is not None and not embedding.is_static:
-			raise NotImplementedError(f"{similarity.name}: operators on the cosine run over static embeddings only; "
-				f"{embedding.name} is contextual")
+		# (a contextual embedding: a source beside the cosine was refused by _source_of; a chain on the cosine is the backend's to take or
+		# to refuse -- __init__ asks it for set_contextual_sim_ops)
 		ops = []
 		for op in operators:
 			try:
@@ -284,6 +290,11 @@ class HipBruteForceIndex(LanesMixin, ShardExchangeMixin, DebugHookMixin, Index):
 				raise NotImplementedError(f"{type(op).__name__}: not an operator of vectorian_amd.kernel (the device runs those six)") from None
 			ops.append((int(kind), np.float32(arg)))
 		return src, ops
+
+	@staticmethod
+	def _contextual_chain_refusal(similarity, embedding):
+		return (f"{similarity.name}: operators on the cosine run over static embeddings only on this backend "
+			f"(it has no set_contextual_sim_ops); {embedding.name} is contextual")
 
 	@staticmethod
 	def _token_sim_mix(token_sim, optimizer):
