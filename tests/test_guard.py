@@ -30,12 +30,18 @@ def test_entry_points_run_their_bodies_under_the_guard():
 	hipMemcpyAsync is a plain local any more"""
 	import re
 	csrc = os.path.join(ROOT, "vectorian_amd", "csrc")
-	for name, body in (("vk_query.cpp", "query_body"), ("vk_batch.cpp", "query_batch_body")):
-		text = open(os.path.join(csrc, name)).read()
-		assert f"vk_run_guarded([&](vk_host_keep &keep) {{ return {body}(" in text
+	# (the helpers both units share -- the fetch of a selection, the listed slices' keys, the gather of the winners' aligner scores:
+	# vk_internal.h -- are held to the same rule; they bind no caller's array)
+	shared = open(os.path.join(csrc, "vk_internal.h")).read()
+	shared = shared[shared.index("int upload_listed_keys("):shared.index("int launch_wrd_exact_both(")]
+	assert shared.count("hipMemcpyAsync(") == 7
+	for name, body in (("vk_query.cpp", "query_body"), ("vk_batch.cpp", "query_batch_body"), ("vk_internal.h", None)):
+		text = open(os.path.join(csrc, name)).read() if body else shared
+		assert not body or f"vk_run_guarded([&](vk_host_keep &keep) {{ return {body}(" in text
 		# every host pointer of an asynchronous copy is a caller's array (out-> / q-> / qs[ / packed16), pinned library memory
-		# (c->h_brows) or comes from the keep (a reference / pointer bound by keep.vec / keep.array)
-		kept = set(re.findall(r"[&*](\w+) = \*?keep\.(?:vec|array)<", text))
+		# (c->h_brows) or comes from the keep (a reference / pointer bound by keep.vec / keep.array; a member of a struct bound by
+		# its constructor's initialiser, `name(keep.vec<`)
+		kept = set(re.findall(r"[&*](\w+) = \*?keep\.(?:vec|array)<", text)) | set(re.findall(r"\b(\w+)\(keep\.(?:vec|array)<", text))
 		for m in re.finditer(r"hipMemcpy(?:2D)?Async\(([^;]*);", text):
 			args = m.group(1)
 			host = [a.strip() for a in args.split(",")]

@@ -94,9 +94,18 @@ def test_the_query_unit_decides_no_route_of_its_own():
 	for gone in ("long_via_wide", "wide_score", "rwmd_long_doc", "doc_fast", "flow_doc", "docg_ok", "doc_ok", "rwmd_inj", "long_apart", "docw_rwmd",
 			"apart_route", "two_blocks", "wide_sub", "score32_plan", "Score32Plan", "transport_in_lds"):
 		assert not re.search(r"\b%s\b" % gone, text), gone
-	body = text[text.index("static int query_body("):text.index('extern "C" {')]
+	# the query's path: the context, its stages and query_body
+	body = text[text.index("struct query_run {"):text.index('extern "C" {')]
+	assert "static int query_body(" in body
 	assert body.count("vk_host::route_query(") == 1 and body.index("vk_host::route_query(") < body.index("hipEventRecord(c->ev[0]")
 	assert not re.search(r"\bwp\.gap_mode = [^r]", body) and "does not fit this corpus (LDS)" not in text
+	# wp is built once: every assignment to one of its fields sits in build_wide(), and the one launch under another gap mode -- the
+	# multi-block kernel's -- sets it on a copy (no stage hands wp itself to a launch: each works on a copy of its own)
+	built = body[body.index("void build_wide() {"):body.index("int prepare() {")]
+	assert len(re.findall(r"\bwp\.\w+ = |memcpy\(wp\.", built)) == len(re.findall(r"\bwp\.\w+ = |memcpy\(wp\.", body)) > 0
+	assert "&wp" not in body and re.findall(r"(\w+)\.gap_mode = r\.score32_gap_mode", body) == ["mb"]
+	multi = body[body.index("int score_multi_block() {"):body.index("int score_span() {")]
+	assert "VkWideParams mb = wp;" in multi and re.findall(r"(\w+)\.gap_mode = r\.(?:wide|score32)_gap_mode", body) == ["wp", "mb"]
 
 
 def test_the_names_are_the_headers():

@@ -11,6 +11,8 @@
 //
 //     int vk_query(...) { return vk_run_guarded([&](vk_host_keep &keep) { return query_body(..., keep); }, drain_stream); }
 //
+// (query_body hands the keep to its stages through the query's context, query_run::keep; the helpers of vk_internal.h take it as an argument)
+//
 // Host only, no HIP types: tests/test_guard.py compiles it with g++ and drives it with a fake stream (CPU tier).
 #ifndef VK_GUARD_H
 #define VK_GUARD_H

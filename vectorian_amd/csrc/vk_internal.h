@@ -565,6 +565,62 @@ int64_t row_of_sentence(vk_corpus *c, int64_t s) {
 	return (int64_t)c->sent_entry[(size_t)s];
 }
 
+// ---- what vk_query.cpp and vk_longq_host.cpp both do around a selection (one copy; each caller keeps its own copies and syncs)
+// `ord` (rows of the slice table) longest slice first, rows of one length in the order given: a work list of a one-wave-per-slice pass
+inline void rows_longest_first(const vk_corpus *c, std::vector<int32_t> &ord) {
+	std::stable_sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) {
+		return (*c->h_end)[(size_t)a] - (*c->h_start)[(size_t)a] > (*c->h_end)[(size_t)b] - (*c->h_start)[(size_t)b]; });
+}
+// q->only_slices as keys of rows of the slice table (long slices sit in padded groups: rows != slices) in d_keys[0], in the caller's
+// order.  sync: the stream is synchronised before the return; else the caller's next synchronisation covers the copy (the keys live
+// in the keep).  *h_keys: the keys on the host.
+int upload_listed_keys(vk_corpus *c, const vk_query_desc *q, vk_host_keep &keep, hipStream_t st, bool sync, const uint64_t **h_keys = nullptr) {
+	std::vector<uint64_t> &hk = keep.vec<uint64_t>((size_t)q->n_only);
+	for (int i = 0; i < q->n_only; i++) hk[(size_t)i] = vk_host::key_of_row(row_of_sentence(c, q->only_slices[i]));
+	VK_HIP(hipMemcpyAsync(c->d_keys[0], hk.data(), hk.size() * 8, hipMemcpyHostToDevice, st));
+	if (sync) VK_HIP(hipStreamSynchronize(st));
+	if (h_keys) *h_keys = hk.data();
+	return VK_OK;
+}
+// The host ends of a selection's copies: `cap` keys and aligner scores and, with tracebacks, cap x stride mappings and edge
+// similarities -- taken from the keep once (candidate rounds fetch into the same ones round after round) -- and `sel`, the view of
+// them that the writer of a result set takes
+struct selected_host {
+	std::vector<uint64_t> &keys;
+	std::vector<float> &raw, &sim;
+	std::vector<int16_t> &map;
+	vk_host::selected sel;
+	selected_host(vk_host_keep &keep, const vk_corpus *c, int cap, int stride, bool traced)
+		: keys(keep.vec<uint64_t>((size_t)cap)), raw(keep.vec<float>((size_t)cap)), sim(keep.vec<float>(traced ? (size_t)cap * stride : 0)),
+		  map(keep.vec<int16_t>(traced ? (size_t)cap * stride : 0)) {
+		sel.keys = keys.data(); sel.cap = cap; sel.slice_of_row = slice_of_row(c);
+		if (traced) { sel.raw = raw.data(); sel.map = map.data(); sel.sim = sim.data(); sel.stride = stride; }
+	}
+};
+// The selected keys at d_keys back on the host and, where tracebacks ran, their outputs at d_raw / d_map / d_sim (rows of h's stride)
+// with them; the stream synchronised: h.sel then states the selection
+int fetch_selected(const uint64_t *d_keys, const float *d_raw, const int16_t *d_map, const float *d_sim, selected_host &h, hipStream_t st) {
+	VK_HIP(hipMemcpyAsync(h.keys.data(), d_keys, h.keys.size() * 8, hipMemcpyDeviceToHost, st));
+	if (h.sel.raw) {
+		VK_HIP(hipMemcpyAsync(h.raw.data(), d_raw, h.raw.size() * 4, hipMemcpyDeviceToHost, st));
+		VK_HIP(hipMemcpyAsync(h.map.data(), d_map, h.map.size() * 2, hipMemcpyDeviceToHost, st));
+		VK_HIP(hipMemcpyAsync(h.sim.data(), d_sim, h.sim.size() * 4, hipMemcpyDeviceToHost, st));
+	}
+	VK_HIP(hipStreamSynchronize(st));
+	return VK_OK;
+}
+// The aligner scores of the first `count` selected rows from the scoring pass's array d_raw into h.raw: more than `singles` of them,
+// the whole array in one copy, gathered here; else one float each.  The stream is synchronised.
+int gather_raw(vk_corpus *c, const vk_host::selected &sel, int count, int singles, selected_host &h, vk_host_keep &keep, hipStream_t st) {
+	const bool whole = count > singles;
+	std::vector<float> &all_raw = keep.vec<float>(whole ? (size_t)c->n_entries : 0);
+	if (whole) VK_HIP(hipMemcpyAsync(all_raw.data(), c->d_raw, (size_t)c->n_entries * 4, hipMemcpyDeviceToHost, st));
+	else for (int i = 0; i < count; i++) VK_HIP(hipMemcpyAsync(&h.raw[(size_t)i], c->d_raw + sel.row(i), 4, hipMemcpyDeviceToHost, st));
+	VK_HIP(hipStreamSynchronize(st));
+	for (int i = 0; whole && i < count; i++) h.raw[(size_t)i] = all_raw[(size_t)sel.row(i)];
+	return VK_OK;
+}
+
 // the exact solver over the `count` candidates at w.keys: slices of at most 64 tokens, then (long_too) those of 65 .. 512 tokens
 int launch_wrd_exact_both(vk_corpus *c, VkWrdParams &w, int count, float *scores_to_mark, bool long_too, hipStream_t st) {
 	VK_HIP(vk_launch_wrd_exact(&w, count, scores_to_mark, st));

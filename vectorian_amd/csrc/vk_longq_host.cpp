@@ -102,8 +102,7 @@ int vk_longq_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_
 			if (lq.n_order < 0) {
 				std::vector<int32_t> ord;
 				for (int32_t e : *c->h_apart) if ((*c->h_end)[(size_t)e] - (*c->h_start)[(size_t)e] > VK_FAST_SENT_LEN) ord.push_back(e);
-				std::stable_sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) {
-					return (*c->h_end)[(size_t)a] - (*c->h_start)[(size_t)a] > (*c->h_end)[(size_t)b] - (*c->h_start)[(size_t)b]; });
+				rows_longest_first(c, ord);
 				if ((rc = lq.order.reserve(ord.size() + 1, &c->device_bytes))) return rc;
 				VK_HIP(hipMemcpyAsync(lq.order, ord.data(), ord.size() * 4, hipMemcpyHostToDevice, st));
 				VK_HIP(hipStreamSynchronize(st));
@@ -129,9 +128,7 @@ int vk_longq_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_
 	const float sel_floor = do_flow ? vk_host::restated_floor(q->min_score) : q->min_score;
 	const uint64_t *d_sel = c->d_keys[0];   // the selected keys on the device, best first
 	if (only) {
-		std::vector<uint64_t> &hk = keep.vec<uint64_t>((size_t)q->n_only);
-		for (int i = 0; i < q->n_only; i++) hk[(size_t)i] = vk_host::key_of_row(row_of_sentence(c, q->only_slices[i]));   // (long slices sit in padded groups: rows != slices)
-		VK_HIP(hipMemcpyAsync(c->d_keys[0], hk.data(), hk.size() * 8, hipMemcpyHostToDevice, st));
+		if ((rc = upload_listed_keys(c, q, keep, st, false))) return rc;   // (the fetch below synchronises)
 	} else if ((rc = kk <= 64 ? select_waves(c, sel_floor, kk, st, &d_sel) : select_blocks(c, sel_floor, kk, st, &d_sel))) return rc;
 	VK_HIP(hipEventRecord(c->ev[3], st));
 
@@ -156,27 +153,15 @@ int vk_longq_query(vk_corpus_t *c, const vk_query_desc *q, vk_topk_out *out, vk_
 	VK_HIP(hipEventRecord(c->ev[4], st));
 
 	// ---- results to the host
-	std::vector<uint64_t> &keys = keep.vec<uint64_t>((size_t)kk);
-	std::vector<float> &raw = keep.vec<float>((size_t)kk), &sim = keep.vec<float>(do_flow ? (size_t)kk * LTP : 0);
-	std::vector<int16_t> &map = keep.vec<int16_t>(do_flow ? (size_t)kk * LTP : 0);
-	VK_HIP(hipMemcpyAsync(keys.data(), d_sel, (size_t)kk * 8, hipMemcpyDeviceToHost, st));
-	if (do_flow) {
-		VK_HIP(hipMemcpyAsync(raw.data(), lq.raw, (size_t)kk * 4, hipMemcpyDeviceToHost, st));
-		VK_HIP(hipMemcpyAsync(map.data(), lq.map, map.size() * 2, hipMemcpyDeviceToHost, st));
-		VK_HIP(hipMemcpyAsync(sim.data(), lq.sim, sim.size() * 4, hipMemcpyDeviceToHost, st));
-	}
-	VK_HIP(hipStreamSynchronize(st));
-	vk_host::selected sel;
-	sel.keys = keys.data(); sel.cap = kk; sel.slice_of_row = slice_of_row(c);
-	if (do_flow) { sel.raw = raw.data(); sel.map = map.data(); sel.sim = sim.data(); sel.stride = LTP; }
+	selected_host got(keep, c, kk, LTP, do_flow);
+	vk_host::selected &sel = got.sel;
+	if ((rc = fetch_selected(d_sel, lq.raw, lq.map, lq.sim, got, st))) return rc;
 	vk_host::result_set rs;
 	// the winners' scores from their canonical aligner scores (no submatch weight with such queries)
 	if (do_flow) vk_host::score_selected(sel, rs, q->min_score, only ? q->n_only : k, only, vk_host::by_traceback{sel, LT, q->tag_weights, total, 0.0f, q->boost});
 	else if (vk_host::score_selected(sel, rs, q->min_score, kk, only) > 0 && out->raw_score) {
-		std::vector<float> &all_raw = keep.vec<float>((size_t)n);
-		VK_HIP(hipMemcpyAsync(all_raw.data(), c->d_raw, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-		VK_HIP(hipStreamSynchronize(st));
-		for (int i = 0; i < rs.n_out; i++) rs.raw[(size_t)i] = all_raw[(size_t)sel.row(i)];
+		if ((rc = gather_raw(c, sel, rs.n_out, 0, got, keep, st))) return rc;   // (always the whole array)
+		std::copy(got.raw.begin(), got.raw.begin() + rs.n_out, rs.raw.begin());
 	}
 	vk_host::write_result_set(out, sel, rs, LT, do_flow);
 	c->have_scores = !only;

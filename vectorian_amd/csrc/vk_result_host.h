@@ -81,7 +81,7 @@ constexpr int kCanonMargin = 8;
 inline float restated_floor(float min_score) { return min_score - 1e-5f * std::max(1.0f, std::fabs(min_score)); }
 
 // ---- the writer of a result set.  Every query path ends here: score_selected, then write_result_set; the candidate rounds (exact
-// transports, submatch weight) keep_best, then write_best.  Callers: query_body's four exits, vk_merge_topk and vk_merge_records
+// transports, submatch weight) keep_best, then write_best.  Callers: the four exits of a query (query_run::listed_transports, transport_rounds, submatch_rounds, selected_result), vk_merge_topk and vk_merge_records
 // (vk_query.cpp); vk_longq_query (vk_longq_host.cpp); batch_winner_rows, query_batch_shared_pass, query_batch_span and the GEMM
 // path of query_batch_body (vk_batch.cpp).
 // What came back from the device for one query: `cap` key slots, best first (up to the first empty one); the aligner scores where

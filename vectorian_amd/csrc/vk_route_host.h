@@ -1,6 +1,6 @@
 // vk_route_host.h -- which kernels a query of at most VK_MAX_QUERY_LEN tokens runs on: decided once, on the host, from
-// plain facts about the corpus and the query, before anything is enqueued.  vk_validate_query reads the refusal, query_body
-// (vk_query.cpp) the rest; no other code decides a route.  Host only, no HIP types: tests/test_route_host.py compiles it with g++ and
+// plain facts about the corpus and the query, before anything is enqueued.  vk_validate_query reads the refusal, query_run::route()
+// and the stages after it (vk_query.cpp) the rest; no other code decides a route.  Host only, no HIP types: tests/test_route_host.py compiles it with g++ and
 // enumerates the facts (CPU tier).  Integers a test reads (vk_query_route, vk_corpus.cpp) are the enums below.
 #ifndef VK_ROUTE_HOST_H
 #define VK_ROUTE_HOST_H
@@ -47,8 +47,8 @@ inline int ws_tail_of(const vk_gap &gap_s, int max_len) {
 struct route_switches {
 	bool long_linear = false, long_pass = false, no_doc_mid = false, no_doc_kernel = false, no_doc_flow = false, no_docw = false, no_docg = false;
 	bool no_doc_rwmd = false, no_doc_general = false, keep_raw = false, no_apart = false, no_score32 = false;
-	bool qlds = false, qreg = false, no_f32_special = false, no_qlds1 = false;   // the LDS carve-up of the fused launch (query_body)
-	bool wrd_turns = false, debug_candidates = false;                            // the exact transports' rounds (query_body)
+	bool qlds = false, qreg = false, no_f32_special = false, no_qlds1 = false;   // the LDS carve-up of the fused launch (query_run::score_fused)
+	bool wrd_turns = false, debug_candidates = false;                            // the exact transports' rounds (query_run::transport_rounds)
 };
 inline route_switches read_route_switches() {
 	const auto on = [](const char *name) { return getenv(name) != nullptr; };
